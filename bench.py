@@ -5,14 +5,19 @@ Metric (BASELINE.json): Mcell-updates/s per iteration (residual + LU-SGS) on a
 256^3 block, % of the HBM roofline.  One iteration = one mgSolution::Iterate
 call (src/mgSolution.cpp:246).  The default line is BASELINE configs[2]:
 single 256^3 block, WENO5 + AUSMPW+ + viscous fluxes, implicit Euler with one
-scalar LU-SGS sweep, state resident in HBM.  The same line carries, under
+scalar LU-SGS sweep, state resident in HBM.  With --full the same line carries, under
 "extra"."rk4", the explicit-RK4 residual sweep (MUSCL thirdOrder + vanAlbada +
 Roe, configs[1] at 256^3) that the north-star ">= 40 % of the HBM roofline"
 clause is stated on.  `--workload rk4|dplur8|rans4` make those the headline instead
 (rans4: BASELINE configs[4] in kind -- 4 blocks, k-omega SST 2003, BLU-SGS, a flat plate
 with a boundary-layer start -- on the 7-equation build of the library).
 
-  python bench.py --gpus N --steps K --warmup W
+  python bench.py --gpus N --steps K --warmup W [--dump-outputs DIR] [--full]
+
+A plain run sets up, warms up, times the K steps and prints the line.  `--full` adds
+what takes runs of its own: `extra.rk4` (N = 1) / `extra.dplur8` (N > 1) and the CPU
+oracle's `cpu_baseline`.  `--dump-outputs DIR` writes what the last timed step handed its
+caller as DIR/<name>.npy (see dump_outputs).
 
 N > 1 (launched by torch.distributed.run, one rank per GPU): weak scaling, one
 256^3 block per rank stacked along k and joined by interblock connections; the
@@ -50,6 +55,8 @@ BYTES_RESID_KERNEL = 216   # of which the residual kernel: state 5 + areas 12 +
                            # widths 3 + vol 1 read, residual 5 + dt 1 written
 BYTES_LUSGS_ITER = 1296    # scalar LU-SGS viscous iteration
 BYTES_DPLUR4_ITER = 1960   # inviscid DPLUR, 4 sweeps
+DUMP_CELLS = 1 << 19       # --dump-outputs: cells sampled over all blocks (<= 30 MB at 7 eq.)
+DUMP_SEED = 20240          # fixed: the same cells in every run and every build
 
 
 def deck_kwargs(workload):
@@ -282,9 +289,41 @@ WORKLOAD_TEXT = {
 }
 
 
-def run_workload(args, workload, api, world, rank, local_rank):
+def dump_outputs(path, sol, case, rank, world, l2, linf, mres):
+    """What the last timed Iterate handed its caller, as float64 .npy files in `path`:
+    state_block<b> -- the conserved state of each block this rank holds (b: its global
+    number), physical cells as [cell, equation] in storage order (k slowest); a block with
+    more cells than its share of DUMP_CELLS gives a fixed sample of them, drawn with
+    DUMP_SEED and the block number; rank 0 adds the norms as agx_iterate returns them
+    (reduced over the ranks): residual_l2sq [n_eq], residual_linf [value, block, i, j, k,
+    equation], matrix_residual."""
+    os.makedirs(path, exist_ok=True)
+    share = DUMP_CELLS // (len(sol.block_ids) * world)
+    for gb in sorted(sol.block_ids):
+        blk = case.blocks[gb]
+        ng, dims = blk.geom.ng, (blk.geom.nk, blk.geom.nj, blk.geom.ni)
+        a = sol.download("state", gb)
+        ncell = dims[0] * dims[1] * dims[2]
+        if ncell <= share:
+            out = a[ng:-ng, ng:-ng, ng:-ng].reshape(ncell, -1)
+        else:
+            rng = np.random.default_rng([DUMP_SEED, blk.global_pos])
+            k, j, i = np.unravel_index(np.sort(rng.choice(ncell, share, replace=False)), dims)
+            out = a[k + ng, j + ng, i + ng]
+        np.save(os.path.join(path, f"state_block{blk.global_pos}.npy"),
+                np.ascontiguousarray(out))
+    if rank == 0:
+        np.save(os.path.join(path, "residual_l2sq.npy"), np.asarray(l2, dtype=np.float64))
+        np.save(os.path.join(path, "residual_linf.npy"),
+                np.array([linf.linf, linf.block, linf.i, linf.j, linf.k, linf.eqn],
+                         dtype=np.float64))
+        np.save(os.path.join(path, "matrix_residual.npy"), np.array([mres], dtype=np.float64))
+
+
+def run_workload(args, workload, api, world, rank, local_rank, dump=None):
     """Set the case up, warm up, time `args.steps` iterations; returns the
-    measured quantities of this rank (rank 0 holds the max-over-ranks time)."""
+    measured quantities of this rank (rank 0 holds the max-over-ranks time).
+    dump: a directory for dump_outputs, written after the timed steps."""
     n = args.size
     dims = tuple(int(v) for v in args.dims.split(",")) if args.dims else None
     # the volume-sized parts of the grid set-up (metrics, wall distance) run in the library
@@ -364,6 +403,8 @@ def run_workload(args, workload, api, world, rank, local_rank):
         elapsed = float(t.item())
     if not np.all(np.isfinite(l2)) and not os.environ.get("AGX_ABLATE"):
         raise SystemExit("non-finite residual")
+    if dump:
+        dump_outputs(dump, sol, case, rank, world, l2, linf, mres)
 
     groups = []
     for g in range(7):
@@ -518,9 +559,18 @@ def main():
     ap.add_argument("--warmup", type=int, default=4)
     ap.add_argument("--size", type=int, default=256)
     ap.add_argument("--workload", choices=["rk4", "lusgs", "dplur8", "rans4"], default="lusgs")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure extra.rk4 (N = 1) / extra.dplur8 (N > 1) and the CPU "
+                         "oracle's cpu_baseline (N = 1)")
+    ap.add_argument("--no-cpu-baseline", action="store_true",
+                    help="with --full: skip cpu_baseline")
     ap.add_argument("--no-extra", action="store_true",
-                    help="skip the extra.rk4 (N = 1) / extra.dplur8 (N > 1) measurement")
+                    help="with --full: skip the extra.rk4 (N = 1) / extra.dplur8 (N > 1) "
+                         "measurement")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps write what the last one computed (the state "
+                         "of every block, sampled, and the norms) as DIR/<name>.npy; "
+                         "bench_outputs/ in the repository is ignored by git")
     ap.add_argument("--backend", choices=["nccl", "gloo"], default="nccl",
                     help="gloo stages the halo slabs through the host (rehearsal of "
                          "the multi-rank path with several ranks on one GPU)")
@@ -560,9 +610,11 @@ def main():
         dist.init_process_group("gloo", rank=rank, world_size=world)
 
     api = aither_amd.load(7 if args.workload == "rans4" else 5)
-    res = run_workload(args, args.workload, api, world, rank, local_rank)
+    res = run_workload(args, args.workload, api, world, rank, local_rank,
+                       dump=args.dump_outputs)
     extra = None
-    if args.workload == "lusgs" and world == 1 and not args.no_extra and not args.dims:
+    want_extra = args.full and not args.no_extra and not args.dims
+    if args.workload == "lusgs" and world == 1 and want_extra:
         # the explicit-RK4 residual sweep the ">= 40 % of roofline" target is stated on
         # (48 warm-up stages: the stage kernel runs 1.9 ms right after set-up and settles
         # at 1.46-1.5 ms some 60 ms later -- clocks and TLBs -- see the per-launch times in
@@ -570,8 +622,7 @@ def main():
         rk_args = argparse.Namespace(**vars(args))
         rk_args.steps, rk_args.warmup = max(args.steps, 80), max(args.warmup, 48)
         extra = ("rk4", rk_args, run_workload(rk_args, "rk4", api, world, rank, local_rank))
-    elif (args.workload == "lusgs" and world > 1 and 8 % world == 0 and not args.no_extra
-          and not args.dims):
+    elif args.workload == "lusgs" and world > 1 and 8 % world == 0 and want_extra:
         # the 8-block DPLUR case (BASELINE configs[3], strong scaling) the north-star
         # ">= 6x at 8 GPUs" clause is stated on rides in the same line
         # (a failure of this second case must not cost the line its headline value)
@@ -589,7 +640,7 @@ def main():
             out["extra"] = {extra[0]: {k: e[k] for k in (
                 "metric", "value", "unit", "n_gpus", "steps", "warmup", "ms_per_step",
                 "scaling", "config", "roofline")}}
-        if not args.no_cpu_baseline and world == 1:
+        if args.full and not args.no_cpu_baseline and world == 1:
             out["cpu_baseline"] = cpu_baseline(args.workload)
             if extra is not None:
                 out["extra"]["rk4"]["cpu_baseline"] = cpu_baseline("rk4", budget_s=8.0)

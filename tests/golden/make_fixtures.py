@@ -19,12 +19,18 @@ after a fixed number of iterations.  This script
 
   python tests/golden/make_fixtures.py            verify the committed tree against
                                                   what the reference yields (default)
-  python tests/golden/make_fixtures.py --write    (re)generate the tree
+  python tests/golden/make_fixtures.py --write    (re)generate the tree and manifest.json
+  python tests/golden/make_fixtures.py --manifest verify the committed tree against
+                                                  manifest.json (no reference needed)
+
+manifest.json records the SHA-256 of every file the reference yielded at the last --write;
+the default check compares it with the reference too.
 
 Cases NOT taken: thermallyPerfect, supersonicMixing, dissociation (multi-species /
 thermally perfect / chemistry) -- outside the path.
 """
 import filecmp
+import hashlib
 import json
 import os
 import re
@@ -112,7 +118,36 @@ def generate(ref, dst_root):
     return truths
 
 
+def digests(root):
+    """case -> {file name: SHA-256} of the case directories under root/cases"""
+    out = {}
+    for case in sorted(os.listdir(os.path.join(root, "cases"))):
+        d = os.path.join(root, "cases", case)
+        out[case] = {f: hashlib.sha256(open(os.path.join(d, f), "rb").read()).hexdigest()
+                     for f in sorted(os.listdir(d))}
+    return out
+
+
+def check_manifest():
+    """the committed tree is the one manifest.json recorded: the same case directories,
+    files and bytes, and a truth vector for every case that takes one"""
+    manifest = json.load(open(os.path.join(HERE, "manifest.json")))
+    assert sorted(manifest) == sorted(CASES), (sorted(manifest), sorted(CASES))
+    assert digests(HERE) == manifest, "tests/golden/cases differs from manifest.json"
+    committed = json.load(open(os.path.join(HERE, "regression_truths.json")))
+    truths = {k for k in committed if not k.startswith("_")}
+    assert truths == {c for c, p in CASES.items() if p is not None}, truths
+    for case in truths:
+        assert {"truth", "iterations", "ignore", "line"} <= set(committed[case]), case
+        assert len(committed[case]["truth"]) >= 5, case
+    print(f"tests/golden/ matches manifest.json: {len(manifest)} case directories "
+          f"({sum(len(v) for v in manifest.values())} data files), "
+          f"{len(truths)} truth vectors")
+
+
 def main():
+    if "--manifest" in sys.argv:
+        return check_manifest()
     args = [a for a in sys.argv[1:] if not a.startswith("--")]
     ref = args[0] if args else "/root/reference"
     write = "--write" in sys.argv
@@ -122,6 +157,7 @@ def main():
         for case, t in truths.items():          # keep this repository's annotations
             committed.setdefault(case, {}).update(t)
         json.dump(committed, open(os.path.join(HERE, "regression_truths.json"), "w"), indent=1)
+        json.dump(digests(HERE), open(os.path.join(HERE, "manifest.json"), "w"), indent=1)
         print("wrote", ", ".join(CASES))
         return
     with tempfile.TemporaryDirectory() as tmp:
@@ -132,6 +168,8 @@ def main():
             assert names == sorted(os.listdir(b)), (case, names, sorted(os.listdir(b)))
             _, mismatch, errors = filecmp.cmpfiles(a, b, names, shallow=False)
             assert not mismatch and not errors, (case, mismatch, errors)
+        assert json.load(open(os.path.join(HERE, "manifest.json"))) == digests(tmp), \
+            "manifest.json differs from what the reference yields (rerun with --write)"
     assert sorted(os.listdir(os.path.join(HERE, "cases"))) == sorted(CASES)
     assert {k for k in committed if not k.startswith("_")} == set(truths)
     for case, t in truths.items():

@@ -54,10 +54,63 @@ def test_failing_rank_fails_the_command():
     assert r.returncode != 0
 
 
+def test_dump_outputs_writes_state_and_norms(oracle, tmp_path, monkeypatch):
+    """--dump-outputs (bench.dump_outputs), here after one oracle iteration of the 8-block
+    DPLUR case: every block's physical cells as [cell, equation] and the norms, float64; a
+    block above its share of DUMP_CELLS gives the same seeded sample of cells every time."""
+    import numpy as np
+    sys.path.insert(0, ROOT)
+    import bench
+    from aither_amd.solver import Solver
+    case = bench.rank_local_chain_case(0, 1, 8, "dplur8")       # 8 blocks of 4^3 cells
+    sol = Solver(oracle, case)
+    sol.store_time_n(0)
+    l2, linf, mres = sol.iterate(0, case.deck.cfl(0))
+    bench.dump_outputs(str(tmp_path / "all"), sol, case, 0, 1, l2, linf, mres)
+    monkeypatch.setattr(bench, "DUMP_CELLS", 8 * 10)                # 10 of 64 per block
+    for d in ("a", "b"):
+        bench.dump_outputs(str(tmp_path / d), sol, case, 0, 1, l2, linf, mres)
+    names = sorted(os.listdir(tmp_path / "all"))
+    assert names == sorted(["residual_l2sq.npy", "residual_linf.npy", "matrix_residual.npy"]
+                           + [f"state_block{b}.npy" for b in range(8)])
+    assert sorted(os.listdir(tmp_path / "a")) == names
+    for b in range(8):
+        full = np.load(tmp_path / "all" / f"state_block{b}.npy")
+        g = case.blocks[b].geom.ng
+        want = sol.download("state", b)[g:-g, g:-g, g:-g].reshape(64, 5)
+        assert full.dtype == np.float64 and np.array_equal(full, want)
+        a = np.load(tmp_path / "a" / f"state_block{b}.npy")
+        assert a.shape == (10, 5) and np.array_equal(a, np.load(tmp_path / "b" /
+                                                                f"state_block{b}.npy"))
+        rows = [int(np.flatnonzero((full == r).all(axis=1))[0]) for r in a]
+        assert rows == sorted(set(rows))         # distinct cells, in storage order
+    assert np.array_equal(np.load(tmp_path / "all" / "residual_l2sq.npy"), l2)
+    assert np.load(tmp_path / "all" / "residual_linf.npy")[0] == linf.linf
+    assert np.load(tmp_path / "all" / "matrix_residual.npy")[0] == mres
+    sol.close()
+
+
+@pytest.mark.gpu
+def test_plain_run_times_its_steps_and_dumps_outputs(tmp_path):
+    """A plain run measures the headline only (no extra, no cpu_baseline), times exactly
+    --steps steps and writes the last one's outputs where --dump-outputs says."""
+    import numpy as np
+    r = _run(["--gpus", "1", "--size", "32", "--steps", "3", "--warmup", "1",
+              "--dump-outputs", str(tmp_path)])
+    assert r.returncode == 0, r.stderr[-3000:]
+    line = _json_line(r.stdout)
+    assert line["steps"] == 3 and "extra" not in line and "cpu_baseline" not in line
+    assert line["value"] * line["ms_per_step"] == pytest.approx(32 ** 3 / 1e3)
+    s = np.load(tmp_path / "state_block0.npy")
+    assert s.shape == (32 ** 3, 5) and s.dtype == np.float64 and np.all(np.isfinite(s))
+    l2 = np.load(tmp_path / "residual_l2sq.npy")
+    assert l2.shape == (5,) and np.all(np.isfinite(l2)) and l2.max() > 0
+
+
 @pytest.mark.gpu
 def test_two_ranks_on_one_gpu_plain_command():
     r = _run(["--gpus", "2", "--backend", "gloo", "--size", "32", "--steps", "2",
-              "--warmup", "1", "--no-cpu-baseline"])
+              "--warmup", "1", "--no-cpu-baseline", "--full"])
     assert r.returncode == 0, r.stderr[-3000:]
     line = _json_line(r.stdout)
     assert line["n_gpus"] == 2 and line["steps"] == 2
