@@ -42,10 +42,15 @@ for _q, _c in enumerate(("mass", "mom_x", "mom_y", "mom_z", "energy", "tke", "sd
 c_dp = C.POINTER(C.c_double)
 
 
+THERMO = {"caloricallyPerfect": 0, "thermallyPerfect": 1}
+MAX_VIB = 4     # AGX_MAX_VIB
+
+
 class Gas(C.Structure):
     _fields_ = [(n, C.c_double) for n in (
         "gas_constant", "n", "heat_of_formation", "visc_c1", "visc_s",
-        "cond_c1", "cond_s", "t_ref", "rho_ref", "l_ref", "a_ref")]
+        "cond_c1", "cond_s", "t_ref", "rho_ref", "l_ref", "a_ref")] + [
+        ("n_vib", C.c_int32), ("pad_", C.c_int32), ("theta_v", C.c_double * MAX_VIB)]
 
 
 class Config(C.Structure):
@@ -55,7 +60,8 @@ class Config(C.Structure):
         "nonlinear_iterations", "equation_set", "inv_flux_jacobian",
         "viscous_recon", "turbulence_model")] + [(n, C.c_double) for n in (
             "kappa", "theta", "zeta", "matrix_relaxation", "dual_time_cfl",
-            "dt_nondim", "viscous_cfl_coeff")] + [("gas", Gas)]
+            "dt_nondim", "viscous_cfl_coeff")] + [("gas", Gas)] + [
+        ("thermodynamic_model", C.c_int32), ("pad_", C.c_int32)]
 
 
 class BlockGeom(C.Structure):

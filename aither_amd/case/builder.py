@@ -215,7 +215,8 @@ def build_case(inp_path, grid_dir=None, deck=None, coords=None, ranks=None, setu
         deck = parse_input(inp_path)
     deck.validate()
     fluid_name = deck.fluids[0] if deck.fluids else "air"
-    gas = _fluid.make_gas(fluid_name, deck.t_ref, deck.rho_ref, deck.l_ref)
+    gas = _fluid.make_gas(fluid_name, deck.t_ref, deck.rho_ref, deck.l_ref,
+                          deck.thermodynamic_model)
     if coords is None:
         base = grid_dir or os.path.dirname(os.path.abspath(inp_path))
         coords = _geo.read_plot3d(os.path.join(base, deck.grid_name + ".xyz"),
@@ -304,7 +305,15 @@ def config_struct(case):
     cfg.dt_nondim = d.dt * g.a_ref / g.l_ref if d.dt > 0.0 else -1.0
     cfg.viscous_cfl_coeff = d.viscous_cfl_coefficient()
     for name, _ in abi.Gas._fields_:
+        if name in ("n_vib", "pad_", "theta_v"):
+            continue
         setattr(cfg.gas, name, getattr(g, name))
+    if g.n_vib > abi.MAX_VIB:
+        raise ValueError(f"{g.n_vib} vibrational modes: at most {abi.MAX_VIB} are built")
+    cfg.gas.n_vib = g.n_vib
+    for m, th in enumerate(g.theta_v):
+        cfg.gas.theta_v[m] = th
+    cfg.thermodynamic_model = abi.THERMO[g.thermodynamic_model]
     return cfg
 
 

@@ -195,8 +195,8 @@ class InputDeck:
         if self.equation_set == "rans" and self.turbulence_model not in ("sst2003", "sstdes",
                                                                          "kOmegaWilcox2006"):
             bad.append(f"turbulenceModel {self.turbulence_model}")
-        if self.thermodynamic_model != "caloricallyPerfect":
-            bad.append("thermallyPerfect")
+        if self.thermodynamic_model not in ("caloricallyPerfect", "thermallyPerfect"):
+            bad.append(f"thermodynamicModel {self.thermodynamic_model}")
         if self.multigrid_levels != 1:
             bad.append("multigrid")
         if self.matrix_solver not in ("lusgs", "dplur", "blusgs", "bdplur"):

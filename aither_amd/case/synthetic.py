@@ -49,6 +49,7 @@ def make_deck(**kw):
     d = InputDeck()
     d.rho_ref, d.t_ref, d.l_ref = 1.225, 288.15, kw.get("l_ref", 1.0)
     d.equation_set = kw.get("equation_set", "euler")
+    d.thermodynamic_model = kw.get("thermodynamic_model", "caloricallyPerfect")
     d.time_integration = kw.get("time_integration", "rk4")
     if d.time_integration == "bdf2":
         d.theta, d.zeta = 1.0, 0.5

@@ -287,6 +287,12 @@ int derive_gas(const agx_config& cfg, GasDev& g) {
   g.mu_ref = a.visc_c1 * pow(a.t_ref, 1.5) / (a.t_ref + a.visc_s);  // transport.cpp:58-59
   g.k_nondim = (a.a_ref * a.a_ref * g.mu_ref) / a.t_ref;            // :67
   g.scaling = g.mu_ref / (a.rho_ref * a.a_ref * a.l_ref);            // transport.hpp:43-46
+#if AGX_TPG
+  // thermallyPerfect (thermodynamic.hpp:125-189): cp, cv, gamma, Pr above are the frozen
+  // (n_vib = 0) values and are not read; the kernels take them from T
+  g.n_vib = a.n_vib;
+  for (int m = 0; m < AGX_MAX_VIB; ++m) g.theta_v[m] = m < a.n_vib ? a.theta_v[m] : 0.0;
+#endif
   return 0;
 }
 
@@ -467,6 +473,10 @@ int check_device_error(agx_ctx* c) {
     hipMemsetAsync(c->err_dev, 0, sizeof(int), c->stream);
     if (code == 3)
       return fail("Singular matrix in Gauss-Jordan elimination!");   // matrix.cpp:81
+    if (code == AGX_ERR_TPG_ENERGY)
+      return fail("thermallyPerfect: the temperature of a cell's specific energy was not "
+                  "found (Newton's method did not converge in %d steps, or the energy lies "
+                  "below the heat of formation)", AGX_TPG_NEWTON_MAX);
     if (code == 2) {
       c->pipe_nblocks = 0;   // (the progress words of an abandoned launch: set up afresh)
       return fail("LU-SGS pipeline: a k-plane waited beyond the spin limit for its "
@@ -1145,7 +1155,13 @@ int update_pass(agx_ctx* c, int mode, int mm, double* l2, agx_linf* linf) {
 extern "C" {
 
 const char* agx_last_error(void) { return g_err; }
-const char* agx_version(void) { return "aither_gfx950 0.1 (HIP, gfx950)"; }
+const char* agx_version(void) {
+#if AGX_TPG
+  return "aither_gfx950 0.1 (HIP, gfx950, thermallyPerfect)";
+#else
+  return "aither_gfx950 0.1 (HIP, gfx950)";
+#endif
+}
 
 int agx_ctx_create(int device, int rank, agx_ctx** out) {
   int ndev = 0;
@@ -1287,6 +1303,24 @@ int agx_config_set(agx_ctx* c, const agx_config* cfg) {
                 "navierStokes, libaither_gfx950.so; 7: rans, libaither_gfx950_rans.so)",
                 cfg->n_eq, AGX_NEQ);
   if (cfg->n_ghost < 1 || cfg->n_ghost > 3) return fail("n_ghost out of range");
+#if AGX_TPG
+  if (cfg->thermodynamic_model != AGX_THERMO_THERMALLY_PERFECT)
+    return fail("thermodynamic_model %d: this library is built for the thermally perfect gas "
+                "(caloricallyPerfect: %s)", cfg->thermodynamic_model,
+                AGX_NEQ == 7 ? "libaither_gfx950_rans.so" : "libaither_gfx950.so");
+  if (cfg->gas.n_vib < 0 || cfg->gas.n_vib > AGX_MAX_VIB)
+    return fail("gas.n_vib = %d: 0 to %d vibrational modes are built", cfg->gas.n_vib,
+                AGX_MAX_VIB);
+  for (int m = 0; m < cfg->gas.n_vib; ++m)
+    if (!(cfg->gas.theta_v[m] > 0.0))
+      return fail("gas.theta_v[%d] = %g: vibrational temperatures are positive", m,
+                  cfg->gas.theta_v[m]);
+#else
+  if (cfg->thermodynamic_model != AGX_THERMO_CALORICALLY_PERFECT)
+    return fail("thermodynamic_model %d: this library is built for the calorically perfect "
+                "gas (thermallyPerfect: %s)", cfg->thermodynamic_model,
+                AGX_NEQ == 7 ? "libaither_gfx950_rans_tp.so" : "libaither_gfx950_tp.so");
+#endif
   // Never substitute: a scheme this build does not implement is an error here,
   // not a different scheme silently (mgSolution.hpp:112-115 must mean the same).
 #if AGX_NEQ == 7
@@ -1333,6 +1367,9 @@ int agx_config_set(agx_ctx* c, const agx_config* cfg) {
   c->gas.wilcox = cfg->turbulence_model == AGX_TURB_KW_WILCOX2006 ? 1 : 0;
   c->gas.sstdes = cfg->turbulence_model == AGX_TURB_SST_DES ? 1 : 0;
   c->gas.turb_prandtl = c->gas.wilcox ? 8.0 / 9.0 : 0.9;
+#if AGX_TPG
+  c->gas.err = c->err_dev;
+#endif
   SolverDev& sp = c->sp;
   sp.diag_add = 0;
   sp.kappa = cfg->kappa;

@@ -13,6 +13,10 @@
 #ifndef AGX_NEQ
 #define AGX_NEQ 5
 #endif
+// AGX_TPG 1: thermally perfect gas (libaither_gfx950[_rans]_tp.so); 0: calorically perfect
+#ifndef AGX_TPG
+#define AGX_TPG 0
+#endif
 #define AGX_EPS 1.0e-30  // include/macros.hpp.in:20
 #define AGX_TURB_MIN 1.0e-20
 
@@ -37,7 +41,16 @@ struct GasDev {
   int wilcox;
   int sstdes;      // turbSstDes: SST 2003 whose k destruction is scaled by phi (turbulence.hpp:616-656)
   double turb_prandtl;
+#if AGX_TPG
+  // (thermally perfect builds only: the calorically perfect kernels' argument layout is
+  // unchanged) vibrational temperatures / t_ref, and the context's device error flag, raised
+  // by temperature_from_energy when its root is not found
+  int n_vib;
+  double theta_v[AGX_MAX_VIB];
+  int* err;
+#endif
 };
+#define AGX_ERR_TPG_ENERGY 5   // device error flag: temperature from energy did not converge
 
 struct Prim {  // primitive: rho, u, v, w, p  (varArray.hpp:40-51)
   double v[AGX_NEQ];
@@ -64,23 +77,153 @@ __device__ __forceinline__ double fast_rsqrt(double x) {
 }
 __device__ __forceinline__ double fast_sqrt(double x) { return x * fast_rsqrt(x); }
 
+// ---- thermodynamics: every use of a gas property goes through these ------------------
+// AGX_TPG 0 (caloricallyPerfect, thermodynamic.hpp:85-121): constants resolved on the host,
+// each function is the expression the kernels have always used.  AGX_TPG 1
+// (thermallyPerfect, thermodynamic.hpp:125-189): with x = theta / T, em = exp(-x),
+//   e(T)  = hf + n R T + R sum theta em / (1 - em)
+//   cv(T) = n R + R sum x^2 em / (1 - em)^2          (= (t / sinh t)^2, t = x / 2)
+// 1 - em by expm1 (no cancellation at high T); both terms are bounded for every T > 0.
+// The ideal-gas law is unchanged: T = p / (rho R) wherever the primitive state is at hand.
+
 // idealGas::Temperature eos.cpp:100-109
 __device__ __forceinline__ double temperature(const GasDev& g, const double* s) {
   return s[4] * fast_rcp(s[0] * g.R);
 }
+#if AGX_TPG
+// VibEqTerm / VibEqCpCvTerm thermodynamic.hpp:140-157: sum over the modes of
+// theta em / (1 - em) (ev) and x^2 em / (1 - em)^2 (cvv)
+__device__ __forceinline__ void vib_terms(const GasDev& g, double t, double& ev, double& cvv) {
+  ev = 0.0;
+  cvv = 0.0;
+  const double it = 1.0 / t;
+  for (int m = 0; m < g.n_vib; ++m) {
+    const double th = g.theta_v[m];
+    const double x = th * it;
+    const double em = exp(-x);
+    const double om = -expm1(-x);
+    const double r = em / om;
+    ev += th * r;
+    cvv += x * x * r / om;
+  }
+}
+__device__ __forceinline__ double vib_energy(const GasDev& g, double t) {
+  double ev, cvv;
+  vib_terms(g, t, ev, cvv);
+  return ev;
+}
+#endif
+// SpeciesCv / SpeciesCp thermodynamic.hpp:110-113, :180-187
+__device__ __forceinline__ double cv_of(const GasDev& g, double t) {
+#if AGX_TPG
+  double ev, cvv;
+  vib_terms(g, t, ev, cvv);
+  return g.R * (g.n + cvv);
+#else
+  return g.cv;
+#endif
+}
+__device__ __forceinline__ double cp_of(const GasDev& g, double t) {
+#if AGX_TPG
+  return cv_of(g, t) + g.R;
+#else
+  return g.cp;
+#endif
+}
+// thermodynamic::Gamma, Prandtl thermodynamic.hpp:55-64
+__device__ __forceinline__ double gamma_of(const GasDev& g, double t) {
+#if AGX_TPG
+  const double cv = cv_of(g, t);
+  return (cv + g.R) / cv;
+#else
+  return g.gamma;
+#endif
+}
+__device__ __forceinline__ double prandtl_of(const GasDev& g, double t) {
+#if AGX_TPG
+  const double gm = gamma_of(g, t);
+  return (4.0 * gm) / (9.0 * gm - 5.0);
+#else
+  return g.prandtl;
+#endif
+}
+__device__ __forceinline__ double inv_prandtl_of(const GasDev& g, double t) {
+#if AGX_TPG
+  const double gm = gamma_of(g, t);
+  return (9.0 * gm - 5.0) / (4.0 * gm);
+#else
+  return g.inv_prandtl;
+#endif
+}
+// SpeciesSpecEnergy / SpeciesSpecEnthalpy thermodynamic.hpp:101-106, :170-177
+__device__ __forceinline__ double spec_energy(const GasDev& g, double t) {
+#if AGX_TPG
+  return g.hf + g.n * g.R * t + g.R * vib_energy(g, t);
+#else
+  return g.hf + g.cv * t;
+#endif
+}
+__device__ __forceinline__ double spec_enthalpy(const GasDev& g, double t) {
+#if AGX_TPG
+  return g.hf + (g.n + 1.0) * g.R * t + g.R * vib_energy(g, t);
+#else
+  return g.hf + g.cp * t;
+#endif
+}
+// TemperatureFromSpecEnergy thermodynamic.cpp:108-114 (calorically perfect) and :132-141
+// (thermally perfect).  The reference brackets the root of e(T) - e with Ridders' method;
+// here Newton's method from the frozen guess T0 = (e - hf) / (n R): e(T) is increasing and
+// convex and e(T0) >= e, so the iterates fall monotonically onto the root (2-4 steps at
+// the truth case's states).  A root not found within AGX_TPG_NEWTON_MAX steps raises the
+// context's error flag (agx_iterate fails with a message): no silent NaN.
+#define AGX_TPG_NEWTON_MAX 50
+__device__ inline double temperature_from_energy(const GasDev& g, double e) {
+#if AGX_TPG
+  const double nr = g.n * g.R;
+  double t = (e - g.hf) / nr;
+  if (t > 0.0) {
+    for (int it = 0; it < AGX_TPG_NEWTON_MAX; ++it) {
+      double ev, cvv;
+      vib_terms(g, t, ev, cvv);
+      const double dt = (g.hf + nr * t + g.R * ev - e) / (g.R * (g.n + cvv));
+      t -= dt;
+      if (fabs(dt) <= 1.0e-14 * t) return t;
+    }
+  }
+  *g.err = AGX_ERR_TPG_ENERGY;
+  return t;
+#else
+  return (e - g.hf) * g.inv_n / g.R;
+#endif
+}
 // SpeedOfSound arrayView.hpp:383-391
 __device__ __forceinline__ double sound_speed(const GasDev& g, const double* s) {
+#if AGX_TPG
+  return fast_sqrt(gamma_of(g, temperature(g, s)) * s[4] * fast_rcp(s[0]));
+#else
   return fast_sqrt(g.gamma * s[4] * fast_rcp(s[0]));
+#endif
 }
 // rho * H = rho (hf + cp T + |v|^2/2) with rho cp T = (n+1) p: no division,
 // no sqrt (EnthalpyFunc arrayView.hpp:401-409 takes |v| by sqrt and squares
-// it again, eos.cpp:80-84 -- a last-ulp difference, inside the 1e-10 budget)
+// it again, eos.cpp:80-84 -- a last-ulp difference, inside the 1e-10 budget);
+// thermally perfect: + rho R (vibrational energy of T)
 __device__ __forceinline__ double rho_enthalpy(const GasDev& g, const double* s) {
+#if AGX_TPG
+  return s[0] * (g.hf + 0.5 * dot3(s + 1, s + 1)) + (g.n + 1.0) * s[4] +
+         s[0] * g.R * vib_energy(g, temperature(g, s));
+#else
   return s[0] * (g.hf + 0.5 * dot3(s + 1, s + 1)) + (g.n + 1.0) * s[4];
+#endif
 }
 // rho * E (InternalEnergy arrayView.hpp:434-443): rho cv T = n p
 __device__ __forceinline__ double rho_energy(const GasDev& g, const double* s) {
+#if AGX_TPG
+  return s[0] * (g.hf + 0.5 * dot3(s + 1, s + 1)) + g.n * s[4] +
+         s[0] * g.R * vib_energy(g, temperature(g, s));
+#else
   return s[0] * (g.hf + 0.5 * dot3(s + 1, s + 1)) + g.n * s[4];
+#endif
 }
 // PrimToCons primitive.hpp:183-201
 __device__ __forceinline__ void prim_to_cons(const GasDev& g, const double* s,
@@ -103,8 +246,13 @@ __device__ __forceinline__ void cons_to_prim(const GasDev& g, const double* u,
   s[1] = u[1] * ir;
   s[2] = u[2] * ir;
   s[3] = u[3] * ir;
+#if AGX_TPG
+  // p = rho R T with T from the specific internal energy E/rho - |v|^2/2 (eos.cpp:40-52)
+  s[4] = rho * g.R * temperature_from_energy(g, u[4] * ir - 0.5 * dot3(s + 1, s + 1));
+#else
   // p = rho R T, T = (E/rho - |v|^2/2 - hf) / cv  =>  p = (rhoE - rho(...)) / n
   s[4] = (u[4] - rho * (g.hf + 0.5 * dot3(s + 1, s + 1))) * g.inv_n;
+#endif
   // turbulence variables with primitive::LimitTurb (primitive.cpp:100-106;
   // turbModel::TkeMin / OmegaMin turbulence.hpp:72-73)
 #pragma unroll
@@ -331,8 +479,15 @@ __device__ __forceinline__ void roe_flux(const GasDev& g, const double* l,
   for (int e = 1; e < AGX_NEQ; ++e) roe[e] = (l[e] + dr * r[e]) * inv1;
   const double p_rho = roe[4] * fast_rcp(roe[0]);
   const double v2R = dot3(roe + 1, roe + 1);
+#if AGX_TPG
+  // T_roe = p_roe / (rho_roe R); h and a from it (inviscidFlux.hpp:274-276)
+  const double tR = p_rho * fast_rcp(g.R);
+  const double hR = spec_enthalpy(g, tR) + 0.5 * v2R;
+  const double a2 = gamma_of(g, tR) * p_rho;
+#else
   const double hR = g.hf + (g.n + 1.0) * p_rho + 0.5 * v2R;
   const double a2 = g.gamma * p_rho;
+#endif
   const double ia = fast_rsqrt(a2);
   const double aR = a2 * ia;
   const double inv_a2 = ia * ia;
@@ -397,8 +552,15 @@ __device__ __forceinline__ void ausm_flux(const GasDev& g, const double* l,
                                           double* f) {
   const double vnL = dot3(l + 1, n), vnR = dot3(r + 1, n);
   // sqrt(cL cR) = (gamma^2 pL pR / (rhoL rhoR))^(1/4)
+#if AGX_TPG
+  // sqrt(cL cR), each with gamma of its own temperature (inviscidFlux.hpp:426-435)
+  const double cS = fast_sqrt(fast_sqrt(gamma_of(g, temperature(g, l)) *
+                                        gamma_of(g, temperature(g, r)) * (l[4] * r[4]) *
+                                        fast_rcp(l[0] * r[0])));
+#else
   const double cS = fast_sqrt(fast_sqrt(g.gamma * g.gamma * (l[4] * r[4]) *
                                         fast_rcp(l[0] * r[0])));
+#endif
   const double vel = 0.5 * (vnL + vnR);
   double c = cS;
   if (vel < 0.0) c = cS * cS * fast_rcp(fmax(vnR, cS));
@@ -451,7 +613,18 @@ __device__ __forceinline__ double inv_cell_spec_rad(const GasDev& g,
   const double fmag = 0.5 * (al[3] + au[3]);
   return (fabs(dot3(s + 1, v)) * im + sound_speed(g, s)) * fmag;
 }
-// viscous term of ViscCell/FaceSpectralRadius spectralRadius.hpp:94-160
+// viscous term of ViscCell/FaceSpectralRadius spectralRadius.hpp:94-160 (gamma and Pr of
+// the cell's temperature t)
+__device__ __forceinline__ double visc_max_term(const GasDev& g, double rho, double t) {
+  const double ir = fast_rcp(rho);
+  return fmax((4.0 / 3.0) * ir, gamma_of(g, t) * ir);
+}
+__device__ __forceinline__ double visc_term(const GasDev& g, double mu, double t) {
+  return g.scaling * (mu * inv_prandtl_of(g, t));
+}
+#if !AGX_TPG
+// the same with the constant gamma and Pr (calorically perfect builds: the tiled and
+// diagonal-ordered kernels, AGX_FAST, which keep no temperature)
 __device__ __forceinline__ double visc_max_term(const GasDev& g, double rho) {
   const double ir = fast_rcp(rho);
   return fmax((4.0 / 3.0) * ir, g.gamma * ir);
@@ -459,6 +632,7 @@ __device__ __forceinline__ double visc_max_term(const GasDev& g, double rho) {
 __device__ __forceinline__ double visc_term(const GasDev& g, double mu) {
   return g.scaling * (mu * g.inv_prandtl);
 }
+#endif
 
 // sigma_k / sigma_w of the k / omega diffusion (SST: blended; Wilcox: sigmaStar, sigma) and
 // the eddy viscosity of that diffusion and of the turbulence spectral radii: the limited
@@ -496,9 +670,12 @@ __device__ __forceinline__ void off_diagonal(const GasDev& g, bool viscous,
   phys_flux(g, s, area, fo);
   phys_flux(g, su, area, fn);
   double sr = 0.5 * area[3] * (fabs(dot3(s + 1, area)) + sound_speed(g, s));
-  if (viscous)
-    sr += area[3] * fast_rcp(dist) * visc_max_term(g, s[0]) *
-          (AGX_NEQ > 5 ? g.scaling * (mu * g.inv_prandtl + mut / g.turb_prandtl) : visc_term(g, mu));
+  if (viscous) {
+    const double t = temperature(g, s);
+    sr += area[3] * fast_rcp(dist) * visc_max_term(g, s[0], t) *
+          (AGX_NEQ > 5 ? g.scaling * (mu * inv_prandtl_of(g, t) + mut / g.turb_prandtl)
+                       : visc_term(g, mu, t));
+  }
   const double sg = positive ? 1.0 : -1.0;
 #pragma unroll
   for (int e = 0; e < 5; ++e)
@@ -524,12 +701,13 @@ __device__ inline void inv_flux_jacobian(const GasDev& g, const double* s, const
                                          double* J) {
   const double* n = area;
   const double vn = dot3(s + 1, n);
-  const double gm1 = g.gamma - 1.0;
+  const double gamma = gamma_of(g, temperature(g, s));   // fluxJacobian.hpp:499
+  const double gm1 = gamma - 1.0;
   const double phi = 0.5 * gm1 * dot3(s + 1, s + 1);
   double u[AGX_NF];
   prim_to_cons(g, s, u);
-  const double a1 = g.gamma * (u[4] * fast_rcp(s[0])) - phi;    // primitive::Energy
-  const double a3 = g.gamma - 2.0;
+  const double a1 = gamma * (u[4] * fast_rcp(s[0])) - phi;    // primitive::Energy
+  const double a3 = gamma - 2.0;
 #pragma unroll
   for (int q = 0; q < AGX_NJ; ++q) J[q] = 0.0;
   J[0] = vn * (1.0 - 1.0);
@@ -548,7 +726,7 @@ __device__ inline void inv_flux_jacobian(const GasDev& g, const double* s, const
     J[AGX_NF * 4 + 1 + c] = a1 * n[c] - gm1 * s[1 + c] * vn;
     J[AGX_NF * (1 + c) + 4] = gm1 * n[c];
   }
-  J[AGX_NF * 4 + 4] = g.gamma * vn;
+  J[AGX_NF * 4 + 4] = gamma * vn;
   const double h = 0.5 * area[3];
 #pragma unroll
   for (int q = 0; q < AGX_NJ; ++q) J[q] *= h;
@@ -576,7 +754,7 @@ __device__ inline void tsl_jacobian(const GasDev& g, const double* s, double lam
   const double vn = dot3(s + 1, n);
   const double rho = s[0];
   const double k = conductivity(g, t) * g.scaling +
-                   (AGX_NEQ > 5 ? mut * g.cp / g.turb_prandtl : 0.0);
+                   (AGX_NEQ > 5 ? mut * cp_of(g, t) / g.turb_prandtl : 0.0);
   const double lambda = 0.0 - (2.0 / 3.0) * mu;
   const double trace = vg[0] + vg[4] + vg[8];
   double tau[3];
@@ -606,7 +784,7 @@ __device__ inline void tsl_jacobian(const GasDev& g, const double* s, double lam
   }
   T4[0] = (-k * t * imr + 0.0) * sc;
   T4[4] = (k * imr) * sc;
-  const double gm1 = g.gamma - 1.0;
+  const double gm1 = gamma_of(g, t) - 1.0;      // fluxJacobian.hpp:625
   double Pq0[3], P4q[3];
 #pragma unroll
   for (int q = 0; q < 3; ++q) { Pq0[q] = -ir * s[1 + q]; P4q[q] = -gm1 * s[1 + q]; }
@@ -807,7 +985,12 @@ struct WallLawDev {
       set_wall_vars(t_int + recovery * u_star * u_star * uplus * uplus /
                                 (2.0 * cp + heat_flux * mu_w / (rho_w * k_w * u_star)));
     }
+#if AGX_TPG
+    // UpdateGamma :202-207: cp of the wall temperature
+    gamma = recovery * u_star * u_star / (2.0 * cp_of(*gas, tw) * tw);
+#else
     gamma = recovery * u_star * u_star / (2.0 * cp * tw);
+#endif
     if (mode == 2) {     // IsothermalBCs :170-172, CalcHeatFlux :223-229
       const double tmp = (t_int / tw - 1.0 + gamma * uplus * uplus) / uplus;
       heat_flux = tmp * (rho_w * tw * k_w * u_star) / mu_w;
@@ -841,9 +1024,14 @@ __device__ inline void wall_law_solve(const GasDev& g, const double* s, double w
   w.vel_tan = sqrt(dot3(vt, vt));
   const double t = s[4] / (s[0] * g.R);
   w.t_int = t;
-  w.recovery = pow(g.prandtl, 1.0 / 3.0);
+#if AGX_TPG
+  // cp and Pr of the interior temperature: Crocco-Busemann (:49-50, CalcWallTemperature
+  // :231-237) and CalcRecoveryFactor :287-290
+  w.cp = cp_of(g, t);
+#endif
+  w.recovery = pow(prandtl_of(g, t), 1.0 / 3.0);
   if (mode == 0) {          // wall temperature from Crocco-Busemann, adiabatic
-    w.set_wall_vars(t + 0.5 * w.recovery * w.vel_tan * w.vel_tan / g.cp);
+    w.set_wall_vars(t + 0.5 * w.recovery * w.vel_tan * w.vel_tan / cp_of(g, t));
   } else if (mode == 1) {   // guess: wall temperature equals interior temperature
     w.heat_flux = wall_value;
     w.set_wall_vars(t);
@@ -930,7 +1118,7 @@ __device__ inline bool ghost_state(const GasDev& g, const double* in, int bc,
             // the wall law's heat flux with the turbulent conductivity (the eddy viscosity
             // is not zero at the wall), 2 x wall distance as gradient length :161-172
             const double kappa = conductivity(g, w.temperature) +
-                                 w.turb_eddy_visc * g.cp / g.turb_prandtl;
+                                 w.turb_eddy_visc * cp_of(g, w.temperature) / g.turb_prandtl;
             tg = d.wall_temperature - w.heat_flux / kappa * 2.0 * wall_dist;
           }
         }
@@ -1044,7 +1232,8 @@ __device__ inline bool ghost_state(const GasDev& g, const double* in, int bc,
         for (int e = 0; e < AGX_NEQ; ++e) gh[e] = layer * gh[e] - in[e];
       return true;
     case AGX_BC_STAGNATION_INLET: {
-      const double gm1 = g.gamma - 1.0;
+      const double gamma = gamma_of(g, temperature(g, in));   // ghostStates.cpp:538-540
+      const double gm1 = gamma - 1.0;
       const double c = sound_speed(g, in);
       const double vn = dot3(in + 1, n);
       const double v2 = dot3(in + 1, in + 1);
@@ -1056,7 +1245,7 @@ __device__ inline bool ghost_state(const GasDev& g, const double* in, int bc,
           (1.0 + ct * sqrt(k * c0sq / (gm1 * rneg * rneg) - 0.5 * gm1));
       const double ratio = cb * cb / c0sq;
       const double tb = d.stagnation_temperature * ratio;
-      const double pb = d.stagnation_pressure * pow(ratio, g.gamma / gm1);
+      const double pb = d.stagnation_pressure * pow(ratio, gamma / gm1);
       const double vb = sqrt(2.0 / gm1 * (d.stagnation_temperature - tb));
       gh[0] = pb / (g.R * tb);
       gh[1] = vb * d.direction[0];
@@ -1100,7 +1289,7 @@ __device__ inline bool ghost_state(const GasDev& g, const double* in, int bc,
           tv[q] = (nr->pg[q] - pgn * n[q]) - rcN * dvn[q];
         }
         const double dvt = sum - (dvn[0] + dvn[1] + dvn[2]);
-        const double trans = -0.5 * (dot3(velT, tv) + g.gamma * sn[4] * dvt);
+        const double trans = -0.5 * (dot3(velT, tv) + gamma_of(g, temperature(g, sn)) * sn[4] * dvt);
         gh[4] = (sn[4] + rcN * dot3(dv, n) + nr->dt * kk * d.pressure -
                  nr->dt * nr->avg_mach * trans) / (1.0 + nr->dt * kk);
       }

@@ -112,7 +112,8 @@ enum {
 };
 // the LDS-tiled / diagonal-ordered production kernels are written for the
 // 5-equation set; the 7-equation build runs on the one-thread-per-cell kernels
-#define AGX_FAST (AGX_NEQ == 5)
+// (and for the calorically perfect gas: the thermally perfect builds run the general kernels)
+#define AGX_FAST (AGX_NEQ == 5 && !AGX_TPG)
 struct SlabDev {               // compact view used by the marching kernel
   double* base;
   long nplane, sx, sxy;
@@ -1387,7 +1388,8 @@ k_visc_residual(BlockDev b, GasDev g, SolverDev sp, double cfl, int fourth) {
   double diag = sp.implicit ? b.a[q] : 0.0;
   double sc[AGX_NEQ];
   load5(b.state, q, sc);
-  const double muc = viscosity(g, temperature(g, sc));
+  const double tc = temperature(g, sc);
+  const double muc = viscosity(g, tc);
   const double vol = b.vol[q];
 #pragma unroll
   for (int d = 0; d < 3; ++d) {
@@ -1401,7 +1403,7 @@ k_visc_residual(BlockDev b, GasDev g, SolverDev sp, double cfl, int fourth) {
     for (int e = 0; e < AGX_NEQ; ++e) res[e] -= f[e];
     // ViscCellSpectralRadius spectralRadius.hpp:94-124
     const double fmag = 0.5 * (b.fa[d][3][q] + b.fa[d][3][q + s]);
-    const double vsr = visc_max_term(g, sc[0]) * visc_term(g, muc) * fmag * fmag / vol;
+    const double vsr = visc_max_term(g, sc[0], tc) * visc_term(g, muc, tc) * fmag * fmag / vol;
     sr += vsr * sp.visc_cfl_coeff;
     diag += 2.0 * vsr;
   }
@@ -1625,8 +1627,9 @@ __device__ inline void rans_face(const BlockDev& b, const GasDev& g, int d, int 
                         (grad[r][2] + grad[2][r]) * n[2];
       tau[r] = lambda * trace * n[r] + (mu + mt) * mm;
     }
-    const double kk = conductivity(g, temperature(g, sf)) * g.scaling;
-    const double kt = mt * g.cp / g.turb_prandtl;
+    const double tf = temperature(g, sf);
+    const double kk = conductivity(g, tf) * g.scaling;
+    const double kt = mt * cp_of(g, tf) / g.turb_prandtl;     // transport.hpp:136
     const double tg = grad[0][3] * n[0] + grad[1][3] * n[1] + grad[2][3] * n[2];
     // UseUnlimitedEddyVisc (Wilcox): the k / omega diffusion takes rho k / omega
     const double mtt = g.scaling * turb_diff_visc(g, sf, o.mut);
@@ -1697,8 +1700,10 @@ __device__ inline void rans_cell_jac_begin(const BlockDev& b, const SolverDev& s
 __device__ inline void rans_cell_direction(const BlockDev& b, const GasDev& g,
                                            const SolverDev& sp, int d, long q, RansCell& c) {
   const double fmag = 0.5 * (b.fa[d][3][q] + b.fa[d][3][q + b.stride(d)]);
-  const double vsr = visc_max_term(g, c.sc[0]) *
-                     (g.scaling * (c.muc * g.inv_prandtl + c.mut_lo / g.turb_prandtl)) * fmag * fmag / c.vol;
+  const double tc = temperature(g, c.sc);
+  const double vsr = visc_max_term(g, c.sc[0], tc) *
+                     (g.scaling * (c.muc * inv_prandtl_of(g, tc) + c.mut_lo / g.turb_prandtl)) *
+                     fmag * fmag / c.vol;
   c.sr += vsr * sp.visc_cfl_coeff;
   c.diag += 2.0 * vsr;
   const double tvsr = g.scaling * (fmag * fmag / c.vol) / c.sc[0] *
@@ -1954,7 +1959,8 @@ k_visc_march(BlockDev b, GasDev g, SolverDev sp, double cfl, int kchunk) {
       }
       double sc[AGX_NEQ];
       load5(b.state, q, sc);
-      const double muc = viscosity(g, temperature(g, sc));
+      const double tc = temperature(g, sc);
+      const double muc = viscosity(g, tc);
       const double vol = b.vol[q];
       double sr = b.specrad[q];
       double diag = sp.implicit ? b.a[q] : 0.0;
@@ -1962,7 +1968,7 @@ k_visc_march(BlockDev b, GasDev g, SolverDev sp, double cfl, int kchunk) {
       for (int d = 0; d < 3; ++d) {
         // ViscCellSpectralRadius spectralRadius.hpp:94-124
         const double fmag = 0.5 * (b.fa[d][3][q] + b.fa[d][3][q + b.stride(d)]);
-        const double vsr = visc_max_term(g, sc[0]) * visc_term(g, muc) * fmag * fmag / vol;
+        const double vsr = visc_max_term(g, sc[0], tc) * visc_term(g, muc, tc) * fmag * fmag / vol;
         sr += vsr * sp.visc_cfl_coeff;
         diag += 2.0 * vsr;
       }
@@ -3433,9 +3439,17 @@ k_output_pack(BlockDev b, GasDev g, OutSpec sp, const double* __restrict__ grads
   const double rR = sp.rho_ref, aR = sp.a_ref, lR = sp.l_ref, tR = sp.t_ref, muR = sp.mu_ref;
   // plain division / sqrt: an output path, the values go to a file
   const double t = s[4] / (s[0] * g.R);
-  const double cs = sqrt(g.gamma * s[4] / s[0]);
   const double v2 = dot3(s + 1, s + 1);
+#if AGX_TPG
+  // output.cpp:236-274 with the gas properties of T
+  const double cv = cv_of(g, t), cp = cv + g.R;
+  const double cs = sqrt(cp / cv * s[4] / s[0]);
+  const double en = spec_energy(g, t) + 0.5 * v2;
+#else
+  const double cp = g.cp, cv = g.cv;
+  const double cs = sqrt(g.gamma * s[4] / s[0]);
   const double en = g.hf + g.n * s[4] / s[0] + 0.5 * v2;       // Energy: e(T) + |v|^2 / 2
+#endif
   for (int v = 0; v < sp.nvar; ++v) {
     const int var = sp.var[v];
     double val = 0.0;
@@ -3451,8 +3465,8 @@ k_output_pack(BlockDev b, GasDev g, OutSpec sp, const double* __restrict__ grads
       case AGX_OUT_TEMPERATURE: val = t * tR; break;
       case AGX_OUT_ENERGY: val = en * aR * aR; break;
       case AGX_OUT_ENTHALPY: val = (en + s[4] / s[0]) * aR * aR; break;
-      case AGX_OUT_CP: val = g.cp * aR * aR / tR; break;
-      case AGX_OUT_CV: val = g.cv * aR * aR / tR; break;
+      case AGX_OUT_CP: val = cp * aR * aR / tR; break;
+      case AGX_OUT_CV: val = cv * aR * aR / tR; break;
       case AGX_OUT_RANK: val = (double)sp.rank; break;
       case AGX_OUT_GLOBAL_POSITION: val = (double)sp.global_pos; break;
       case AGX_OUT_VISCOSITY: {

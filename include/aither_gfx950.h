@@ -128,7 +128,14 @@ enum { AGX_HALO_STATE = 0, AGX_HALO_UPDATE = 1,
 
 /* ---- plain-old-data descriptors --------------------------------------- */
 
-/* single-species calorically-perfect ideal gas + Sutherland transport.
+/* thermodynamic model (input::ThermodynamicModel, input.cpp:795-803).  A library is built for
+ * one of them: libaither_gfx950[_rans].so for the calorically perfect gas,
+ * libaither_gfx950[_rans]_tp.so (-DAGX_TPG=1) for the thermally perfect one (cv, cp, gamma
+ * and Pr functions of T, thermodynamic.hpp:125-189); agx_config_set REFUSES the other. */
+enum { AGX_THERMO_CALORICALLY_PERFECT = 0, AGX_THERMO_THERMALLY_PERFECT = 1 };
+enum { AGX_MAX_VIB = 4 };     /* vibrational modes per species (fluidDatabase: 1) */
+
+/* single-species ideal gas (calorically or thermally perfect) + Sutherland transport.
  * Values are the already-nondimensional ones the reference holds after
  * input::NondimensionalizeFluid (fluid.cpp:83-97, eos.cpp:26-36,
  * thermodynamic.cpp:27-41, transport.cpp:31-69). */
@@ -142,6 +149,10 @@ typedef struct agx_gas {
   double rho_ref;        /* referenceDensity [kg/m^3]                      */
   double l_ref;          /* referenceLength [m]                            */
   double a_ref;          /* reference speed of sound [m/s] (input.cpp:608-613) */
+  /* thermally perfect gas (AGX_THERMO_THERMALLY_PERFECT): the vibrational temperatures of
+   * the species divided by t_ref (fluid.cpp:92); n_vib = 0 for a calorically perfect gas */
+  int32_t n_vib, pad_;
+  double theta_v[AGX_MAX_VIB];
 } agx_gas;
 
 /* solver configuration; one per context */
@@ -170,6 +181,8 @@ typedef struct agx_config {
                                 local time stepping from CFL               */
   double viscous_cfl_coeff;  /* input::ViscousCFLCoefficient (input.cpp:1110) */
   agx_gas gas;
+  int32_t thermodynamic_model; /* AGX_THERMO_* (input::ThermodynamicModel)  */
+  int32_t pad_;
 } agx_config;
 
 /* geometry of one block, host AoS arrays with ghosts (procBlock.hpp:65-90).

@@ -38,6 +38,16 @@
 
 namespace aither_gfx950 {
 
+// The library that serves a deck: numEqns 5 (euler / navierStokes) or 7 (rans), and
+// input::ThermodynamicModel as AGX_THERMO_* (agx_config.thermodynamic_model).  All four
+// export the same agx_* entry points; agx_config_set refuses the model a library is not
+// built for.
+inline const char *LibraryName(int numEqns, int thermodynamicModel) {
+  const bool tp = thermodynamicModel == AGX_THERMO_THERMALLY_PERFECT;
+  if (numEqns == 7) return tp ? "libaither_gfx950_rans_tp.so" : "libaither_gfx950_rans.so";
+  return tp ? "libaither_gfx950_tp.so" : "libaither_gfx950.so";
+}
+
 // L-infinity residual with its location, resid.hpp:24-75
 class resid {
   double linf_ = 0.0;

@@ -1,0 +1,291 @@
+"""Thermally perfect gas on the MI355X (libaither_gfx950_tp.so, libaither_gfx950_rans_tp.so):
+the reference's thermallyPerfect truth reproduced by the HIP library alone; each library's
+refusal of the other model; the device thermodynamics pointwise and through one explicit
+update against the numpy restatement (aither_amd.case.fluid); and -- with no vibrational
+mode, where the model is the calorically perfect gas -- the paths the truth case does not
+touch against the calorically perfect sibling library."""
+import ctypes as C
+import json
+import os
+
+import numpy as np
+import pytest
+
+import aither_amd
+from aither_amd import abi
+from aither_amd.case import fluid, synthetic
+from aither_amd.case.builder import build_case, config_struct
+from aither_amd.case.inputfile import State, parse_input
+from aither_amd.solver import MultigridSolver, Solver
+from parity_utils import flux_scale, rel_err
+
+pytestmark = pytest.mark.gpu
+
+HERE = os.path.dirname(os.path.abspath(__file__))
+TP_DIR = os.path.join(HERE, "golden", "thermallyPerfect")
+TP_INP = os.path.join(TP_DIR, "thermallyPerfect.inp")
+TP, CP = "thermallyPerfect", "caloricallyPerfect"
+RTOL = 1.0e-10
+
+FARFIELD = {s: ("characteristic", 1) for s in range(1, 7)}
+WALL_J = {3: ("viscousWall", 2), 1: ("characteristic", 1), 2: ("pressureOutlet", 3),
+          4: ("characteristic", 1)}
+WALL_ISO = {3: ("viscousWall", 4), 4: ("viscousWall", 2),
+            1: ("characteristic", 1), 2: ("characteristic", 1)}
+RANS_WALL = {3: ("viscousWall", 2), 1: ("characteristic", 1), 2: ("characteristic", 1),
+             4: ("characteristic", 1), 5: ("characteristic", 1), 6: ("characteristic", 1)}
+
+
+def test_reference_truth():
+    """20 free-running iterations of the reference's thermallyPerfect deck (SST 2003, LU-SGS,
+    supersonic ramp, air with a vibrational mode) reproduce its truth vector
+    (regressionTests.py:463-471) to the printed digits."""
+    spec = json.load(open(os.path.join(TP_DIR, "truth.json")))
+    sol = Solver(aither_amd.load(7, TP), build_case(TP_INP))
+    out = sol.run(spec["iterations"])
+    sol.close()
+    for idx, (got, t) in enumerate(zip(out["norm"], spec["truth"])):
+        if idx in spec["ignore"]:
+            continue
+        assert f"{got:.4e}" == f"{t:.4e}", (idx, got, t)
+
+
+def _config_set(api, cfg):
+    ctx = C.c_void_p()
+    api.check(api.ctx_create(0, 0, C.byref(ctx)), "ctx_create")
+    try:
+        rc = api.config_set(ctx, C.byref(cfg))
+        return rc, api.last_error() or b""
+    finally:
+        api.ctx_destroy(ctx)
+
+
+@pytest.mark.parametrize("n_eq", [5, 7])
+def test_each_library_refuses_the_other_model(n_eq):
+    kw = dict(equation_set="rans", turbulence_model="sst2003", bcs=RANS_WALL) if n_eq == 7 else {}
+    case = synthetic.single_block_case((6, 5, 4), thermodynamic_model=TP,
+                                       time_integration="implicitEuler", cfl=5.0, **kw)
+    cfg = config_struct(case)
+    tp, cp = aither_amd.load(n_eq, TP), aither_amd.load(n_eq, CP)
+    rc, msg = _config_set(tp, cfg)
+    assert rc == 0, msg
+    rc, msg = _config_set(cp, cfg)
+    assert rc != 0 and b"_tp.so" in msg, msg
+    cfg.thermodynamic_model = abi.THERMO[CP]
+    cfg.gas.n_vib = 0
+    rc, msg = _config_set(cp, cfg)
+    assert rc == 0, msg
+    rc, msg = _config_set(tp, cfg)
+    assert rc != 0 and b"thermally perfect" in msg, msg
+    cfg.thermodynamic_model = abi.THERMO[TP]
+    cfg.gas.n_vib = abi.MAX_VIB + 1
+    rc, msg = _config_set(tp, cfg)
+    assert rc != 0 and b"n_vib" in msg, msg
+
+
+def _rho_e(gas, s):
+    """rho E of primitive states [..., rho u v w p] with the numpy model"""
+    t = s[..., 4] / (s[..., 0] * gas.gas_constant)
+    return s[..., 0] * (fluid.spec_energy(gas, t) + 0.5 * (s[..., 1:4] ** 2).sum(-1))
+
+
+def test_output_pack_pointwise():
+    """Temperature, sos, mach, energy, enthalpy, cp and cv of states whose T spans 0.1-5
+    t_ref (air at t_ref = 288.15 K: theta / T = 106 .. 2.1) against the numpy model."""
+    case = synthetic.single_block_case((16, 12, 10), thermodynamic_model=TP,
+                                       time_integration="explicitEuler", cfl=0.3)
+    gas, g = case.gas, case.ng
+    st = case.blocks[0].state.copy()
+    inner = st[g:-g, g:-g, g:-g]
+    t = np.geomspace(0.1, 5.0, inner[..., 0].size).reshape(inner.shape[:3])
+    inner[..., 4] = inner[..., 0] * gas.gas_constant * t
+    sol = Solver(aither_amd.load(5, TP), case)
+    sol.upload("state", 0, st)
+    names = ["temperature", "sos", "mach", "energy", "enthalpy", "cp", "cv"]
+    got = dict(zip(names, sol.output_pack(0, names)))
+    sol.close()
+    rho, p = inner[..., 0], inner[..., 4]
+    tt = p / (rho * gas.gas_constant)
+    a_r, t_r = gas.a_ref, gas.t_ref
+    v2 = (inner[..., 1:4] ** 2).sum(-1)
+    cs = np.sqrt(fluid.gamma(gas, tt) * p / rho)
+    e = fluid.spec_energy(gas, tt) + 0.5 * v2
+    want = dict(temperature=tt * t_r, sos=cs * a_r, mach=np.sqrt(v2) / cs, energy=e * a_r ** 2,
+                enthalpy=(e + p / rho) * a_r ** 2, cp=fluid.cp(gas, tt) * a_r ** 2 / t_r,
+                cv=fluid.cv(gas, tt) * a_r ** 2 / t_r)
+    for n in names:
+        np.testing.assert_allclose(got[n], want[n], rtol=1e-12, atol=0.0, err_msg=n)
+    # the range runs from the frozen mode (cv = n R) to a mostly excited one (cv ~ (n + 0.7) R)
+    cvs = want["cv"] / (a_r ** 2 / t_r) / gas.gas_constant
+    assert cvs.min() < gas.n + 1e-6 and cvs.max() > gas.n + 0.6
+
+
+def test_explicit_update_takes_temperature_from_energy():
+    """One explicit Euler step (procBlock.cpp:892): rho E of the new primitive state, formed
+    by the numpy model, equals rho E_old - dt / V R_E -- the device's energy -> temperature
+    root checked directly, at T ~ 6 t_ref where the vibrational energy is ~10 % of e."""
+    case = synthetic.single_block_case((10, 9, 8), stretch=1.1, bcs=WALL_J,
+                                       equation_set="navierStokes", thermodynamic_model=TP,
+                                       time_integration="explicitEuler", cfl=0.3)
+    gas, g = case.gas, case.ng
+    ni, nj, nk = case.blocks[0].geom.n
+    st = case.blocks[0].state.copy()
+    st[..., 4] *= 6.0
+    sol = Solver(aither_amd.load(5, TP), case)
+    sol.upload("state", 0, st)
+    old = sol.download("state", 0)[g:-g, g:-g, g:-g]
+    sol.step(0)
+    new = sol.download("state", 0)[g:-g, g:-g, g:-g]
+    res = sol.download("residual", 0)
+    dt = sol.download("dt", 0)[..., 0]
+    sol.close()
+    vol = np.asarray(case.blocks[0].geom.vol.a).reshape(nk + 2 * g, nj + 2 * g, ni + 2 * g)
+    vol = vol[g:-g, g:-g, g:-g]
+    want = _rho_e(gas, old) - dt / vol * res[..., 4]
+    got = _rho_e(gas, new)
+    assert np.abs(got - want).max() <= 1e-11 * np.abs(want).max()
+    # (the momentum update, for the record: the same step)
+    np.testing.assert_allclose(new[..., 0] * new[..., 1],
+                               old[..., 0] * old[..., 1] - dt / vol * res[..., 1],
+                               rtol=0, atol=1e-12 * np.abs(old[..., 0] * old[..., 1]).max())
+
+
+# ---- no vibrational mode: the thermally perfect build against its calorically perfect
+# sibling, per time step from identical inputs (as tests/parity_utils.run_pair does
+# against the oracle) -------------------------------------------------------------------
+SYNC_FIELDS = ("state", "cons_n", "cons_nm1", "update")
+
+
+def _frozen(case):
+    """the case's gas as a thermally perfect gas without vibrational modes"""
+    case.gas.theta_v = []
+    return case
+
+
+def _stagnation_case(model):
+    """stagnation inlet (i-min) and nonreflecting pressure outlet (i-max), slip walls"""
+    n = (10, 9, 8)
+    deck = synthetic.make_deck(thermodynamic_model=model, time_integration="implicitEuler",
+                               matrix_solver="lusgs", cfl=5.0)
+    deck.bc_states.append(State("stagnationInlet", dict(tag=11, p0=103300.0, t0=289.7,
+                                                        direction=[1.0, 0.0, 0.0])))
+    deck.bcs = [synthetic.box_surfaces(*n, {1: ("stagnationInlet", 11),
+                                            2: ("pressureOutlet", 7)})]
+    case = build_case(None, deck=deck, coords=[synthetic.box_nodes(*n, 1.1)])
+    synthetic.perturbed_state(case)
+    return case
+
+
+def _pair(n_eq, make, steps=3, outputs=False):
+    c_cp, c_tp = make(CP), _frozen(make(TP))
+    sc, st = Solver(aither_amd.load(n_eq, CP), c_cp), Solver(aither_amd.load(n_eq, TP), c_tp)
+    ng = c_cp.ng
+    rfloor = 1.0e-3 * flux_scale(c_cp)
+    nfloor = rfloor * np.sqrt(c_cp.total_cells)
+    nh = 0
+    for nn in range(steps):
+        if nn > 0:
+            for gb in sc.block_ids:
+                for f in SYNC_FIELDS:
+                    st.upload(f, gb, sc.download(f, gb))
+                sc.upload("state", gb, sc.download("state", gb))
+            st.l2_first = None if sc.l2_first is None else sc.l2_first.copy()
+        sc.step(nn), st.step(nn)
+        assert len(sc.history) == len(st.history)
+        for hc, ht in zip(sc.history[nh:], st.history[nh:]):
+            e = rel_err(ht["l2"][None, :], hc["l2"][None, :], nfloor)
+            assert e < RTOL, ("L2", nn, e)
+        nh = len(sc.history)
+        for gb in sc.block_ids:
+            for f in ("state", "residual", "dt"):
+                a, b = st.download(f, gb), sc.download(f, gb)
+                if f == "state":
+                    a, b = a[ng:-ng, ng:-ng, ng:-ng], b[ng:-ng, ng:-ng, ng:-ng]
+                e = rel_err(a, b, rfloor if f == "residual" else 0.0)
+                assert e < RTOL, (f, gb, nn, e)
+    if outputs:
+        names = ["density", "pressure", "mach", "sos", "temperature", "energy", "enthalpy",
+                 "cp", "cv", "viscosity"]
+        for x, y, n in zip(st.output_pack(0, names), sc.output_pack(0, names), names):
+            assert np.abs(x - y).max() <= RTOL * np.abs(y).max(), n
+    sc.close(), st.close()
+
+
+FIVE = {
+    "muscl_roe_rk4": dict(n=(10, 9, 8), stretch=1.2, skew=0.01, time_integration="rk4",
+                          cfl=0.5),
+    "weno_ausm_visc_lusgs": dict(n=(10, 9, 8), stretch=1.2, bcs=WALL_J,
+                                 equation_set="navierStokes", face_reconstruction="weno",
+                                 limiter="none", inviscid_flux="ausm",
+                                 time_integration="implicitEuler", matrix_solver="lusgs",
+                                 cfl=10.0),
+    "dplur_muscl_ausm": dict(n=(10, 9, 8), stretch=1.1, bcs=FARFIELD, inviscid_flux="ausm",
+                             limiter="none", time_integration="implicitEuler",
+                             matrix_solver="dplur", matrix_sweeps=4, cfl=50.0),
+    "wenoz_roe_bdf2_dual": dict(n=(10, 9, 8), stretch=1.1, face_reconstruction="wenoZ",
+                                limiter="none", time_integration="bdf2",
+                                nonlinear_iterations=3, dt=2.0e-5, dual_time_cfl=100.0,
+                                matrix_sweeps=2),
+    "bdplur_visc_iso_wall": dict(n=(9, 9, 8), stretch=1.15, bcs=WALL_ISO,
+                                 equation_set="navierStokes", time_integration="implicitEuler",
+                                 matrix_solver="bdplur", matrix_sweeps=3, cfl=5.0),
+}
+RANS = {
+    "sst_blusgs": dict(matrix_solver="blusgs", matrix_sweeps=2),
+    "sst_bdplur": dict(matrix_solver="bdplur", matrix_sweeps=3, inviscid_flux="ausm"),
+    "wilcox2006_lusgs": dict(turbulence_model="kOmegaWilcox2006", matrix_solver="lusgs",
+                             matrix_sweeps=2),
+    "sst_wall_law": dict(matrix_solver="lusgs", wall_treatment="wallLaw"),
+}
+
+
+@pytest.mark.parametrize("name", sorted(FIVE))
+def test_no_vibration_matches_calorically_perfect(name):
+    _pair(5, lambda m: synthetic.single_block_case(thermodynamic_model=m, **FIVE[name]),
+          outputs=name == "weno_ausm_visc_lusgs")
+
+
+def test_no_vibration_stagnation_inlet_nonreflecting_outlet():
+    _pair(5, _stagnation_case)
+
+
+@pytest.mark.parametrize("name", sorted(RANS))
+def test_no_vibration_matches_calorically_perfect_rans(name):
+    deck = dict(n=(9, 8, 7), stretch=1.2, bcs=RANS_WALL, equation_set="rans",
+                turbulence_model="sst2003", time_integration="implicitEuler", cfl=10.0)
+    deck.update(RANS[name])
+    _pair(7, lambda m: synthetic.single_block_case(thermodynamic_model=m, **deck))
+
+
+def test_no_vibration_multigrid_v_cycle():
+    kw = dict(n=(12, 10, 8), nblocks=1, axis="i", stretch=1.1, levels=2, cycle="V",
+              time_integration="implicitEuler", matrix_solver="dplur", matrix_sweeps=4,
+              cfl=40.0)
+    cc, tc = synthetic.multigrid_levels(thermodynamic_model=CP, **kw)
+    ct, tt = synthetic.multigrid_levels(thermodynamic_model=TP, **kw)
+    for c in ct:
+        _frozen(c)
+    sc = MultigridSolver(aither_amd.load(5, CP), cc, tc)
+    st = MultigridSolver(aither_amd.load(5, TP), ct, tt)
+    oc, ot = sc.step(0), st.step(0)
+    assert rel_err(ot["l2"][None, :], oc["l2"][None, :]) < RTOL
+    g = cc[0].ng
+    a = st.download("state", 0)[g:-g, g:-g, g:-g]
+    b = sc.download("state", 0)[g:-g, g:-g, g:-g]
+    assert rel_err(a, b) < RTOL
+    sc.close(), st.close()
+
+
+def test_the_model_takes_effect():
+    """The truth deck switched to caloricallyPerfect on the plain rans library: residuals
+    differ from the thermally perfect ones by more than 1e-3 relative."""
+    tp = Solver(aither_amd.load(7, TP), build_case(TP_INP))
+    deck = parse_input(TP_INP)
+    deck.thermodynamic_model = CP
+    cp = Solver(aither_amd.load(7, CP), build_case(TP_INP, deck=deck))
+    for nn in range(3):
+        tp.step(nn), cp.step(nn)
+    a, b = tp.history[-1]["l2"], cp.history[-1]["l2"]
+    tp.close(), cp.close()
+    d = np.abs(a - b) / np.abs(b)
+    assert np.max(d[:5]) > 1e-3, d
