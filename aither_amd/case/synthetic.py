@@ -87,25 +87,30 @@ def make_deck(**kw):
     if kw.get("wall_treatment") is not None:
         wall = dict(wallTreatment=kw["wall_treatment"])
     vel = list(kw.get("velocity", [50.0, 20.0, 10.0]))     # free stream, m/s
-    d.ics = [State("icState", dict(tag=-1, pressure=101325.0, density=1.225,
+    # temperature_factor: every pressure (initial, boundary states) and the wall temperature
+    # times this factor at unchanged density, so the whole case sits at temperature_factor x
+    # 288 K (a thermally perfect gas with its vibrational mode excited); 1.0 changes nothing
+    tf = float(kw.get("temperature_factor", 1.0))
+    p_inf = 101325.0 * tf
+    d.ics = [State("icState", dict(tag=-1, pressure=p_inf, density=1.225,
                                    velocity=vel, **turb))]
     d.bc_states = [
-        State("characteristic", dict(tag=1, pressure=101325.0, density=1.225,
+        State("characteristic", dict(tag=1, pressure=p_inf, density=1.225,
                                      velocity=vel, **turb)),
         State("viscousWall", dict(tag=2, **wall)),
-        State("pressureOutlet", dict(tag=3, pressure=101325.0)),
-        State("viscousWall", dict(tag=4, temperature=300.0,
+        State("pressureOutlet", dict(tag=3, pressure=p_inf)),
+        State("viscousWall", dict(tag=4, temperature=300.0 * tf,
                                   velocity=[5.0, 0.0, 0.0], **wall)),
         State("viscousWall", dict(tag=5, heatFlux=2.0e3, **wall)),
-        State("inlet", dict(tag=6, pressure=101325.0, density=1.225,
+        State("inlet", dict(tag=6, pressure=p_inf, density=1.225,
                             velocity=[50.0, 20.0, 10.0], nonreflecting=True,
                             lengthScale=1.0)),
-        State("pressureOutlet", dict(tag=7, pressure=101325.0, nonreflecting=True,
+        State("pressureOutlet", dict(tag=7, pressure=p_inf, nonreflecting=True,
                                      lengthScale=1.0)),
-        State("supersonicInflow", dict(tag=8, pressure=101325.0, density=1.225,
+        State("supersonicInflow", dict(tag=8, pressure=p_inf, density=1.225,
                                        velocity=vel, **turb)),
         State("supersonicOutflow", dict(tag=9)),
-        State("inlet", dict(tag=10, pressure=101325.0, density=1.225, velocity=vel, **turb)),
+        State("inlet", dict(tag=10, pressure=p_inf, density=1.225, velocity=vel, **turb)),
     ]
     return d
 

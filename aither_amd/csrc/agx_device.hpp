@@ -1028,8 +1028,12 @@ __device__ inline void wall_law_solve(const GasDev& g, const double* s, double w
   // cp and Pr of the interior temperature: Crocco-Busemann (:49-50, CalcWallTemperature
   // :231-237) and CalcRecoveryFactor :287-290
   w.cp = cp_of(g, t);
-#endif
+  // ... except the isothermal wall, whose recovery factor is formed with the WALL temperature
+  // (IsothermalBCs wallLaw.cpp:163)
+  w.recovery = pow(prandtl_of(g, mode == 2 ? wall_value : t), 1.0 / 3.0);
+#else
   w.recovery = pow(prandtl_of(g, t), 1.0 / 3.0);
+#endif
   if (mode == 0) {          // wall temperature from Crocco-Busemann, adiabatic
     w.set_wall_vars(t + 0.5 * w.recovery * w.vel_tan * w.vel_tan / cp_of(g, t));
   } else if (mode == 1) {   // guess: wall temperature equals interior temperature

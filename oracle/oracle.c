@@ -104,6 +104,7 @@ struct ora_ctx {
   conn_t conn[MAXCONN];
   /* derived gas constants */
   double gamma, cp, cv, mu_ref, k_nondim, scaling, prandtl;
+  int tp;            /* thermallyPerfect with at least one vibrational mode */
   int have_time_n;   /* StoreOldSolution has run (consVarsN_ non-empty) */
   double mres_opsq;  /* sum of the squared OPERANDS of the last matrix residual (tests) */
   double mres_sumsq; /* ... and of the squared residual itself */
@@ -141,20 +142,124 @@ static inline double dot3(const double *a, const double *b) {
   return ((0.0 + a[0] * b[0]) + a[1] * b[1]) + a[2] * b[2];
 }
 static inline double mag3(const double *a) { return sqrt(dot3(a, a)); }
+/* Sign utility.hpp:125-128 */
+static inline int sign_d(double v) { return (0.0 < v) - (v < 0.0); }
 
 static inline double temperature(const ora_ctx *c, const double *s) {
   /* idealGas::Temperature eos.cpp:100-109 */
   const double rhoR = 0.0 + s[0] * c->cfg.gas.gas_constant;
   return s[4] / rhoR;
 }
+/* thermallyPerfect (include/thermodynamic.hpp:125-189): cv, cp, gamma and Pr are
+ * functions of T.  c->tp is set by ora_config_set for a thermally perfect gas with at least
+ * one vibrational mode; a thermally perfect gas without one IS the calorically perfect class
+ * (every Vib* sum below is empty) and takes its expressions, closed-form root included.
+ * With c->tp == 0 every function keeps the expression (and the association) it always had.
+ * All of them are pure: no state, no dependence on the thread that calls them. */
+static inline double tp_vib_cpcv(const ora_ctx *c, double t) {
+  /* thermallyPerfect::VibEqCpCvTerm thermodynamic.hpp:133-140, ThetaV :129-131 */
+  double vibEq = 0.0;
+  for (int ii = 0; ii < c->cfg.gas.n_vib; ++ii) {
+    const double tv = c->cfg.gas.theta_v[ii] / (2.0 * t);
+    vibEq += pow(tv / sinh(tv), 2.0);
+  }
+  return vibEq;
+}
+static inline double tp_vib_e(const ora_ctx *c, double t) {
+  /* thermallyPerfect::VibEqTerm thermodynamic.hpp:142-148; exp(x) - 1.0 is taken by
+   * expm1 (the same quantity without the cancellation at small theta / T) */
+  double vibEq = 0.0;
+  for (int ii = 0; ii < c->cfg.gas.n_vib; ++ii) {
+    const double vt = c->cfg.gas.theta_v[ii];
+    vibEq += vt / expm1(vt / t);
+  }
+  return vibEq;
+}
+static inline double cp_of(const ora_ctx *c, double t) {
+  /* thermodynamic::Cp thermodynamic.cpp:63-71, thermallyPerfect::SpeciesCp
+   * thermodynamic.hpp:173-176 */
+  if (!c->tp) return c->cp;
+  const double R = c->cfg.gas.gas_constant;
+  return 0.0 + 1.0 * (R * (c->cfg.gas.n + 1.0) + R * tp_vib_cpcv(c, t));
+}
+static inline double cv_of(const ora_ctx *c, double t) {
+  /* thermodynamic::Cv thermodynamic.cpp:73-81, thermallyPerfect::SpeciesCv
+   * thermodynamic.hpp:177-180 */
+  if (!c->tp) return c->cv;
+  const double R = c->cfg.gas.gas_constant;
+  return 0.0 + 1.0 * (R * c->cfg.gas.n + R * tp_vib_cpcv(c, t));
+}
+static inline double gamma_of(const ora_ctx *c, double t) {
+  /* thermodynamic::Gamma thermodynamic.hpp:58-60 */
+  if (!c->tp) return c->gamma;
+  return cp_of(c, t) / cv_of(c, t);
+}
+static inline double prandtl_of(const ora_ctx *c, double t) {
+  /* thermodynamic::Prandtl thermodynamic.hpp:61-64 */
+  if (!c->tp) return c->prandtl;
+  const double gamma = gamma_of(c, t);
+  return (4.0 * gamma) / (9.0 * gamma - 5.0);
+}
 static inline double sos(const ora_ctx *c, const double *s) {
-  /* SpeedOfSound arrayView.hpp:383-391 */
+  /* SpeedOfSound arrayView.hpp:383-391: gamma of the state's own temperature */
+  if (c->tp) return sqrt(gamma_of(c, temperature(c, s)) * s[4] / s[0]);
   return sqrt(c->gamma * s[4] / s[0]);
 }
 static inline double spec_energy(const ora_ctx *c, double t) {
-  /* thermodynamic::SpecEnergy thermodynamic.cpp:83-92 */
+  /* thermodynamic::SpecEnergy thermodynamic.cpp:83-92; thermallyPerfect::SpeciesSpecEnergy
+   * thermodynamic.hpp:163-166 */
+  if (c->tp)
+    return 0.0 + 1.0 * (c->cfg.gas.heat_of_formation +
+                        c->cfg.gas.gas_constant * c->cfg.gas.n * t +
+                        c->cfg.gas.gas_constant * tp_vib_e(c, t));
   return 0.0 + 1.0 * (c->cfg.gas.heat_of_formation +
                       c->cfg.gas.gas_constant * c->cfg.gas.n * t);
+}
+static inline double spec_enthalpy(const ora_ctx *c, double t) {
+  /* thermodynamic::SpecEnthalpy thermodynamic.cpp:94-103; thermallyPerfect::
+   * SpeciesSpecEnthalpy thermodynamic.hpp:167-170 */
+  if (c->tp)
+    return 0.0 + 1.0 * (c->cfg.gas.heat_of_formation +
+                        c->cfg.gas.gas_constant * (c->cfg.gas.n + 1.0) * t +
+                        c->cfg.gas.gas_constant * tp_vib_e(c, t));
+  return 0.0 + 1.0 * (c->cfg.gas.heat_of_formation +
+                      c->cfg.gas.gas_constant *
+                          (c->cfg.gas.n + 1.0) * t);
+}
+static double tp_temperature_from_energy(const ora_ctx *c, double e) {
+  /* thermallyPerfect::TemperatureFromSpecEnergy thermodynamic.cpp:132-141: Ridders' method
+   * (FindRoot utility.hpp:132-184) on func(t) = e - SpecEnergy(t) over [1e-8, 1e4].  The
+   * reference stops at |x2 - x1| <= 1e-8 and takes the LAST t handed to func (its lambda
+   * stores it; FindRoot's return value is dropped).  Same bracket, same method, same "last
+   * t evaluated" here, but iterated to round-off: until the bracket is within 1e-15 T or no
+   * longer shrinks.  A high-precision statement of the same root. */
+  double x1 = 1.0e-8, x2 = 1.0e4;
+  double f1 = e - spec_energy(c, x1);
+  double f2 = e - spec_energy(c, x2);
+  if (sign_d(f1) == sign_d(f2) && sign_d(f1) != 0) return x2; /* last t evaluated */
+  double x4 = x1;
+  for (int ii = 0; ii < 200; ++ii) {
+    const double width = fabs(x2 - x1);
+    const double x3 = 0.5 * (x1 + x2);
+    const double f3 = e - spec_energy(c, x3);
+    if (f3 == 0.0) return x3;
+    const double denom = sqrt(fabs(f3 * f3 - f1 * f2));
+    if (denom == 0.0) return x3;
+    const int fac = sign_d(f1 - f2);
+    x4 = x3 + (x3 - x1) * (fac * f3) / denom;
+    const double f4 = e - spec_energy(c, x4);
+    if (f4 == 0.0) return x4;
+    if (sign_d(f4) != sign_d(f3)) {
+      x1 = x3; f1 = f3; x2 = x4; f2 = f4;
+    } else if (sign_d(f4) != sign_d(f1)) {
+      x2 = x4; f2 = f4;
+    } else {
+      x1 = x4; f1 = f4;
+    }
+    const double w = fabs(x2 - x1);
+    if (w <= 1.0e-15 * fabs(x4) || !(w < width)) return x4;
+  }
+  return x4;
 }
 static inline double energy(const ora_ctx *c, const double *s) {
   /* InternalEnergy arrayView.hpp:434-443; idealGas::Energy eos.cpp:70-72 */
@@ -166,9 +271,7 @@ static inline double enthalpy(const ora_ctx *c, const double *s) {
   /* EnthalpyFunc arrayView.hpp:401-409; idealGas::Enthalpy eos.cpp:80-84 */
   const double t = temperature(c, s);
   const double vel = mag3(s + 1);
-  const double h = 0.0 + 1.0 * (c->cfg.gas.heat_of_formation +
-                                c->cfg.gas.gas_constant *
-                                    (c->cfg.gas.n + 1.0) * t);
+  const double h = spec_enthalpy(c, t);
   return h + 0.5 * vel * vel;
 }
 static void prim_to_cons(const ora_ctx *c, const double *s, double *u) {
@@ -196,7 +299,8 @@ static void cons_to_prim(const ora_ctx *c, const double *u, double *s) {
   const double mf = s[0] / (0.0 + s[0]);
   const double hf = 0.0 + c->cfg.gas.heat_of_formation * mf;
   const double cv = 0.0 + mf * (c->cfg.gas.gas_constant * c->cfg.gas.n);
-  const double t = (spec - hf) / cv;
+  /* thermallyPerfect::TemperatureFromSpecEnergy thermodynamic.cpp:132-141 */
+  const double t = c->tp ? tp_temperature_from_energy(c, spec) : (spec - hf) / cv;
   s[4] = 0.0 + s[0] * c->cfg.gas.gas_constant * t;
   /* turbulence variables, then primitive::LimitTurb primitive.cpp:100-106 with
    * turbModel::TkeMin / OmegaMin = 1e-20 (turbulence.hpp:72-73) */
@@ -482,8 +586,6 @@ static void roe_flux(const ora_ctx *c, const double *l, const double *r,
   }
 }
 
-static inline int sign_d(double v) { return (0.0 < v) - (v < 0.0); }
-
 /* AUSMFlux (AUSMPW+) inviscidFlux.hpp:396-481 and member :162-209 */
 static void ausm_flux(const ora_ctx *c, const double *l, const double *r,
                       const double *n, double *f) {
@@ -551,17 +653,19 @@ static double inv_cell_spec_rad(const ora_ctx *c, const double *s,
 }
 static double turb_prandtl(const ora_ctx *c);
 /* ViscCellSpectralRadius spectralRadius.hpp:94-124 */
-static double visc_term_t(const ora_ctx *c, double mu, double mut) {
-  return c->scaling * (mu / c->prandtl + mut / turb_prandtl(c));
+static double visc_term_t(const ora_ctx *c, double t, double mu, double mut) {
+  /* Prandtl of the cell's own temperature, spectralRadius.hpp:111-119, 139-147 */
+  return c->scaling * (mu / prandtl_of(c, t) + mut / turb_prandtl(c));
 }
 static double visc_cell_spec_rad(const ora_ctx *c, const double *s,
                                  const double *al, const double *au,
                                  double vol, double mu, double mut) {
   const double fMag = 0.5 * (al[3] + au[3]);
   const double a = 4.0 / (3.0 * s[0]);
-  const double b = c->gamma / s[0];
+  const double t = temperature(c, s);          /* spectralRadius.hpp:111 */
+  const double b = gamma_of(c, t) / s[0];
   const double maxTerm = a > b ? a : b;        /* max(a, b) */
-  return maxTerm * visc_term_t(c, mu, mut) * fMag * fMag / vol;
+  return maxTerm * visc_term_t(c, t, mu, mut) * fMag * fMag / vol;
 }
 
 /* ------------------------------------------------------------------------ */
@@ -655,10 +759,11 @@ static double wl_func(wall_law *w, double yplus) {
     /* HeatFluxBCs :113-124: wall temperature from Crocco-Busemann with the wall properties
      * of the PREVIOUS evaluation (CalcWallTemperature :231-237), then SetWallVars */
     const double tNew = w->tInt + w->recoveryFactor * w->uStar * w->uStar * w->uplus * w->uplus /
-                                      (2.0 * c->cp + w->heatFlux * w->muW / (w->rhoW * w->kW * w->uStar));
+                                      (2.0 * cp_of(c, w->tInt) + w->heatFlux * w->muW / (w->rhoW * w->kW * w->uStar));
     wl_set_wall_vars(w, tNew);
   }
-  w->gamma = w->recoveryFactor * w->uStar * w->uStar / (2.0 * c->cp * w->tW);
+  /* UpdateGamma :202-207 is handed the wall temperature in all three modes (:58, :117, :170) */
+  w->gamma = w->recoveryFactor * w->uStar * w->uStar / (2.0 * cp_of(c, w->tW) * w->tW);
   if (w->mode == 2) {
     /* IsothermalBCs :170-172, CalcHeatFlux :223-229 */
     const double tmp = (w->tInt / w->tW - 1.0 + w->gamma * w->uplus * w->uplus) / w->uplus;
@@ -721,9 +826,11 @@ static void wall_law_solve(const ora_ctx *c, const double *state, double wallDis
   w.velTanMag = mag3(velTan);
   const double t = temperature(c, state);
   w.tInt = t;
-  w.recoveryFactor = pow(c->prandtl, 1.0 / 3.0);
+  /* CalcRecoveryFactor :287-290 with the interior temperature (:47, :105), but with the
+   * WALL temperature for an isothermal wall (:163) */
+  w.recoveryFactor = pow(prandtl_of(c, mode == 2 ? wallValue : t), 1.0 / 3.0);
   if (mode == 0) {         /* wall temperature from Crocco-Busemann, adiabatic */
-    wl_set_wall_vars(&w, t + 0.5 * w.recoveryFactor * w.velTanMag * w.velTanMag / c->cp);
+    wl_set_wall_vars(&w, t + 0.5 * w.recoveryFactor * w.velTanMag * w.velTanMag / cp_of(c, t));
   } else if (mode == 1) {  /* guess: wall temperature equals interior temperature */
     w.heatFlux = wallValue;
     wl_set_wall_vars(&w, t);
@@ -821,7 +928,7 @@ static int ghost_state_nr(const ora_ctx *c, const double *interior, int bc,
           /* the wall law's heat flux with the turbulent conductivity (the eddy viscosity is
            * not zero at the wall), 2 x wall distance as gradient length :161-172 */
           const double kappa = conductivity(c, w->temperature) +
-                               w->turb_eddy_visc * c->cp / turb_prandtl_fwd(c);
+                               w->turb_eddy_visc * cp_of(c, w->temperature) / turb_prandtl_fwd(c);
           tGhost = tWall - w->heat_flux / kappa * 2.0 * wallDist;
         }
       }
@@ -968,7 +1075,9 @@ static int ghost_state_nr(const ora_ctx *c, const double *interior, int bc,
     if (layer > 1)
       for (int e = 0; e < NEQ; ++e) ghost[e] = layer * ghost[e] - interior[e];
   } else if (bc == AGX_BC_STAGNATION_INLET) {
-    const double g = c->gamma - 1.0;
+    /* gamma of the interior cell's temperature, ghostStates.cpp:538-540, 558 */
+    const double gammaI = gamma_of(c, temperature(c, interior));
+    const double g = gammaI - 1.0;
     const double sosI = sos(c, interior);
     const double vn = dot3(interior + 1, n);
     const double rNeg = vn - 2.0 * sosI / g;
@@ -982,7 +1091,7 @@ static int ghost_state_nr(const ora_ctx *c, const double *interior, int bc,
                                0.5 * g));
     const double tb = d->stagnation_temperature * (sosB * sosB / stagSoSsq);
     const double pb = d->stagnation_pressure *
-                      pow(sosB * sosB / stagSoSsq, c->gamma / g);
+                      pow(sosB * sosB / stagSoSsq, gammaI / g);
     const double vbMag = sqrt(2.0 / g * (d->stagnation_temperature - tb));
     const double R = 0.0 + 1.0 * c->cfg.gas.gas_constant;
     const double rhoGhost = pb / (R * tb);
@@ -1034,7 +1143,9 @@ static int ghost_state_nr(const ora_ctx *c, const double *interior, int bc,
       const double dVelT = sum - (dVelN[0] + dVelN[1] + dVelN[2]);
       double tv[3];
       for (int q = 0; q < 3; ++q) tv[q] = pGradT[q] - rhoSoSN * dVelN[q];
-      const double trans = -0.5 * (dot3(velT, tv) + c->gamma * sn[4] * dVelT);
+      /* gamma of the state at time n, ghostStates.cpp:633-634 */
+      const double gammaN = gamma_of(c, temperature(c, sn));
+      const double trans = -0.5 * (dot3(velT, tv) + gammaN * sn[4] * dVelT);
       ghost[4] = (sn[4] + rhoSoSN * deltaVel + nr->dt * k * pb - nr->dt * beta * trans) /
                  (1.0 + nr->dt * k);
     }
@@ -1390,7 +1501,8 @@ static int is_lusgs(const ora_ctx *c) {    /* input.cpp:847 */
 static void inv_flux_jacobian(const ora_ctx *c, const double *s, const double *area, double *J) {
   const double *n = area;
   const double velNorm = dot3(s + 1, n);
-  const double gamma = c->gamma, gm1 = gamma - 1.0;
+  /* gamma of the state's own temperature, fluxJacobian.hpp:495-499 */
+  const double gamma = gamma_of(c, temperature(c, s)), gm1 = gamma - 1.0;
   const double phi = 0.5 * gm1 * dot3(s + 1, s + 1);
   double u[NEQM];
   prim_to_cons(c, s, u);
@@ -1434,7 +1546,7 @@ static void tsl_jacobian(const ora_ctx *c, const double *s, double lamVisc, doub
   const double velNorm = dot3(s + 1, n);
   const double rho = s[0];
   const double k = conductivity(c, t) * c->scaling;
-  const double kt = mut * c->cp / 0.9;
+  const double kt = mut * cp_of(c, t) / 0.9;      /* TurbConductivity(.., t, ..) :694-695 */
   const double lambda = 0.0 - (2.0 / 3.0) * (mu + mut);
   const double trace = vGrad[0] + vGrad[4] + vGrad[8];
   double tauNorm[3];
@@ -1457,7 +1569,7 @@ static void tsl_jacobian(const ora_ctx *c, const double *s, double lamVisc, doub
   }
   TT_(4, 4) = (k + kt) / ((mu + mut) * rho);
   for (int q = 0; q < NJ; ++q) T[q] *= area[3] * (mu + mut) / dist;
-  const double gm1 = c->gamma - 1.0, invRho = 1.0 / rho;
+  const double gm1 = gamma_of(c, t) - 1.0, invRho = 1.0 / rho;   /* :623-625 */
   PP_(0, 0) = 1.0;
   for (int q = 0; q < 3; ++q) {
     PP_(1 + q, 0) = -invRho * s[1 + q];
@@ -1915,7 +2027,7 @@ static void visc_flux(const ora_ctx *c, const double *velGrad,
   f[3] = tau[2];
   const double t = temperature(c, s);
   const double kk = conductivity(c, t) * c->scaling;
-  const double kt = mut * c->cp / turb_prandtl(c);
+  const double kt = mut * cp_of(c, t) / turb_prandtl(c); /* cp of the face state's T, :109-113 */
   f[4] = dot3(tau, s + 1) + (kk + kt) * dot3(tGrad, n) + 0.0;
   if (NEQ > NF) {
     const double tkeCoeff = sigma_k(c, f1);
@@ -2369,9 +2481,10 @@ static void off_diagonal(const ora_ctx *c, const double *state, const double *di
   double sr = 0.5 * fArea[3] * (fabs(dot3(state + 1, fArea)) + sos(c, state));
   if (c->cfg.is_viscous) {
     const double a = 4.0 / (3.0 * state[0]);
-    const double bq = c->gamma / state[0];
+    const double t = temperature(c, state);      /* ViscFaceSpectralRadius spectralRadius.hpp:139 */
+    const double bq = gamma_of(c, t) / state[0];
     const double maxTerm = a > bq ? a : bq;
-    sr += fArea[3] / dist * maxTerm * visc_term_t(c, mu, mut);
+    sr += fArea[3] / dist * maxTerm * visc_term_t(c, t, mu, mut);
   }
   for (int e = 0; e < NF; ++e) {
     const double fc = 0.5 * fArea[3] * (fn[e] - fo[e]);
@@ -2690,6 +2803,21 @@ int ora_config_set(ora_ctx *c, const agx_config *cfg) {
     return fail("rans: the sst2003, sstdes and kOmegaWilcox2006 models are restated");
   if (cfg->n_eq == 7 && cfg->inv_flux_jacobian == AGX_JACOBIAN_APPROX_ROE)
     return fail("rans: approximateRoe is not restated");
+  /* input::AssignThermodynamicModel input.cpp:795-803: two models and nothing else */
+  if (cfg->thermodynamic_model != AGX_THERMO_CALORICALLY_PERFECT &&
+      cfg->thermodynamic_model != AGX_THERMO_THERMALLY_PERFECT)
+    return fail("thermodynamic_model %d is not restated (caloricallyPerfect, thermallyPerfect)",
+                (int)cfg->thermodynamic_model);
+  if (cfg->thermodynamic_model == AGX_THERMO_CALORICALLY_PERFECT && cfg->gas.n_vib != 0)
+    return fail("a calorically perfect gas has no vibrational modes (n_vib = %d)",
+                (int)cfg->gas.n_vib);
+  if (cfg->thermodynamic_model == AGX_THERMO_THERMALLY_PERFECT &&
+      (cfg->gas.n_vib < 0 || cfg->gas.n_vib > AGX_MAX_VIB))
+    return fail("thermally perfect gas: n_vib = %d is outside 0 .. AGX_MAX_VIB = %d",
+                (int)cfg->gas.n_vib, (int)AGX_MAX_VIB);
+  for (int ii = 0; ii < cfg->gas.n_vib; ++ii)
+    if (!(cfg->gas.theta_v[ii] > 0.0))
+      return fail("thermally perfect gas: theta_v[%d] is not positive", ii);
   if (g_live_cfg > 0 && !c->have_cfg && cfg->n_eq != g_neq)
     return fail("oracle: one equation count per process at a time (%d live)", g_neq);
   if (!c->have_cfg) ++g_live_cfg;
@@ -2702,6 +2830,9 @@ int ora_config_set(ora_ctx *c, const agx_config *cfg) {
   c->cv = 0.0 + 1.0 * (g->gas_constant * g->n);
   c->gamma = c->cp / c->cv;
   c->prandtl = (4.0 * c->gamma) / (9.0 * c->gamma - 5.0);
+  /* thermallyPerfect thermodynamic.hpp:125-189; without a vibrational mode the class is the
+   * calorically perfect one and takes its code paths */
+  c->tp = cfg->thermodynamic_model == AGX_THERMO_THERMALLY_PERFECT && g->n_vib > 0;
   /* sutherland::sutherland transport.cpp:31-69 */
   c->mu_ref = g->visc_c1 * pow(g->t_ref, 1.5) / (g->t_ref + g->visc_s);
   c->k_nondim = (g->a_ref * g->a_ref * c->mu_ref) / g->t_ref;
@@ -2953,8 +3084,13 @@ int ora_output_pack(ora_ctx *c, int id, int nvar, const int32_t *vars, double *o
             case AGX_OUT_TEMPERATURE: val = t * tR; break;
             case AGX_OUT_ENERGY: val = energy(c, s) * aR * aR; break;
             case AGX_OUT_ENTHALPY: val = enthalpy(c, s) * aR * aR; break;
-            case AGX_OUT_CP: val = gs->gas_constant * (gs->n + 1.0) * aR * aR / tR; break;
-            case AGX_OUT_CV: val = gs->gas_constant * gs->n * aR * aR / tR; break;
+            /* output.cpp:268-277: Cp, Cv of the cell's temperature */
+            case AGX_OUT_CP:
+              val = (c->tp ? cp_of(c, t) : gs->gas_constant * (gs->n + 1.0)) * aR * aR / tR;
+              break;
+            case AGX_OUT_CV:
+              val = (c->tp ? cv_of(c, t) : gs->gas_constant * gs->n) * aR * aR / tR;
+              break;
             case AGX_OUT_RANK: val = (double)c->rank; break;
             case AGX_OUT_GLOBAL_POSITION: val = (double)b->gpos; break;
             case AGX_OUT_VISCOSITY_RATIO:

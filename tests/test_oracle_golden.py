@@ -39,7 +39,7 @@ def test_oracle_reproduces_reference_truth(oracle, name):
     sol.close()
 
 
-@pytest.mark.parametrize("kind", ["weno_visc_lusgs", "rans_blusgs", "dplur"])
+@pytest.mark.parametrize("kind", ["weno_visc_lusgs", "rans_blusgs", "dplur", "rans_blusgs_tp"])
 def test_oracle_does_not_depend_on_the_thread_count(oracle, kind):
     """The oracle's loops are threaded over k-planes / hyperplane cells for the bench's
     cpu_baseline on all host cores; every sum is still formed in the serial order, so one
@@ -60,6 +60,12 @@ def test_oracle_does_not_depend_on_the_thread_count(oracle, kind):
                             cfl=10.0),
         "dplur": dict(inviscid_flux="ausm", time_integration="implicitEuler",
                       matrix_solver="dplur", matrix_sweeps=3, cfl=5.0),
+        # a thermally perfect gas at ~2000 K (vibrational mode excited): the T-dependent gas
+        # properties and the energy -> temperature root are pure functions of their arguments
+        "rans_blusgs_tp": dict(bcs=wall, equation_set="rans", turbulence_model="sst2003",
+                               time_integration="implicitEuler", matrix_solver="blusgs",
+                               cfl=10.0, thermodynamic_model="thermallyPerfect",
+                               temperature_factor=7.0),
     }[kind]
     out = []
     os.environ["ORA_OMP_MIN_CELLS"] = "0"      # thread even these small blocks

@@ -1,9 +1,16 @@
-"""Thermally perfect gas on the MI355X (libaither_gfx950_tp.so, libaither_gfx950_rans_tp.so):
-the reference's thermallyPerfect truth reproduced by the HIP library alone; each library's
-refusal of the other model; the device thermodynamics pointwise and through one explicit
-update against the numpy restatement (aither_amd.case.fluid); and -- with no vibrational
-mode, where the model is the calorically perfect gas -- the paths the truth case does not
-touch against the calorically perfect sibling library."""
+"""Thermally perfect gas on the MI355X (libaither_gfx950_tp.so, libaither_gfx950_rans_tp.so).
+
+First line of defence: parity of the two libraries with the CPU oracle WITH THE VIBRATIONAL
+MODE ACTIVE (test_tp_* below): the oracle carries the model as an independent restatement of
+the reference, pinned on the reference's thermallyPerfect truth
+(tests/test_thermally_perfect_host.py), and every row of DESIGN section 8's device-site table is
+reached by a hot (~2000 K) case of tests/tp_cases.py at parity_utils.RTOL.
+
+Beside it: the reference's truth reproduced by the HIP library alone; each library's refusal
+of the other model; the device thermodynamics pointwise and through one explicit update
+against the numpy restatement (aither_amd.case.fluid).  Second line of defence: with no
+vibrational mode, where the model is the calorically perfect gas, the `_tp` builds against
+their calorically perfect siblings (test_no_vibration_*)."""
 import ctypes as C
 import json
 import os
@@ -15,9 +22,10 @@ import aither_amd
 from aither_amd import abi
 from aither_amd.case import fluid, synthetic
 from aither_amd.case.builder import build_case, config_struct
-from aither_amd.case.inputfile import State, parse_input
+from aither_amd.case.inputfile import parse_input
 from aither_amd.solver import MultigridSolver, Solver
-from parity_utils import flux_scale, rel_err
+from parity_utils import RTOL, flux_scale, rel_err, run_pair
+import tp_cases
 
 pytestmark = pytest.mark.gpu
 
@@ -25,7 +33,6 @@ HERE = os.path.dirname(os.path.abspath(__file__))
 TP_DIR = os.path.join(HERE, "golden", "thermallyPerfect")
 TP_INP = os.path.join(TP_DIR, "thermallyPerfect.inp")
 TP, CP = "thermallyPerfect", "caloricallyPerfect"
-RTOL = 1.0e-10
 
 FARFIELD = {s: ("characteristic", 1) for s in range(1, 7)}
 WALL_J = {3: ("viscousWall", 2), 1: ("characteristic", 1), 2: ("pressureOutlet", 3),
@@ -163,17 +170,7 @@ def _frozen(case):
 
 
 def _stagnation_case(model):
-    """stagnation inlet (i-min) and nonreflecting pressure outlet (i-max), slip walls"""
-    n = (10, 9, 8)
-    deck = synthetic.make_deck(thermodynamic_model=model, time_integration="implicitEuler",
-                               matrix_solver="lusgs", cfl=5.0)
-    deck.bc_states.append(State("stagnationInlet", dict(tag=11, p0=103300.0, t0=289.7,
-                                                        direction=[1.0, 0.0, 0.0])))
-    deck.bcs = [synthetic.box_surfaces(*n, {1: ("stagnationInlet", 11),
-                                            2: ("pressureOutlet", 7)})]
-    case = build_case(None, deck=deck, coords=[synthetic.box_nodes(*n, 1.1)])
-    synthetic.perturbed_state(case)
-    return case
+    return tp_cases.stagnation_case(model)
 
 
 def _pair(n_eq, make, steps=3, outputs=False):
@@ -289,3 +286,146 @@ def test_the_model_takes_effect():
     tp.close(), cp.close()
     d = np.abs(a - b) / np.abs(b)
     assert np.max(d[:5]) > 1e-3, d
+
+
+# ---- the vibrational mode active: the `_tp` libraries against the oracle -----------------
+# parity_utils.run_pair unchanged: per time step from identical inputs, state / residual /
+# dt, L2 and Linf norms and the derived matrix-residual bound, all at parity_utils.RTOL.
+# Every case comes from tests/tp_cases.py, which asserts that the mode is excited in every
+# cell and names the rows of DESIGN section 8's device-site table the case reaches.
+def _report(name, sg, so, case):
+    """worst relative error of the last step, printed (-s) for DESIGN section 8"""
+    g = case.ng
+    rfloor = 1.0e-3 * flux_scale(case)
+    worst = {}
+    for gb in sg.block_ids:
+        for f in ("state", "residual", "dt"):
+            a, b = sg.download(f, gb), so.download(f, gb)
+            if f == "state":
+                a, b = a[g:-g, g:-g, g:-g], b[g:-g, g:-g, g:-g]
+            worst[f] = max(worst.get(f, 0.0), rel_err(a, b, rfloor if f == "residual" else 0.0))
+    print("TP-PARITY", name, " ".join(f"{k}={v:.2e}" for k, v in worst.items()))
+
+
+def _run(name, n_eq, oracle, case, steps=3):
+    sg, so = run_pair(aither_amd.load(n_eq, TP), oracle, case, steps)
+    _report(name, sg, so, case)
+    sg.close(), so.close()
+
+
+def test_tp_truth_deck_per_iteration(oracle):
+    """The truth deck itself (Roe + minmod MUSCL, SST 2003, LU-SGS, supersonic ramp), per
+    iteration from identical inputs: localises what the five-digit truth only sums up."""
+    _run("truth_deck", 7, oracle, tp_cases.excited(build_case(TP_INP)))
+
+
+@pytest.mark.parametrize("name", sorted(tp_cases.FIVE))
+def test_tp_five_equation_parity(oracle, name):
+    _run(name, 5, oracle, tp_cases.hot_single(**tp_cases.FIVE[name]))
+
+
+def test_tp_stagnation_inlet_nonreflecting_outlet_parity(oracle):
+    """stagnation inlet gamma(T_interior), nonreflecting outlet gamma(T_n)
+    (ghostStates.cpp:538-558, 633) -- _stagnation_case, unfrozen and hot"""
+    _run("stagnation", 5, oracle, tp_cases.excited(tp_cases.stagnation_case(TP, tp_cases.HOT)))
+
+
+@pytest.mark.parametrize("name", sorted(tp_cases.RANS))
+def test_tp_rans_parity(oracle, name):
+    _run(name, 7, oracle, tp_cases.rans_case(name))
+
+
+@pytest.mark.parametrize("vel", tp_cases.RANS_BOX_VELOCITIES)
+def test_tp_rans_inlet_and_supersonic_boundaries_parity(oracle, vel):
+    _run(f"rans_box_{vel[0]:.0f}", 7, oracle, tp_cases.rans_box_case(vel))
+
+
+@pytest.mark.parametrize("tag,solver", tp_cases.WALL_LAW)
+def test_tp_wall_law_parity(oracle, tag, solver):
+    _run(f"wall_law_{tag}_{solver}", 7, oracle, tp_cases.wall_law_case(tag, solver))
+
+
+def test_tp_stacked_blocks_parity_five(oracle):
+    _run("stacked_blusgs_visc", 5, oracle, tp_cases.stacked_five(), steps=2)
+
+
+def test_tp_stacked_blocks_parity_rans(oracle):
+    _run("stacked_rans_lusgs", 7, oracle, tp_cases.stacked_rans(), steps=2)
+
+
+def _multigrid(n_eq, oracle, make, matrix_rtol, update_by_largest):
+    cg, tg = make()
+    co, to = make()
+    sg = MultigridSolver(aither_amd.load(n_eq, TP), cg, tg)
+    so = MultigridSolver(oracle, co, to)
+    g, levels, nblocks = cg[0].ng, len(cg), len(cg[0].blocks)
+    worst = dict(l2=0.0, matrix=0.0, state=0.0, update=0.0)
+    for nn in range(3):
+        og, oo = sg.step(nn), so.step(nn)
+        worst["l2"] = max(worst["l2"], float((np.abs(og["l2"] - oo["l2"]) / oo["l2"]).max()))
+        worst["matrix"] = max(worst["matrix"], abs(og["matrix"] - oo["matrix"]) / oo["matrix"])
+        print("TP-PARITY multigrid", n_eq, nn, worst)
+        assert np.allclose(og["l2"], oo["l2"], rtol=1e-9, atol=1e-12 * oo["l2"].max())
+        assert abs(og["matrix"] - oo["matrix"]) <= matrix_rtol * oo["matrix"]
+        scale = max(np.abs(so.download("update", gb, lev)).max()
+                    for lev in range(levels) for gb in range(nblocks))
+        for lev in range(levels):
+            for gb in range(nblocks):
+                a = sg.download("state", gb, lev)[g:-g, g:-g, g:-g]
+                b = so.download("state", gb, lev)[g:-g, g:-g, g:-g]
+                e = rel_err(a, b)
+                worst["state"] = max(worst["state"], e)
+                assert e < 1e-9, (nn, lev, gb, "state", e)
+                a = sg.download("update", gb, lev)[g:-g, g:-g, g:-g]
+                b = so.download("update", gb, lev)[g:-g, g:-g, g:-g]
+                e = (np.abs(a - b).max() / scale) if update_by_largest else rel_err(a, b)
+                worst["update"] = max(worst["update"], e)
+                assert e < 1e-9, (nn, lev, gb, "update", e)
+    print("TP-PARITY multigrid", n_eq, "final", worst)
+    sg.close(), so.close()
+
+
+def test_tp_multigrid_five_equations_parity(oracle):
+    """W cycle, three levels, two blocks, DPLUR: the bounds of test_multigrid_synthetic_parity"""
+    _multigrid(5, oracle, tp_cases.multigrid_five, 1e-8, False)
+
+
+def test_tp_multigrid_seven_equations_parity(oracle):
+    """W cycle, three levels, two blocks, SST + BLU-SGS: the bounds (and the update's scale)
+    of test_multigrid_seven_equations_parity"""
+    _multigrid(7, oracle, tp_cases.multigrid_rans, 1e-7, True)
+
+
+def test_tp_outputs_parity(oracle):
+    """k_output_pack (every thermodynamic name plus viscosity), the restart pack and the
+    temperature / viscosity / gradient fields of the device against the oracle's, hot."""
+    case = tp_cases.hot_single(**tp_cases.FIVE["weno_ausm_visc_lusgs"])
+    agx = aither_amd.load(5, TP)
+    sg, so = run_pair(agx, oracle, case, 1)
+    # both hold their own state after the step: give the device the oracle's, bit for bit
+    sg.upload("state", 0, so.download("state", 0))
+    names = ["density", "pressure", "mach", "sos", "temperature", "energy", "enthalpy",
+             "cp", "cv", "viscosity"]
+    for x, y, n in zip(sg.output_pack(0, names), so.output_pack(0, names), names):
+        e = np.abs(x - y).max() / np.abs(y).max()
+        print("TP-PARITY output", n, f"{e:.2e}")
+        assert e < RTOL, (n, e)
+    x, y = sg.restart_pack(0), so.restart_pack(0)
+    assert rel_err(x, y) < RTOL
+    sg.close(), so.close()
+    # the fields, as test_temperature_viscosity_fields: the oracle's arrays belong to the
+    # state its last residual saw
+    sg, so2 = Solver(agx, case), Solver(oracle, case)
+    oracle.check(oracle.phase_bc_faces(so2.ctx)); oracle.check(oracle.phase_bc_edges(so2.ctx))
+    oracle.check(oracle.phase_residual(so2.ctx, 0, case.deck.cfl(0)))
+    sg.upload("state", 0, so2.download("state", 0))
+    g = case.ng
+    for f in ("temperature", "viscosity"):
+        a, b = sg.download(f, 0), so2.download(f, 0)
+        inner = (slice(g, -g),) * 3
+        assert rel_err(a[inner], b[inner]) < RTOL, f
+        assert rel_err(a[g:-g, g:-g, :], b[g:-g, g:-g, :]) < RTOL, f
+    for f in ("vel_grad", "temp_grad", "dens_grad", "press_grad"):
+        a, b = sg.download(f, 0), so2.download(f, 0)
+        assert np.abs(b).max() > 0 and rel_err(a, b) < RTOL, f
+    sg.close(), so2.close()
