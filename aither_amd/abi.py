@@ -22,7 +22,14 @@ BC = {"slipWall": 0, "viscousWall": 1, "characteristic": 2, "inlet": 3,
 FIELD = {"state": 0, "residual": 1, "dt": 2, "spec_radius": 3, "cons_n": 4,
          "update": 5, "diagonal": 6, "temperature": 7, "viscosity": 8,
          "cons_nm1": 9, "vel_grad": 10, "temp_grad": 11, "dens_grad": 12,
-         "press_grad": 13}
+         "press_grad": 13,
+         # the geometry the device holds (download only), ghost cells included
+         "volume": 14, "center": 15, "farea_i": 16, "farea_j": 17, "farea_k": 18,
+         "width_i": 19, "width_j": 20, "width_k": 21, "wall_dist": 22}
+# geometry fields: (components, direction with one more entry or None)
+GEOM_FIELDS = {"volume": (1, None), "center": (3, None), "farea_i": (4, "i"),
+               "farea_j": (4, "j"), "farea_k": (4, "k"), "width_i": (1, None),
+               "width_j": (1, None), "width_k": (1, None), "wall_dist": (1, None)}
 HALO_STATE, HALO_UPDATE, HALO_VELGRAD_A, HALO_VELGRAD_B, HALO_TURB = 0, 1, 2, 3, 4
 # variables of a function file (AGX_OUT_*), under the reference's names (output.cpp:235-407)
 OUT = {"density": 0, "vel_x": 1, "vel_y": 2, "vel_z": 3, "pressure": 4, "mach": 5, "sos": 6,
@@ -68,7 +75,8 @@ class BlockGeom(C.Structure):
     _fields_ = [(n, C.c_int32) for n in (
         "ni", "nj", "nk", "ng", "parent_block", "global_pos")] + [
         (n, c_dp) for n in ("farea_i", "farea_j", "farea_k", "vol", "center",
-                            "width_i", "width_j", "width_k", "wall_dist")]
+                            "width_i", "width_j", "width_k", "wall_dist",
+                            "nodes")]
 
 
 class BcState(C.Structure):

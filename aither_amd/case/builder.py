@@ -126,7 +126,13 @@ def initial_from_cloud(deck, gas, geom, path):
     from scipy.spatial import cKDTree
     pts, st = cloud_states(deck, gas, path)
     ng = geom.ng
-    cen = geom.center.a[ng:ng + geom.nk, ng:ng + geom.nj, ng:ng + geom.ni, :]
+    if isinstance(geom, _geo.NodeGeometry):     # (the centroids alone, plot3d.cpp:35-43)
+        x = geom.nodes
+        cen = 0.125 * sum(x[dk:x.shape[0] - 1 + dk, dj:x.shape[1] - 1 + dj,
+                            di:x.shape[2] - 1 + di]
+                          for dk in (0, 1) for dj in (0, 1) for di in (0, 1))
+    else:
+        cen = geom.center.a[ng:ng + geom.nk, ng:ng + geom.nj, ng:ng + geom.ni, :]
     _, idx = cKDTree(pts).query(cen.reshape(-1, 3))
     return st[idx].reshape(geom.nk, geom.nj, geom.ni, -1)
 
@@ -207,10 +213,20 @@ def _wall_distance(blocks, nearest=None):
                     sign * wd.v(rs["i"], rs["j"], rs["k"])
 
 
-def build_case(inp_path, grid_dir=None, deck=None, coords=None, ranks=None, setup=None):
+def build_case(inp_path, grid_dir=None, deck=None, coords=None, ranks=None, setup=None,
+               geometry="host"):
     """Build a Case from an .inp file (and its .xyz grid).  `deck`/`coords`
     may be given directly for synthetic cases.  setup: a solver.DeviceSetup -- the
-    volume-sized parts (metrics, wall distance) then run in the library."""
+    volume-sized parts (metrics, wall distance) then run in the library.
+    geometry="device": the blocks carry their nodes, sizes, surfaces and initial state and
+    no metric arrays (geometry.NodeGeometry); the library forms the whole geometry on the
+    device when a Solver creates them (agx_block_geom.nodes), SwapGeomSlice's border update
+    of the connections included.  Connections are still found here."""
+    if geometry not in ("host", "device"):
+        raise ValueError(f"geometry={geometry!r}: 'host' or 'device'")
+    if geometry == "device" and ranks is not None and len(set(ranks)) > 1:
+        raise NotImplementedError("geometry='device' with blocks on several ranks: ghost "
+                                  "geometry and wall points would have to cross ranks")
     if deck is None:
         deck = parse_input(inp_path)
     deck.validate()
@@ -234,8 +250,11 @@ def build_case(inp_path, grid_dir=None, deck=None, coords=None, ranks=None, setu
     blocks = []
     total = 0
     for b, x in enumerate(coords):
-        g = _geo.BlockGeometry(x, ng, metrics=setup.metrics if setup else None)
-        g.assign_ghost_geom(deck.bcs[b])
+        if geometry == "device":
+            g = _geo.NodeGeometry(np.ascontiguousarray(x, dtype=np.float64), ng)
+        else:
+            g = _geo.BlockGeometry(x, ng, metrics=setup.metrics if setup else None)
+            g.assign_ghost_geom(deck.bcs[b])
         ic_file = deck.ic_for_block(b).get("file")
         if ic_file is not None:       # (relative to the case directory, as the reference runs)
             base = grid_dir or os.path.dirname(os.path.abspath(inp_path))
@@ -247,6 +266,8 @@ def build_case(inp_path, grid_dir=None, deck=None, coords=None, ranks=None, setu
         blocks.append(Block(g, deck.bcs[b], st, b, b, ranks[b], local_pos[b]))
         total += g.ni * g.nj * g.nk
     conns = _conn.find_connections(deck.bcs, coords, deck, ranks, local_pos)
+    if geometry == "device":
+        return Case(deck, gas, blocks, conns, total, n_eq=7 if deck.is_rans() else 5)
     geoms = [b.geom for b in blocks]
     for c in conns:
         if c.is_interblock:

@@ -201,6 +201,20 @@ def _grow(arr, d):
     return np.concatenate([arr, last], axis=ax)
 
 
+class NodeGeometry:
+    """What a block built with geometry="device" carries: its nodes and sizes.  The metric
+    arrays exist on the device only (agx_block_geom.nodes); Solver.geometry fetches them."""
+
+    def __init__(self, coords, ng):
+        nk, nj, ni = (s - 1 for s in coords.shape[:3])
+        self.ni, self.nj, self.nk, self.ng = ni, nj, nk, ng
+        self.nodes = coords
+
+    @property
+    def n(self):
+        return (self.ni, self.nj, self.nk)
+
+
 class BlockGeometry:
     """Ghost-padded metrics of one block."""
 

@@ -6,6 +6,7 @@
 // mgSolution::Iterate (src/mgSolution.cpp:246-269).  There is no CPU compute
 // path here: every entry point fails loudly if HIP is unavailable.
 #include "agx_kernels.hpp"
+#include "agx_geometry.hpp"
 #include <rccl/rccl.h>
 #include <cstdarg>
 #include <cstdio>
@@ -62,6 +63,11 @@ struct Block {
   int* mg_start = nullptr;
   double *mg_vf = nullptr, *mg_cf = nullptr;
   const void *mg_tc_key = nullptr, *mg_vf_key = nullptr, *mg_cf_key = nullptr;
+  // node-built blocks (agx_block_geom.nodes): the node coordinates and the face-centre
+  // planes, both on the device until agx_setup_finalize has completed the geometry
+  bool node_built = false;
+  double* nodes_dev = nullptr;
+  double* fcen = nullptr;
   int* d2_tab = nullptr;      // device: dstart[Pi + Pj] | ij_of_pos[Pi * Pj]
   std::vector<int> dstart;    // host copy (halo index maps)
   // hyperplane-per-launch sweeps captured as graphs: [forward][both triangles][un_is_u]
@@ -1152,6 +1158,360 @@ int update_pass(agx_ctx* c, int mode, int mm, double* l2, agx_linf* linf) {
 }  // namespace
 
 // ===========================================================================
+
+// ---- node-built blocks (agx_block_geom.nodes): the whole geometry on the device ----------
+// Kernels: agx_geometry.hpp.  The order is that of the host set-up (main.cpp:100-203 as
+// aither_amd/case/builder.py restates it).
+namespace {
+GeoPlanes geo_planes(Block& b) {
+  GeoPlanes g;
+  const BlockDev& d = b.d;
+  g.vol = d.vol; g.wdist = d.wdist;
+  for (int q = 0; q < 3; ++q) {
+    g.cen[q] = d.cen[q];
+    for (int cc = 0; cc < 4; ++cc) g.fa[q][cc] = d.fa[q][cc];
+    for (int cc = 0; cc < 3; ++cc)
+      g.fc[q][cc] = b.fcen ? b.fcen + (long)(3 * q + cc) * d.nplane : nullptr;
+  }
+  return g;
+}
+inline dim3 geo_grid(long n) { return dim3((unsigned)((std::max<long>(n, 1) + 255) / 256)); }
+
+// cell range of a surface as boundarySurface::RangeI/J/K give it (lo == hi: one plane)
+void surface_range(const agx_bc_surface& s, int* lo, int* hi) {
+  lo[0] = s.imin; lo[1] = s.jmin; lo[2] = s.kmin;
+  hi[0] = s.imax; hi[1] = s.jmax; hi[2] = s.kmax;
+  for (int q = 0; q < 3; ++q) if (lo[q] == hi[q]) hi[q] = lo[q] + 1;
+}
+
+// agx_block_create: the nodes go to the device and stay there until agx_setup_finalize;
+// volume, centre and face areas of the physical cells straight into the block's planes
+int geo_block_metrics(agx_ctx* c, Block& b, const double* nodes) {
+  const BlockDev& d = b.d;
+  const long nn = (long)(d.ni + 1) * (d.nj + 1) * (d.nk + 1);
+  HIPCHK(hipMalloc((void**)&b.nodes_dev, sizeof(double) * 3 * nn));
+  HIPCHK(hipMemcpyAsync(b.nodes_dev, nodes, sizeof(double) * 3 * nn, hipMemcpyHostToDevice,
+                        c->stream));
+  HIPCHK(hipMemsetAsync(c->err_dev, 0, sizeof(int), c->stream));
+  hipLaunchKernelGGL(k_metrics_planes, geo_grid(nn), dim3(256), 0, c->stream, d, b.nodes_dev,
+                     geo_planes(b), 1, c->err_dev);
+  hipLaunchKernelGGL(k_geo_fill, geo_grid(d.nplane), dim3(256), 0, c->stream, d.wdist,
+                     (long)d.nplane, 1.0e10);                  // DEFAULT_WALL_DIST
+  HIPCHK(hipGetLastError());
+  HIPCHK(hipMemcpyAsync(c->err_host, c->err_dev, sizeof(int), hipMemcpyDeviceToHost, c->stream));
+  HIPCHK(hipStreamSynchronize(c->stream));
+  const int code = *c->err_host;
+  if (code) {
+    *c->err_host = 0;
+    hipMemsetAsync(c->err_dev, 0, sizeof(int), c->stream);
+    if (code == 4) return fail("negative volume in PLOT3D block");
+    return fail("negative %c-face area in PLOT3D block", "ijk"[(code - 5) % 3]);
+  }
+  return 0;
+}
+
+// SwapGeomSlice of one interblock connection (utility.cpp:212-255; PutGeomSlice
+// procBlock.cpp:3165-3600 as connections.py restates it).  The copy records of both sides
+// are built here from the connection's index map; the sender's volumes of the slice come
+// back to the host (surface-sized) for the T-intersection test.
+int geo_swap(agx_ctx* c, Conn& k) {
+  const int ng = c->cfg.n_ghost;
+  const agx_connection cc = k.c;           // (the borders as they are before this swap)
+  std::vector<GeoCopy> rec[2];
+  bool adj[2][4] = {};
+  for (int recv = 0; recv < 2; ++recv) {
+    const int snd = 1 - recv;
+    Block& R = c->blocks[cc.local_block[recv]];
+    Block& S = c->blocks[cc.local_block[snd]];
+    std::vector<int> ca, cs;
+    auto idxR = [&](int i, int j, int kk) { ca.push_back(i); ca.push_back(j); ca.push_back(kk);
+                                            return R.d.idx(i, j, kk); };
+    auto idxS = [&](int i, int j, int kk) { cs.push_back(i); cs.push_back(j); cs.push_back(kk);
+                                            return S.d.idx(i, j, kk); };
+    MapOut m;
+    build_side_map(cc, recv, ng, idxR, idxS, m);
+    const long n = (long)m.dst.size();
+    if (n == 0) continue;
+    // the sender's volume of every cell of the slice
+    std::vector<double> svol(n);
+    long* idx_dev = nullptr;
+    double* buf = nullptr;
+    if (to_device(m.src, &idx_dev)) return 1;
+    HIPCHK(hipMalloc((void**)&buf, sizeof(double) * n));
+    hipLaunchKernelGGL(k_geo_gather1, geo_grid(n), dim3(256), 0, c->stream, S.d.vol, idx_dev, n, buf);
+    HIPCHK(hipGetLastError());
+    HIPCHK(hipMemcpyAsync(svol.data(), buf, sizeof(double) * n, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(hipStreamSynchronize(c->stream));
+    HIPCHK(hipFree(idx_dev));
+    HIPCHK(hipFree(buf));
+    int orient = cc.orientation;
+    if (recv == 1) { if (orient == 4) orient = 5; else if (orient == 5) orient = 4; }
+    int rd1, rd2, rd3, sd1, sd2, sd3;
+    dirs_of(cc.boundary[recv], rd1, rd2, rd3);
+    dirs_of(cc.boundary[snd], sd1, sd2, sd3);
+    const int len1 = cc.d1_end[recv] - cc.d1_start[recv] + 2 * ng;
+    const int len2 = cc.d2_end[recv] - cc.d2_start[recv] + 2 * ng;
+    const int blk_start = cc.boundary[recv] % 2 == 0 ? cc.const_surf[recv] : -ng;
+    const bool lluu = (cc.boundary[0] + cc.boundary[1]) % 2 == 0;
+    const bool neg1 = orient == 3 || orient == 4 || orient == 7 || orient == 8;
+    const bool neg2 = orient >= 5 && orient <= 8;
+    const int nr[3] = {R.d.ni, R.d.nj, R.d.nk};
+    auto& out = rec[recv];
+    for (long q = 0; q < n; ++q) {
+      const int* a = &ca[3 * q];
+      const int* sc = &cs[3 * q];
+      if (svol[q] == 0.0) {
+        // T-intersection (procBlock.cpp:3213-3262): an empty sender cell on a line that is
+        // physical in one in-plane direction only marks the patch border it lies on
+        bool ph[3];
+        for (int d = 0; d < 3; ++d) ph[d] = a[d] >= 0 && a[d] < nr[d];
+        for (int d = 0; d < 3; ++d) {
+          if (!(ph[d] && !ph[(d + 1) % 3] && !ph[(d + 2) % 3])) continue;
+          if (d == rd1) adj[recv][a[rd2] < cc.d2_start[recv] ? 2 : 3] = true;
+          else if (d == rd2) adj[recv][a[rd1] < cc.d1_start[recv] ? 0 : 1] = true;
+        }
+        continue;
+      }
+      const int l1 = a[rd1] - (cc.d1_start[recv] - ng), l2 = a[rd2] - (cc.d2_start[recv] - ng),
+                l3 = a[rd3] - blk_start;
+      out.push_back(GeoCopy{m.dst[q], m.src[q], 0, 0, 0, 0});
+      out.push_back(GeoCopy{m.dst[q], m.src[q], 1, 0, 0, 0});
+      auto put = [&](int dr, int ds, int a_off, int s_off, bool flip) {
+        int ai[3] = {a[0], a[1], a[2]}, si[3] = {sc[0], sc[1], sc[2]};
+        ai[dr] += a_off; si[ds] += s_off;
+        out.push_back(GeoCopy{R.d.idx(ai[0], ai[1], ai[2]), S.d.idx(si[0], si[1], si[2]), 2, dr,
+                              ds, flip ? 1 : 0});
+      };
+      // direction 3 (procBlock.cpp:3276-3300): lower/lower or upper/upper pairs take the
+      // sender's face above the cell, running backwards, normal flipped
+      const int s3 = lluu ? 1 : 0, fac3 = lluu ? -1 : 1;
+      put(rd3, sd3, 0, s3, lluu);
+      if (l3 == ng - 1) put(rd3, sd3, 1, s3 + fac3, lluu);
+      const int drs[2] = {rd1, rd2}, dss[2] = {sd1, sd2}, lc[2] = {l1, l2},
+                le[2] = {len1 - 1, len2 - 1};
+      const bool ng_[2] = {neg1, neg2};
+      for (int w = 0; w < 2; ++w) {
+        if (!ng_[w]) {
+          put(drs[w], dss[w], 0, 0, false);
+          if (lc[w] == le[w]) put(drs[w], dss[w], 1, 1, false);
+        } else {               // reversed: upper / lower faces swap
+          put(drs[w], dss[w], 0, 1, true);
+          if (lc[w] == le[w]) put(drs[w], dss[w], 1, 0, true);
+        }
+      }
+    }
+  }
+  // both slices are taken (gathered) before either insert (utility.cpp:232-233)
+  GeoCopy* rec_dev[2] = {nullptr, nullptr};
+  double* buf_dev[2] = {nullptr, nullptr};
+  for (int recv = 0; recv < 2; ++recv) {
+    const long n = (long)rec[recv].size();
+    if (n == 0) continue;
+    Block& S = c->blocks[cc.local_block[1 - recv]];
+    HIPCHK(hipMalloc((void**)&rec_dev[recv], sizeof(GeoCopy) * n));
+    HIPCHK(hipMalloc((void**)&buf_dev[recv], sizeof(double) * 7 * n));
+    HIPCHK(hipMemcpyAsync(rec_dev[recv], rec[recv].data(), sizeof(GeoCopy) * n,
+                          hipMemcpyHostToDevice, c->stream));
+    hipLaunchKernelGGL(k_geo_gather, geo_grid(n), dim3(256), 0, c->stream, geo_planes(S),
+                       rec_dev[recv], n, buf_dev[recv]);
+  }
+  for (int recv = 0; recv < 2; ++recv) {
+    const long n = (long)rec[recv].size();
+    if (n == 0) continue;
+    Block& R = c->blocks[cc.local_block[recv]];
+    hipLaunchKernelGGL(k_geo_scatter, geo_grid(n), dim3(256), 0, c->stream, geo_planes(R),
+                       rec_dev[recv], n, buf_dev[recv]);
+  }
+  HIPCHK(hipGetLastError());
+  HIPCHK(hipStreamSynchronize(c->stream));
+  for (int recv = 0; recv < 2; ++recv) {
+    if (rec_dev[recv]) HIPCHK(hipFree(rec_dev[recv]));
+    if (buf_dev[recv]) HIPCHK(hipFree(buf_dev[recv]));
+    for (int q = 0; q < 4; ++q)
+      if (adj[recv][q]) k.c.patch_border[4 * recv + q] = 1;
+  }
+  return 0;
+}
+
+// SwapWallDist (gridLevel.cpp:261-285) of one connection, with its borders as SwapGeomSlice
+// left them
+int geo_swap_wall_dist(agx_ctx* c, Conn& k) {
+  const int ng = c->cfg.n_ghost;
+  const agx_connection& cc = k.c;
+  long* dst_dev[2] = {nullptr, nullptr};
+  long* src_dev[2] = {nullptr, nullptr};
+  double* buf[2] = {nullptr, nullptr};
+  long n[2] = {0, 0};
+  for (int recv = 0; recv < 2; ++recv) {
+    Block& R = c->blocks[cc.local_block[recv]];
+    Block& S = c->blocks[cc.local_block[1 - recv]];
+    auto idxR = [&](int i, int j, int kk) { return R.d.idx(i, j, kk); };
+    auto idxS = [&](int i, int j, int kk) { return S.d.idx(i, j, kk); };
+    MapOut m;
+    build_side_map(cc, recv, ng, idxR, idxS, m);
+    n[recv] = (long)m.dst.size();
+    if (n[recv] == 0) continue;
+    if (to_device(m.dst, &dst_dev[recv]) || to_device(m.src, &src_dev[recv])) return 1;
+    HIPCHK(hipMalloc((void**)&buf[recv], sizeof(double) * n[recv]));
+    hipLaunchKernelGGL(k_geo_gather1, geo_grid(n[recv]), dim3(256), 0, c->stream, S.d.wdist,
+                       src_dev[recv], n[recv], buf[recv]);
+  }
+  for (int recv = 0; recv < 2; ++recv) {
+    if (n[recv] == 0) continue;
+    Block& R = c->blocks[cc.local_block[recv]];
+    hipLaunchKernelGGL(k_geo_scatter1, geo_grid(n[recv]), dim3(256), 0, c->stream, R.d.wdist,
+                       dst_dev[recv], n[recv], buf[recv]);
+  }
+  HIPCHK(hipGetLastError());
+  HIPCHK(hipStreamSynchronize(c->stream));
+  for (int recv = 0; recv < 2; ++recv) {
+    if (dst_dev[recv]) HIPCHK(hipFree(dst_dev[recv]));
+    if (src_dev[recv]) HIPCHK(hipFree(src_dev[recv]));
+    if (buf[recv]) HIPCHK(hipFree(buf[recv]));
+  }
+  return 0;
+}
+
+// agx_setup_finalize, node-built blocks: everything between the metrics and the index maps
+int geo_complete(agx_ctx* c) {
+  const int ng = c->cfg.n_ghost;
+  for (auto& k : c->conns) {
+    const agx_connection& cc = k.c;
+    const bool l0 = cc.rank[0] == c->rank, l1 = cc.rank[1] == c->rank;
+    if (!l0 && !l1) continue;
+    if (!(l0 && l1))
+      return fail("agx_setup_finalize: node-built blocks with a connection whose partner is on "
+                  "another rank (blocks %d and %d): ghost geometry and wall points would have "
+                  "to cross ranks; create the blocks from arrays for multi-rank runs",
+                  cc.block[0], cc.block[1]);
+    for (int s = 0; s < 2; ++s)
+      if (cc.local_block[s] < 0 || cc.local_block[s] >= (int)c->blocks.size())
+        return fail("connection refers to unknown block");
+  }
+  // face centres of the physical faces, for the pass only
+  for (auto& b : c->blocks) {
+    const BlockDev& d = b.d;
+    if (!b.nodes_dev) return fail("agx_setup_finalize: the geometry of this context is complete");
+    HIPCHK(hipMalloc((void**)&b.fcen, sizeof(double) * 9 * d.nplane));
+    HIPCHK(hipMemsetAsync(b.fcen, 0, sizeof(double) * 9 * d.nplane, c->stream));
+    const long nn = (long)(d.ni + 1) * (d.nj + 1) * (d.nk + 1);
+    hipLaunchKernelGGL(k_metrics_planes, geo_grid(nn), dim3(256), 0, c->stream, d, b.nodes_dev,
+                       geo_planes(b), 2, c->err_dev);
+  }
+  HIPCHK(hipGetLastError());
+  // 1. AssignGhostCellsGeom: layer by layer, surface by surface in the given order
+  for (auto& b : c->blocks) {
+    const BlockDev& d = b.d;
+    const int nd[3] = {d.ni, d.nj, d.nk};
+    for (int layer = 1; layer <= ng; ++layer)
+      for (const agx_bc_surface& s : b.surf_host) {
+        if (s.bc_type == AGX_BC_INTERBLOCK) continue;
+        GhostGeomOp o;
+        const int st = surface_type(s);
+        o.d3 = (st - 1) / 2; o.upper = st % 2 == 0; o.layer = layer;
+        surface_range(s, o.lo, o.hi);
+        o.n3 = nd[o.d3];
+        const int da = o.d3 == 0 ? 1 : 0, db = o.d3 == 2 ? 1 : 2;
+        const long n = (long)(o.hi[da] - o.lo[da] + 1) * (o.hi[db] - o.lo[db] + 1);
+        hipLaunchKernelGGL(k_ghost_geom, geo_grid(n), dim3(256), 0, c->stream, d, geo_planes(b), o);
+      }
+  }
+  HIPCHK(hipGetLastError());
+  // 2. SwapGeomSlice, connection by connection in creation order
+  for (auto& k : c->conns)
+    if (k.c.is_interblock && k.c.rank[0] == c->rank && geo_swap(c, k)) return 1;
+  // 3. AssignGhostCellsGeomEdge, then CalcCellWidths over the whole padded array
+  for (auto& b : c->blocks) {
+    const BlockDev& d = b.d;
+    const int nd[3] = {d.ni, d.nj, d.nk};
+    const GeoPlanes g = geo_planes(b);
+    for (int dir = 0; dir < 3; ++dir) {
+      EdgeGeomOp o;
+      o.d = dir; o.two = (dir + 1) % 3; o.three = (dir + 2) % 3; o.nd = nd[dir];
+      const int max2 = nd[o.two], max3 = nd[o.three];
+      for (int layer3 = 1; layer3 <= ng; ++layer3)
+        for (int layer2 = 1; layer2 <= ng; ++layer2)
+          for (int cn = 0; cn < 4; ++cn) {
+            o.u2 = cn > 1; o.u3 = cn % 2 == 1;
+            o.p2 = o.u2 ? max2 + layer2 - 2 : 1 - layer2;
+            o.g2 = o.u2 ? o.p2 + 1 : o.p2 - 1;
+            o.i2 = o.u2 ? max2 - layer2 : layer2 - 1;
+            o.p3 = o.u3 ? max3 + layer3 - 2 : 1 - layer3;
+            o.g3 = o.u3 ? o.p3 + 1 : o.p3 - 1;
+            hipLaunchKernelGGL(k_edge_geom, geo_grid(o.nd + 1), dim3(256), 0, c->stream, d, g, o);
+          }
+    }
+    const long ncell = (long)(d.ni + 2 * ng) * (d.nj + 2 * ng) * (d.nk + 2 * ng);
+    hipLaunchKernelGGL(k_cell_widths, geo_grid(ncell), dim3(256), 0, c->stream, d, g, d.wid[0],
+                       d.wid[1], d.wid[2]);
+  }
+  HIPCHK(hipGetLastError());
+  // 4. wall distance (main.cpp:191-203, procBlock::CalcWallDistance, SwapWallDist)
+  if (c->cfg.is_viscous) {
+    long nwall = 0;
+    for (auto& b : c->blocks)
+      for (const agx_bc_surface& s : b.surf_host) {
+        if (s.bc_type != AGX_BC_VISCOUSWALL) continue;
+        int lo[3], hi[3];
+        surface_range(s, lo, hi);
+        nwall += (long)(hi[0] - lo[0]) * (hi[1] - lo[1]) * (hi[2] - lo[2]);
+      }
+    if (nwall > 0) {
+      double* wall = nullptr;
+      HIPCHK(hipMalloc((void**)&wall, sizeof(double) * 3 * nwall));
+      long off = 0;
+      for (auto& b : c->blocks)
+        for (const agx_bc_surface& s : b.surf_host) {
+          if (s.bc_type != AGX_BC_VISCOUSWALL) continue;
+          int lo[3], hi[3];
+          surface_range(s, lo, hi);
+          const long n = (long)(hi[0] - lo[0]) * (hi[1] - lo[1]) * (hi[2] - lo[2]);
+          hipLaunchKernelGGL(k_wall_points, geo_grid(n), dim3(256), 0, c->stream, b.d,
+                             geo_planes(b), (surface_type(s) - 1) / 2, lo[0], lo[1], lo[2], hi[0],
+                             hi[1], hi[2], wall + 3 * off);
+          off += n;
+        }
+      for (auto& b : c->blocks) {
+        const BlockDev& d = b.d;
+        const long ncell = (long)d.ni * d.nj * d.nk;
+        hipLaunchKernelGGL(k_nearest_wall_planes, geo_grid(ncell), dim3(256), 0, c->stream, d,
+                           geo_planes(b), nwall, wall);
+        for (const agx_bc_surface& s : b.surf_host) {
+          int lo[3], hi[3];
+          surface_range(s, lo, hi);
+          const int st = surface_type(s);
+          const long n = (long)(hi[0] - lo[0]) * (hi[1] - lo[1]) * (hi[2] - lo[2]) * ng;
+          hipLaunchKernelGGL(k_wall_dist_ghosts, geo_grid(n), dim3(256), 0, c->stream, d, d.wdist,
+                             (st - 1) / 2, st % 2 == 0 ? 1 : 0,
+                             s.bc_type == AGX_BC_VISCOUSWALL ? 1 : 0, lo[0], lo[1], lo[2], hi[0],
+                             hi[1], hi[2]);
+        }
+      }
+      HIPCHK(hipGetLastError());
+      HIPCHK(hipStreamSynchronize(c->stream));
+      HIPCHK(hipFree(wall));
+      for (auto& k : c->conns)
+        if (k.c.rank[0] == c->rank && geo_swap_wall_dist(c, k)) return 1;
+    }
+  }
+  // 5. what agx_block_create does after its uploads
+#if AGX_FAST
+  for (auto& b : c->blocks)
+    if (b.d.d2.base) {
+      const long n = (long)b.d.d2.Pi * b.d.d2.Pj * (b.d.nk + 2 * b.d.ng);
+      hipLaunchKernelGGL(k_d2_geo, dim3((n + 255) / 256), dim3(256), 0, c->stream, b.d);
+    }
+  HIPCHK(hipGetLastError());
+#endif
+  HIPCHK(hipStreamSynchronize(c->stream));
+  for (auto& b : c->blocks) {
+    HIPCHK(hipFree(b.fcen)); b.fcen = nullptr;
+    HIPCHK(hipFree(b.nodes_dev)); b.nodes_dev = nullptr;
+  }
+  return 0;
+}
+}  // namespace
+
 extern "C" {
 
 const char* agx_last_error(void) { return g_err; }
@@ -1226,6 +1586,8 @@ void agx_ctx_destroy(agx_ctx* c) {
       if (p) hipFree(p);
     if (b.d2_tab) hipFree(b.d2_tab);
     if (b.kp_mem) hipFree(b.kp_mem);
+    if (b.nodes_dev) hipFree(b.nodes_dev);
+    if (b.fcen) hipFree(b.fcen);
     for (auto& g1 : b.sweep_graph) for (auto& g2 : g1) for (auto& g3 : g2)
       if (g3) hipGraphExecDestroy(g3);
     if (b.surf_dev) hipFree(b.surf_dev);
@@ -1396,6 +1758,19 @@ int agx_block_create(agx_ctx* c, const agx_block_geom* g, int* block_id) {
   if (!c->have_cfg) return fail("agx_config_set must precede agx_block_create");
   if (g->ng != c->cfg.n_ghost) return fail("block ghost layers != config n_ghost");
   if (g->ni < 1 || g->nj < 1 || g->nk < 1) return fail("empty block");
+  const bool from_nodes = g->nodes != nullptr;
+  if (from_nodes) {
+    const double* arr[9] = {g->farea_i, g->farea_j, g->farea_k, g->vol, g->center, g->width_i,
+                            g->width_j, g->width_k, g->wall_dist};
+    const char* nm[9] = {"farea_i", "farea_j", "farea_k", "vol", "center", "width_i", "width_j",
+                         "width_k", "wall_dist"};
+    for (int q = 0; q < 9; ++q)
+      if (arr[q])
+        return fail("agx_block_create: nodes given together with %s (a block is built from "
+                    "its nodes or from the nine arrays)", nm[q]);
+  }
+  if (!c->blocks.empty() && c->blocks[0].node_built != from_nodes)
+    return fail("agx_block_create: a context holds node-built or array-built blocks, not both");
   HIPCHK(hipSetDevice(c->device));
   c->blocks.emplace_back();
   Block& b = c->blocks.back();
@@ -1481,6 +1856,12 @@ int agx_block_create(agx_ctx* c, const agx_block_geom* g, int* block_id) {
     HIPCHK(hipMalloc((void**)&b.d2, sizeof(double) * z.nd2 * D2_DOUBLES));
     HIPCHK(hipMemsetAsync(b.d2, 0, sizeof(double) * z.nd2 * D2_DOUBLES, c->stream));
     z.base = b.d2;
+  }
+  b.node_built = from_nodes;
+  if (from_nodes) {
+    if (geo_block_metrics(c, b, g->nodes)) return 1;
+    *block_id = (int)c->blocks.size() - 1;
+    return 0;
   }
   const int ci = d.ni + 2 * d.ng, cj = d.nj + 2 * d.ng, ck = d.nk + 2 * d.ng;
   if (upload_aos(c, b, g->farea_i, d.fa[0], 4, ci + 1, cj, ck, d.ng)) return 1;
@@ -1728,6 +2109,7 @@ int halo_batch_tables(agx_ctx* c, int what) {
 int agx_setup_finalize(agx_ctx* c) {
   HIPCHK(hipSetDevice(c->device));
   const int ng = c->cfg.n_ghost;
+  if (!c->blocks.empty() && c->blocks[0].node_built && geo_complete(c)) return 1;
   long max_parts = 1, max_halo = 1;
   long march_parts = 0;
   for (auto& blk : c->blocks) {
@@ -1877,6 +2259,22 @@ static int field_info(Block& b, int field, double* const** p, int* ncomp, int* g
   }
   return 1;
 }
+// the geometry planes (download only): `face` = the direction with one more entry, or -1
+static int geom_field_info(Block& b, int field, double* const** p, int* ncomp, int* face) {
+  BlockDev& d = b.d;
+  static thread_local double* one[1];
+  *face = -1;
+  switch (field) {
+    case AGX_FIELD_VOLUME: one[0] = d.vol; *p = one; *ncomp = 1; return 0;
+    case AGX_FIELD_CENTER: *p = d.cen; *ncomp = 3; return 0;
+    case AGX_FIELD_FAREA_I: case AGX_FIELD_FAREA_J: case AGX_FIELD_FAREA_K:
+      *face = field - AGX_FIELD_FAREA_I; *p = d.fa[*face]; *ncomp = 4; return 0;
+    case AGX_FIELD_WIDTH_I: case AGX_FIELD_WIDTH_J: case AGX_FIELD_WIDTH_K:
+      one[0] = d.wid[field - AGX_FIELD_WIDTH_I]; *p = one; *ncomp = 1; return 0;
+    case AGX_FIELD_WALL_DIST: one[0] = d.wdist; *p = one; *ncomp = 1; return 0;
+  }
+  return 1;
+}
 
 // x of the D2 LU-SGS path <-> the SoA planes the field transfers use
 static int d2_x_copy(agx_ctx* c, Block& b, int to_d2) {
@@ -1945,6 +2343,13 @@ int agx_field_download(agx_ctx* c, int id, int field, double* out) {
     return download_aos(c, b, out, one, 1, b.d.ni + 2 * g, b.d.nj + 2 * g, b.d.nk + 2 * g, g);
   }
   double* const* p; int nc, gh;
+  if (!geom_field_info(b, field, &p, &nc, &gh)) {      // (gh: the face direction here)
+    if (b.node_built && !c->finalized)
+      return fail("the geometry of a node-built block is complete after agx_setup_finalize");
+    const int g = b.d.ng;
+    return download_aos(c, b, out, p, nc, b.d.ni + 2 * g + (gh == 0), b.d.nj + 2 * g + (gh == 1),
+                        b.d.nk + 2 * g + (gh == 2), g);
+  }
   if (field_info(b, field, &p, &nc, &gh))
     return fail("unknown field %d", field);
   const int g = gh ? b.d.ng : 0;
@@ -2081,6 +2486,9 @@ int agx_field_upload(agx_ctx* c, int id, int field, const double* in) {
   if (id < 0 || id >= (int)c->blocks.size()) return fail("bad block id %d", id);
   Block& b = c->blocks[id];
   double* const* p; int nc, gh;
+  if (field >= AGX_FIELD_VOLUME && field <= AGX_FIELD_WALL_DIST)
+    return fail("field %d (geometry) cannot be uploaded: it is set when the block is created",
+                field);
   if (field_info(b, field, &p, &nc, &gh)) return fail("field %d cannot be uploaded", field);
   const int g = gh ? b.d.ng : 0;
   if (upload_aos(c, b, in, p, nc, b.d.ni + 2 * g, b.d.nj + 2 * g, b.d.nk + 2 * g, g)) return 1;

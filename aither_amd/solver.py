@@ -15,6 +15,7 @@ import numpy as np
 
 from . import abi
 from .case import builder as _b
+from .case import geometry as _geo
 
 EPS = 1.0e-30  # macros.hpp.in:20
 
@@ -134,10 +135,14 @@ class Solver:
             bg = abi.BlockGeom()
             bg.ni, bg.nj, bg.nk, bg.ng = g.ni, g.nj, g.nk, g.ng
             bg.parent_block, bg.global_pos = blk.parent, blk.global_pos
-            arrs = dict(farea_i=g.farea["i"].a, farea_j=g.farea["j"].a,
-                        farea_k=g.farea["k"].a, vol=g.vol.a, center=g.center.a,
-                        width_i=g.width["i"].a, width_j=g.width["j"].a,
-                        width_k=g.width["k"].a, wall_dist=g.wall_dist.a)
+            if isinstance(g, _geo.NodeGeometry):
+                # the nodes alone: the library forms the geometry on the device
+                arrs = dict(nodes=g.nodes)
+            else:
+                arrs = dict(farea_i=g.farea["i"].a, farea_j=g.farea["j"].a,
+                            farea_k=g.farea["k"].a, vol=g.vol.a, center=g.center.a,
+                            width_i=g.width["i"].a, width_j=g.width["j"].a,
+                            width_k=g.width["k"].a, wall_dist=g.wall_dist.a)
             for name, a in arrs.items():
                 a = np.ascontiguousarray(a, dtype=np.float64)
                 self._keep.append(a)
@@ -225,9 +230,26 @@ class Solver:
         return out
 
     def download(self, field, gb):
+        if field in abi.GEOM_FIELDS:
+            return self.geometry(field, gb)
         out = np.empty(self._shape(field, gb))
         self.api.check(self.api.field_download(
             self.ctx, self.block_ids[gb], abi.FIELD[field],
+            out.ctypes.data_as(abi.c_dp)), "field_download")
+        return out
+
+    def geometry(self, name, gb):
+        """One of the geometry arrays of block gb as the device holds it (abi.GEOM_FIELDS:
+        volume, center, farea_i/j/k, width_i/j/k, wall_dist), in the host layout
+        agx_block_geom documents, ghost cells included.  For a block created from its nodes
+        this is the only place its centres or wall distance can be had."""
+        comps, face = abi.GEOM_FIELDS[name]
+        g = self.case.blocks[gb].geom
+        pad = 2 * g.ng
+        out = np.empty((g.nk + pad + (face == "k"), g.nj + pad + (face == "j"),
+                        g.ni + pad + (face == "i"), comps))
+        self.api.check(self.api.field_download(
+            self.ctx, self.block_ids[gb], abi.FIELD[name],
             out.ctypes.data_as(abi.c_dp)), "field_download")
         return out
 

@@ -89,7 +89,15 @@ enum { AGX_FIELD_STATE = 0,      /* state_      nEq, with ghosts           */
         * exchanged); no ghosts.
         * VEL_GRAD: 9 per cell, [3 r + c] = d(velocity c)/d(x_r) (tensor.hpp) */
        AGX_FIELD_VEL_GRAD = 10, AGX_FIELD_TEMP_GRAD = 11,
-       AGX_FIELD_DENS_GRAD = 12, AGX_FIELD_PRESS_GRAD = 13
+       AGX_FIELD_DENS_GRAD = 12, AGX_FIELD_PRESS_GRAD = 13,
+       /* the geometry the device holds, in the host layout agx_block_geom documents, ghost
+        * cells included (download only; agx_field_upload refuses them): what a node-built
+        * block was given by the library, or what an array-built one was created from */
+       AGX_FIELD_VOLUME = 14,    /* vol_        1                               */
+       AGX_FIELD_CENTER = 15,    /* center_     3                               */
+       AGX_FIELD_FAREA_I = 16, AGX_FIELD_FAREA_J = 17, AGX_FIELD_FAREA_K = 18, /* 4 */
+       AGX_FIELD_WIDTH_I = 19, AGX_FIELD_WIDTH_J = 20, AGX_FIELD_WIDTH_K = 21, /* 1 */
+       AGX_FIELD_WALL_DIST = 22  /* wallDist_   1                               */
 };
 
 /* variables of a function file, WriteFunFile (output.cpp:235-407): formed and
@@ -203,6 +211,17 @@ typedef struct agx_block_geom {
   const double *center;
   const double *width_i, *width_j, *width_k;   /* cellWidthI/J/K_          */
   const double *wall_dist;   /* may be NULL for inviscid                   */
+  /* OR the node coordinates alone, [nk+1][nj+1][ni+1][3], i fastest, nondimensional (as
+   * agx_plot3d_metrics takes them), with all nine pointers above NULL: the library forms the
+   * whole geometry on the device.  agx_block_create computes the metrics of the physical
+   * cells (and refuses a block turned inside out); agx_setup_finalize completes the ghost
+   * geometry in the reference's order -- AssignGhostCellsGeom, SwapGeomSlice (which may set
+   * entries of the stored connections' patch_border, the T-intersection rule),
+   * AssignGhostCellsGeomEdge, CalcCellWidths and, in viscous runs, CalcWallDistance and
+   * SwapWallDist.  All blocks of a context are built the same way, and all partners of its
+   * connections are on this rank.  NULL: the arrays above are used.  Callers zero the
+   * struct, so one compiled before this field existed passes NULL. */
+  const double *nodes;
 } agx_block_geom;
 
 /* boundary-state data for one surface: the union of the fields the
@@ -274,7 +293,8 @@ int agx_block_create(agx_ctx *ctx, const agx_block_geom *geom, int *block_id);
 int agx_block_set_bcs(agx_ctx *ctx, int block_id, int n_surfaces,
                       const agx_bc_surface *surfaces);
 int agx_conn_create(agx_ctx *ctx, const agx_connection *conn, int *conn_id);
-/* finish setup: build index maps, hyperplane order, allocate work arrays */
+/* finish setup: complete the geometry of node-built blocks (agx_block_geom.nodes), build
+ * index maps, hyperplane order, allocate work arrays */
 int agx_setup_finalize(agx_ctx *ctx);
 
 /* ---- state movement ---------------------------------------------------- */

@@ -109,7 +109,11 @@ class hotPath {
     Check(AGX_SYM(config_set)(ctx_, &cfg), "hotPath::Configure");
   }
   // geometry of one procBlock (ghost-inclusive arrays in the reference's own
-  // layout), its boundarySurfaces and the initial state; returns the block id
+  // layout), its boundarySurfaces and the initial state; returns the block id.
+  // Or geom.nodes alone (plot3dBlock's coordinates, the nine array pointers null): the
+  // library forms the whole geometry on the device, complete after Finalize; an adapter
+  // whose host code wants cell centres or the wall distance then fetches them with
+  // agx_field_download and AGX_FIELD_CENTER / AGX_FIELD_WALL_DIST
   int AddBlock(const agx_block_geom &geom, const std::vector<agx_bc_surface> &surfs) {
     int id = -1;
     Check(AGX_SYM(block_create)(ctx_, &geom, &id), "hotPath::AddBlock");
