@@ -300,6 +300,26 @@ __device__ __forceinline__ void kp_term_mem(const Z& z, const G& g, bool viscous
 // advance the block's epoch.  Against flag + payload (store, drain, barrier, flag store,
 // poll, barrier, load) this takes the store acknowledgement, the flag's own trip and one
 // barrier out of every plane-to-plane hop.
+//
+// THE INVARIANT the two-bit tag rests on.  A plane polls only cells of its own block (the
+// positions of its live lanes in plane kq, and only when that plane is swept by this launch:
+// has_pre); ghost positions are read once, never polled.  The launches that write x in the
+// D2 arrays are
+//   * k_lusgs_prepare with write_x (more than one sweep, or a block with a connection
+//     side: someone reads the initial x)  -- every padded position, tagged, epoch advanced;
+//   * each half sweep (k_lusgs_kp)        -- every cell of the block, tagged, epoch advanced;
+//   * k_d2_x_copy towards the D2 arrays (a field upload, the multigrid transfers)
+//                                         -- every padded position, tagged, epoch advanced;
+//   * the halo scatter of AGX_HALO_UPDATE -- ghost positions only, the sender's bits as they
+//     are, epoch NOT advanced (nothing polls what it writes).
+// So every launch that advances a block's epoch rewrites EVERY position a later launch of
+// that block polls, and what a poller finds before its producer has stored is the value of
+// the block's previous epoch: tag (epoch - 1) & 3, never epoch & 3 -- however many launches
+// an iteration has (the tag of the third sweep repeats that of the first: harmless, the
+// values in between were all overwritten).  A writer that advanced the epoch and skipped
+// polled positions, or wrote them without advancing it, would break this after four epochs.
+// (tests/test_production_paths_gpu.py: test_kp_tag_wrap*, three to five sweeps, with
+// connections and under multigrid, parity and run-to-run bits.)
 struct KpArgs {
   int* ticket;      // next k-plane to hand out
   int* err;
@@ -622,12 +642,18 @@ k_lusgs_kp(KpBlk b, KpGas g, int viscous, int nsl, KpArgs kp) {
           const v2d v0 = {xn[0], xn[1]}, v1 = {xn[2], xn[3]}, v2 = {xn[4], ainv};
           // (s_nop 4: the base may have been written by a v_readlane just before --
           // VALU-writes-SGPR -> VMEM needs 5 wait states, and the compiler's hazard
-          // recogniser does not look inside inline asm)
-          asm volatile("s_nop 4\n\tglobal_store_dwordx4 %0, %1, %2 sc1"
+          // recogniser does not look inside inline asm;
+          // s_nop 1 after the store: a store of more than 64 bits followed by a VALU write of
+          // its data registers needs 2 wait states on gfx940 and later, and the recogniser
+          // does not know that this asm is such a store.  Without it the instance with the
+          // most live registers, <.., CONN = true, CH = 2>, stored wrong x: 3e-2 of the
+          // update off the oracle, different from run to run
+          // (tests/test_production_paths_gpu.py::test_kp_two_chunks[stacked-*]))
+          asm volatile("s_nop 4\n\tglobal_store_dwordx4 %0, %1, %2 sc1\n\ts_nop 1"
                        :: "v"(po), "v"(v0), "s"(z.pab(PA_X + 0) + kbase * 16) : "memory");
-          asm volatile("s_nop 4\n\tglobal_store_dwordx4 %0, %1, %2 sc1"
+          asm volatile("s_nop 4\n\tglobal_store_dwordx4 %0, %1, %2 sc1\n\ts_nop 1"
                        :: "v"(po), "v"(v1), "s"(z.pab(PA_X + 1) + kbase * 16) : "memory");
-          asm volatile("s_nop 4\n\tglobal_store_dwordx4 %0, %1, %2 sc1"
+          asm volatile("s_nop 4\n\tglobal_store_dwordx4 %0, %1, %2 sc1\n\ts_nop 1"
                        :: "v"(po), "v"(v2), "s"(z.pab(PA_X + 2) + kbase * 16) : "memory");
         }
         // hand-over to the next diagonal through LDS

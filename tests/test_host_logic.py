@@ -320,3 +320,106 @@ def test_wall_functions_are_active_on_every_thermal_wall_type(oracle, tag):
     assert np.isfinite(res["wallLaw"]).all()
     d = np.abs(res[None] - res["wallLaw"]).reshape(-1, 7).max(axis=0)
     assert np.all(d[[1, 2, 3, 5, 6]] > 0.0), d
+
+
+def test_production_path_cases_select_their_branch():
+    """tests/test_production_paths_gpu.py: every case there has the property that selects the
+    branch it is there for -- the dispatch conditions of agx_api.hip restated on its tables, so
+    that a later change of a shape cannot silently stop covering a branch."""
+    from test_production_paths_gpu import (
+        CONFIG3, CONFIG4, FLUXES, FUSED_RUNS, KP_CH2, KP_CH2_RUNS, KP_CHUNK, KP_LIMIT,
+        KP_MAX_DIAG, KP_OVER, KP_TICKETS, KP_WRAP, KP_WRAP_MG, MAX_RESIDENT_WGS, ORIENT_DECKS,
+        SCHEMES, THIN_DECKS, THIN_SHAPES, TILE_I, TILE_J, TILE_N, VISC_TILE_RUNS, VTILE_I,
+        can_fuse, ghost_layers, kp_chunks, on_d2_path, tile_kw, tiles, uniform_flow_case)
+
+    def conn_sides(spec):
+        return spec.get("kind", "single") != "single"
+
+    # A: two chunks, all four (FULL, CONN) forms
+    forms = set()
+    for name, sweeps in KP_CH2_RUNS:
+        spec = KP_CH2[name]
+        assert on_d2_path(spec) and kp_chunks(spec["n"]) == 2, name
+        assert KP_CHUNK < min(spec["n"][:2]) <= KP_MAX_DIAG, name
+        forms.add((sweeps > 1, conn_sides(spec)))
+    assert forms == {(False, False), (True, False), (False, True), (True, True)}
+    assert min(KP_CH2["edge"]["n"][:2]) - KP_CHUNK == 2           # two live lanes
+    assert min(KP_CH2["filled"]["n"][:2]) - KP_CHUNK >= 32
+    # the limit, and one beyond it
+    assert on_d2_path(KP_LIMIT) and min(KP_LIMIT["n"][:2]) == KP_MAX_DIAG
+    assert 2 * 19 * 8 * (KP_MAX_DIAG + 2) > 48 * 1024             # hipFuncSetAttribute
+    assert on_d2_path(KP_OVER) and min(KP_OVER["n"][:2]) == KP_MAX_DIAG + 1
+    # tickets
+    for name, spec in KP_TICKETS.items():
+        assert on_d2_path(spec) and spec["n"][2] > MAX_RESIDENT_WGS, name
+    assert conn_sides(KP_TICKETS["stacked"]) and KP_TICKETS["stacked"]["axis"] == "k"
+    # tag wrap: single block, a connection across each of i, j, k, and the cube
+    assert {s.get("axis") for s in KP_WRAP.values() if s["kind"] == "stacked"} == set("ijk")
+    assert {s["kind"] for s in KP_WRAP.values()} == {"single", "stacked", "cube"}
+    assert all(on_d2_path(s) and s["equation_set"] == "navierStokes" for s in KP_WRAP.values())
+    assert on_d2_path(KP_WRAP_MG) and KP_WRAP_MG["matrix_sweeps"] >= 3 and \
+        KP_WRAP_MG["nblocks"] == 2 and KP_WRAP_MG["levels"] > 1
+    # B: all twelve instances, fused (both FUSE forms) and not; ragged tiles
+    gx, gy = tiles(TILE_N)
+    assert gx >= 3 and gy >= 3 and TILE_N[0] % TILE_I and TILE_N[1] % TILE_J
+    assert (TILE_N[0] + VTILE_I - 1) // VTILE_I >= 3 and TILE_N[0] % VTILE_I
+    assert min(256, max(1, gx * gy * TILE_N[2] // 8)) > 2          # march_plan: workgroups
+    assert len({(r, l, f) for r, l, f, ti in FUSED_RUNS if ti == "rk4"}) == 12
+    assert {(r, f) for r, l, f, ti in FUSED_RUNS if ti == "explicitEuler"} == \
+        {(r, f) for r in ("weno", "wenoZ") for f in FLUXES}
+    for r, l, f, ti in FUSED_RUNS:
+        assert can_fuse(tile_kw(r, l, f, time_integration=ti))
+    assert not can_fuse(tile_kw("weno", "none", "roe", time_integration="implicitEuler"))
+    assert len(SCHEMES) * len(FLUXES) == 12
+    assert 2 <= len(VISC_TILE_RUNS) <= 3
+    # thin blocks: no thicker than the ghost depth in some direction, or (the last shape) one
+    # tile column and a cell with ragged rows
+    for deck, kw in THIN_DECKS.items():
+        thin = [n for n in THIN_SHAPES if min(n) <= ghost_layers(kw)]
+        assert len(thin) >= 3 and any(min(n) < ghost_layers(kw) for n in thin), deck
+        for n in set(THIN_SHAPES) - set(thin):
+            assert n[0] > TILE_I and n[0] % TILE_I and n[1] % TILE_J, (n, deck)
+    assert ghost_layers(THIN_DECKS["weno_rk4"]) == 3 and can_fuse(THIN_DECKS["weno_rk4"])
+    assert on_d2_path(THIN_DECKS["lusgs1"]) and on_d2_path(THIN_DECKS["lusgs2"])
+    assert on_d2_path(THIN_DECKS["visc_central"]) and on_d2_path(THIN_DECKS["visc_central4th"])
+    assert THIN_DECKS["lusgs1"]["matrix_sweeps"] == 1 and THIN_DECKS["lusgs2"]["matrix_sweeps"] == 2
+    assert any(n[0] + n[1] - 1 == 1 for n in THIN_SHAPES)          # nsteps = 1
+    assert any(n[2] == 1 for n in THIN_SHAPES)
+    # C: every orientation under every deck
+    for name, changes in ORIENT_DECKS.items():
+        case = uniform_flow_case(**changes)
+        assert sorted({c.orientation for c in case.connections}) == list(range(1, 9)), name
+        assert len(case.connections) == 9 and len(case.blocks) == 10
+        if case.deck.is_viscous():
+            assert any(s.bc_type == "viscousWall" for s in case.blocks[0].surfaces)
+            assert np.abs(case.blocks[9].geom.wall_dist.a).max() > 0.0
+    ng3 = uniform_flow_case(**ORIENT_DECKS["weno_lusgs"])
+    assert ng3.ng == 3
+    assert ORIENT_DECKS["dplur3"]["matrix_sweeps"] >= 3
+    assert ORIENT_DECKS["visc_lusgs3"]["matrix_sweeps"] >= 3
+    assert uniform_flow_case(**ORIENT_DECKS["rans_lusgs"]).n_eq == 7
+    # D: the full sizes
+    assert CONFIG3["n"] == (256, 256, 256) and on_d2_path(CONFIG3)
+    assert CONFIG4["n"] == (128, 128, 128) and CONFIG4["splits"] == (2, 2, 2) and \
+        CONFIG4["matrix_solver"] == "dplur" and CONFIG4["matrix_sweeps"] == 4
+
+
+def test_oracle_runs_the_thin_block_cases(oracle):
+    """The thin-block cases of tests/test_production_paths_gpu.py on the oracle alone: blocks
+    one to three cells thick under WENO, LU-SGS, DPLUR and the viscous fluxes with a wall stay
+    finite and move -- none of the 24 combinations is ill-conditioned in the reference's own
+    formulas (none had to be dropped there)."""
+    from test_production_paths_gpu import THIN_DECKS, THIN_SHAPES, thin_case
+    for n in THIN_SHAPES:
+        for deck in sorted(THIN_DECKS):
+            case = thin_case(n, deck)
+            s = Solver(oracle, case)
+            for nn in range(2):
+                out = s.step(nn)
+            g = case.ng
+            st = s.download("state", 0)[g:-g, g:-g, g:-g]
+            ini = case.blocks[0].state[g:-g, g:-g, g:-g]
+            assert np.isfinite(st).all() and np.isfinite(out["l2"]).all(), (n, deck)
+            assert st[..., 0].min() > 0.5 and st[..., 4].min() > 0.3, (n, deck)
+            assert np.abs(st - ini).max() > 0.0, (n, deck)
+            s.close()
