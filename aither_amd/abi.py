@@ -45,6 +45,12 @@ for _n, _base in (("tempGrad", 32), ("densityGrad", 35), ("pressGrad", 38), ("tk
         OUT[f"{_n}_{_c}"] = _base + _q
 for _q, _c in enumerate(("mass", "mom_x", "mom_y", "mom_z", "energy", "tke", "sdr")):
     OUT[f"resid_{_c}"] = 47 + _q
+# variables of the wall function file (AGX_WALL_*), under the reference's names
+# (output.cpp:519-553); shearStress_x/y/z: the components, an extension
+WALL_OUT = {"yplus": 64, "shearStress": 65, "viscosityRatio": 66, "heatFlux": 67,
+            "frictionVelocity": 68, "density": 69, "pressure": 70, "temperature": 71,
+            "viscosity": 72, "tke": 73, "sdr": 74,
+            "shearStress_x": 75, "shearStress_y": 76, "shearStress_z": 77}
 
 c_dp = C.POINTER(C.c_double)
 

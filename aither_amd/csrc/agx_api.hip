@@ -89,6 +89,11 @@ struct Block {
   // wall-law surfaces (rans): offsets | wallData_ of their faces (BlockDev)
   int* wall_off_dev = nullptr;
   double* wall_mem = nullptr;
+  // viscousWall surfaces in the order given (the order of wallData_): what k_wall_pack
+  // walks, and the faces of all of them
+  std::vector<WallSurfDev> wall_tab;
+  WallSurfDev* wall_tab_dev = nullptr;
+  long wall_faces = 0;
 };
 
 struct ConnSide {          // what side s receives / sends
@@ -213,6 +218,7 @@ struct agx_ctx {
   int mresid_split = 1;      // bands of diagonals per XCD in k_matrix_resid_d2 (AGX_MRESID_SPLIT)
   bool mresid_march = true;  // AGX_MRESID=plane: one plane position per thread (comparison form)
   bool have_time_n = false;  // agx_store_time_n has run (nonreflecting BCs read consVarsN)
+  bool have_wall_data = false;   // a residual's viscous ghost fill has stored the wall-law data
   // agx_iterate fills the ghost cells for the NEXT call right after the update,
   // behind the norm read-back the host waits for, so that the GPU does not idle
   // while the host turns the iteration around
@@ -1595,6 +1601,7 @@ void agx_ctx_destroy(agx_ctx* c) {
     if (b.nr_mem) hipFree(b.nr_mem);
     if (b.wall_off_dev) hipFree(b.wall_off_dev);
     if (b.wall_mem) hipFree(b.wall_mem);
+    if (b.wall_tab_dev) hipFree(b.wall_tab_dev);
   }
   for (auto& k : c->conns) {
     for (int s = 0; s < 2; ++s) {
@@ -1969,6 +1976,35 @@ int agx_block_set_bcs(agx_ctx* c, int id, int n, const agx_bc_surface* s) {
     HIPCHK(hipMemset(b.wall_mem, 0, nd));        // y+ = 0: low-Re until the first ghost fill
     b.d.wall_off = b.wall_off_dev;
     b.d.wallv = (WallVars*)b.wall_mem;
+    c->have_wall_data = false;
+  }
+  // the table of the wall-surface output (agx_output_pack with AGX_WALL_*)
+  if (b.wall_tab_dev) HIPCHK(hipFree(b.wall_tab_dev));
+  b.wall_tab_dev = nullptr;
+  b.wall_tab.clear();
+  b.wall_faces = 0;
+  for (int q = 0; q < n; ++q) {
+    if (s[q].bc_type != AGX_BC_VISCOUSWALL) continue;
+    WallSurfDev w;
+    const int lo[3] = {s[q].imin, s[q].jmin, s[q].kmin}, hi[3] = {s[q].imax, s[q].jmax, s[q].kmax};
+    const int nn[3] = {b.d.ni, b.d.nj, b.d.nk};
+    w.side = surface_type(s[q]);
+    const int d3 = (w.side - 1) / 2;
+    for (int d = 0; d < 3; ++d) {
+      w.lo[d] = lo[d];
+      w.n[d] = d == d3 ? 1 : hi[d] - lo[d];
+      // (the kernel indexes the planes from these: they must lie on the block)
+      if (lo[d] < 0 || hi[d] > nn[d] || w.n[d] < 1 || (d == d3 && lo[d] != 0 && lo[d] != nn[d]))
+        return fail("viscousWall surface %d does not lie on a side of block %d", q, id);
+    }
+    w.off = b.wall_faces;
+    b.wall_faces += (long)w.n[0] * w.n[1] * w.n[2];
+    b.wall_tab.push_back(w);
+  }
+  if (!b.wall_tab.empty()) {
+    HIPCHK(hipMalloc((void**)&b.wall_tab_dev, sizeof(WallSurfDev) * b.wall_tab.size()));
+    HIPCHK(hipMemcpy(b.wall_tab_dev, b.wall_tab.data(), sizeof(WallSurfDev) * b.wall_tab.size(),
+                     hipMemcpyHostToDevice));
   }
   return 0;
 }
@@ -2300,7 +2336,7 @@ static int ghosts_for_output(agx_ctx* c) {
     if (agx_phase_bc_edges(c)) return 1;
   }
   if (c->cfg.is_viscous) {
-    if (bc_pass(c, true, 1)) return 1;
+    if (bc_pass(c, true, 2)) return 1;     // (2: the stored wall-law data stay the last residual's)
     if (bc_pass(c, false, 1)) return 1;
   }
   c->ghosts_prefilled = false;   // (the next iteration starts from its own inviscid fill)
@@ -2367,12 +2403,56 @@ OutSpec out_spec(const agx_ctx* c, const Block& b) {
   sp.global_pos = b.global_pos;
   return sp;
 }
+// WriteWallFun's payload of one block (the ids are wall ids, nvar is in their range)
+int wall_pack(agx_ctx* c, int id, int nvar, const int32_t* vars, double* out) {
+  Block& b = c->blocks[id];
+  if (!c->cfg.is_viscous)
+    return fail("agx_output_pack: wall variables need a viscous context (an inviscid run keeps "
+                "no wallData_)");
+  if (b.wall_tab.empty())
+    return fail("agx_output_pack: block %d has no viscousWall surface", id);
+  if (!c->finalized) return fail("agx_setup_finalize has not been called");
+  if (b.d.wallv && !c->have_wall_data)
+    return fail("agx_output_pack: the wall-law surfaces hold no wall data before the first "
+                "residual");
+  OutSpec sp = out_spec(c, b);
+  sp.nvar = nvar;
+  for (int v = 0; v < nvar; ++v) sp.var[v] = vars[v];
+  const long total = b.wall_faces;
+  double* tmp = nullptr;
+  if (stage_buffer(c, (size_t)nvar * total, &tmp)) return 1;
+  if (ghosts_for_output(c)) return 1;
+  const int fourth = c->cfg.viscous_recon == AGX_VISC_RECON_CENTRAL_4TH ? 1 : 0;
+  hipLaunchKernelGGL(k_wall_pack, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, c->stream,
+                     b.d, c->gas, sp, b.wall_tab_dev, (int)b.wall_tab.size(), total, fourth, tmp);
+  HIPCHK(hipGetLastError());
+  HIPCHK(hipMemcpyAsync(out, tmp, sizeof(double) * nvar * total, hipMemcpyDeviceToHost,
+                        c->stream));
+  HIPCHK(hipStreamSynchronize(c->stream));
+  return 0;
+}
 }  // namespace
 
 int agx_output_pack(agx_ctx* c, int id, int nvar, const int32_t* vars, double* out) {
   if (flush_consn(c)) return 1;
   if (id < 0 || id >= (int)c->blocks.size()) return fail("bad block id %d", id);
   if (nvar < 1 || nvar > AGX_OUT_COUNT) return fail("agx_output_pack: nvar %d out of range", nvar);
+  // cell variables or wall variables (WriteWallFun), each range with its own bound on nvar
+  int n_wall = 0;
+  for (int v = 0; v < nvar; ++v) {
+    const bool cell = vars[v] >= 0 && vars[v] < AGX_OUT_COUNT;
+    const bool wall = vars[v] >= AGX_WALL_YPLUS && vars[v] < AGX_WALL_END;
+    if (!cell && !wall) return fail("unknown output variable %d", vars[v]);
+    n_wall += wall;
+  }
+  if (n_wall > 0) {
+    if (n_wall != nvar)
+      return fail("agx_output_pack: cell and wall variables in one call (a function file holds "
+                  "one kind)");
+    if (nvar > AGX_WALL_END - AGX_WALL_YPLUS)
+      return fail("agx_output_pack: nvar %d out of range", nvar);
+    return wall_pack(c, id, nvar, vars, out);
+  }
   Block& b = c->blocks[id];
   OutSpec sp = out_spec(c, b);
   sp.nvar = nvar;
@@ -2772,6 +2852,7 @@ int agx_phase_residual(agx_ctx* c, int mm, double cfl) {
       Timer t(c, G_BC);
       if (bc_pass(c, true, 1)) return 1;
       if (bc_pass(c, false, 1)) return 1;
+      c->have_wall_data = true;
     }
     Timer t(c, G_VISC);
     for (auto& blk : c->blocks)

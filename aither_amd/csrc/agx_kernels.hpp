@@ -1301,9 +1301,16 @@ __device__ __forceinline__ void visc_face_terms(const BlockDev& b, const GasDev&
     for (int c = 0; c < 4; ++c) grad[r][c] *= inv_vol;
   visc_face_state(b, g, d, qU, fourth, sf, muf);
 }
-// viscous flux * |A| through the lower d-face of cell index qU (cells qL|qU)
+// what the wall-surface output (k_wall_pack) keeps of a face besides its flux: TauNormal
+// (utility.cpp:426-437), the conductive heat flux k grad T . n (viscousFlux.cpp:170-178), the
+// face state and its laminar viscosity
+struct ViscWallOut { double tau[3], qn, sf[AGX_NEQ], muf; };
+// viscous flux * |A| through the lower d-face of cell index qU (cells qL|qU); WALL: also what
+// k_wall_pack keeps (an instantiation of its own: the residual kernels' is what it was)
+template <bool WALL = false>
 __device__ __forceinline__ void visc_face(const BlockDev& b, const GasDev& g,
-                                          int d, long qU, double* f, bool fourth = false) {
+                                          int d, long qU, double* f, bool fourth = false,
+                                          ViscWallOut* wo = nullptr) {
   double grad[3][4];          // [derivative direction][u, v, w, T]
   double sf[AGX_NEQ], muf;
   visc_face_terms(b, g, d, qU, fourth, grad, sf, muf);
@@ -1327,6 +1334,12 @@ __device__ __forceinline__ void visc_face(const BlockDev& b, const GasDev& g,
   f[2] = tau[1] * n[3];
   f[3] = tau[2] * n[3];
   f[4] = (dot3(tau, sf + 1) + kk * tg) * n[3];
+  if constexpr (WALL) {
+    for (int r = 0; r < 3; ++r) wo->tau[r] = tau[r];
+    wo->qn = kk * tg;
+    for (int e = 0; e < AGX_NEQ; ++e) wo->sf[e] = sf[e];
+    wo->muf = muf;
+  }
 }
 
 // Block-matrix solvers: thin-shear-layer part of the main diagonal of a cell (the
@@ -1583,10 +1596,45 @@ __device__ inline void rans_face_state(const GasDev& g, const WallVars* wl,
     sf[6] = fmax(sf[6], AGX_TURB_MIN);
   }
 }
+// eddy viscosity and blending functions at the lower d-face of cell qU from the face state,
+// the face gradients and the wall distance of the face (procBlock.cpp:1316-1365); shared by the
+// viscous residual and the wall-surface output (k_wall_pack)
+__device__ __forceinline__ void rans_face_eddy(const BlockDev& b, const GasDev& g, int d, long qU,
+                                               const double* sf, const double* G,
+                                               const double* kg, const double* wg, double muf,
+                                               double& mut, double& f1, double& f2) {
+  const long qL = qU - b.stride(d);
+  // wall distance at the face by the two-cell rule
+  const double wU = b.wid[d][qL], wD = b.wid[d][qU];
+  const double cD = wD / (wU + wD), cU = wU / (wU + wD);
+  double wdist = cD * b.wdist[qU] + cU * b.wdist[qL];
+  if (wdist < 0.0 && wdist > -1.0e-10) wdist = 0.0;
+  if (g.wilcox) kw_eddy_visc_blending(g, sf, G, mut, f1, f2);
+  else sst_eddy_visc_blending(g, sf, G, kg, wg, muf, wdist, mut, f1, f2);
+}
+// TauNormal and (k + kt) grad T . n of viscousFlux::CalcFlux / CalcWallFlux with the eddy
+// viscosity `mut` (not yet scaled)
+__device__ __forceinline__ void rans_tau_q(const GasDev& g, const double (*grad)[4],
+                                           const double* sf, double muf, double mut,
+                                           const double* n, double* tau, double& qn) {
+  const double mu = g.scaling * muf, mt = g.scaling * mut;
+  const double lambda = -(2.0 / 3.0) * (mu + mt);
+  const double trace = grad[0][0] + grad[1][1] + grad[2][2];
+  for (int r = 0; r < 3; ++r) {
+    const double mm = (grad[r][0] + grad[0][r]) * n[0] + (grad[r][1] + grad[1][r]) * n[1] +
+                      (grad[r][2] + grad[2][r]) * n[2];
+    tau[r] = lambda * trace * n[r] + (mu + mt) * mm;
+  }
+  const double tf = temperature(g, sf);
+  const double kk = conductivity(g, tf) * g.scaling;
+  const double kt = mt * cp_of(g, tf) / g.turb_prandtl;     // transport.hpp:136
+  const double tg = grad[0][3] * n[0] + grad[1][3] * n[1] + grad[2][3] * n[2];
+  qn = (kk + kt) * tg;
+}
 __device__ inline void rans_face(const BlockDev& b, const GasDev& g, int d, int fi, int fj,
                                  int fk, bool fourth, RansFace& o, double* sf, double& muf,
                                  double* n) {
-  const long qU = b.idx(fi, fj, fk), qL = qU - b.stride(d);
+  const long qU = b.idx(fi, fj, fk);
   double grad[3][4];
   visc_face_terms(b, g, d, qU, fourth, grad, sf, muf);
   turb_face_grads(b, d, qU, o.kg, o.wg);
@@ -1610,32 +1658,16 @@ __device__ inline void rans_face(const BlockDev& b, const GasDev& g, int d, int 
     f[5] = (wl->viscosity + wsk * wl->turb_eddy_visc) * dot3(o.kg, n);
     f[6] = (wl->viscosity + wsw * wl->turb_eddy_visc) * dot3(o.wg, n);
   } else {
-    // wall distance at the face by the two-cell rule
-    const double wU = b.wid[d][qL], wD = b.wid[d][qU];
-    const double cD = wD / (wU + wD), cU = wU / (wU + wD);
-    double wdist = cD * b.wdist[qU] + cU * b.wdist[qL];
-    if (wdist < 0.0 && wdist > -1.0e-10) wdist = 0.0;
-    if (g.wilcox) kw_eddy_visc_blending(g, sf, o.G, o.mut, o.f1, o.f2);
-    else sst_eddy_visc_blending(g, sf, o.G, o.kg, o.wg, muf, wdist, o.mut, o.f1, o.f2);
+    rans_face_eddy(b, g, d, qU, sf, o.G, o.kg, o.wg, muf, o.mut, o.f1, o.f2);
     // viscousFlux::CalcFlux
-    const double mu = g.scaling * muf, mt = g.scaling * o.mut;
-    const double lambda = -(2.0 / 3.0) * (mu + mt);
-    const double trace = grad[0][0] + grad[1][1] + grad[2][2];
-    double tau[3];
-    for (int r = 0; r < 3; ++r) {
-      const double mm = (grad[r][0] + grad[0][r]) * n[0] + (grad[r][1] + grad[1][r]) * n[1] +
-                        (grad[r][2] + grad[2][r]) * n[2];
-      tau[r] = lambda * trace * n[r] + (mu + mt) * mm;
-    }
-    const double tf = temperature(g, sf);
-    const double kk = conductivity(g, tf) * g.scaling;
-    const double kt = mt * cp_of(g, tf) / g.turb_prandtl;     // transport.hpp:136
-    const double tg = grad[0][3] * n[0] + grad[1][3] * n[1] + grad[2][3] * n[2];
+    const double mu = g.scaling * muf;
+    double tau[3], qn;
+    rans_tau_q(g, grad, sf, muf, o.mut, n, tau, qn);
     // UseUnlimitedEddyVisc (Wilcox): the k / omega diffusion takes rho k / omega
     const double mtt = g.scaling * turb_diff_visc(g, sf, o.mut);
     f[0] = 0.0;
     f[1] = tau[0]; f[2] = tau[1]; f[3] = tau[2];
-    f[4] = dot3(tau, sf + 1) + (kk + kt) * tg;
+    f[4] = dot3(tau, sf + 1) + qn;
     f[5] = (mu + turb_sigma_k(g, o.f1) * mtt) * dot3(o.kg, n);
     f[6] = (mu + turb_sigma_w(g, o.f1) * mtt) * dot3(o.wg, n);
   }
@@ -2031,7 +2063,7 @@ __host__ __device__ inline int surface_type(const agx_bc_surface& s) {
 }
 
 // Face ghost cells: procBlock::AssignInviscidGhostCells procBlock.cpp:2449-2532
-// (viscous = 0) / AssignViscousGhostCells :2760-2838 (viscous = 1, viscousWall
+// (viscous = 0) / AssignViscousGhostCells :2760-2838 (viscous = 1 or 2, viscousWall
 // surfaces only).  All layers and surfaces are independent (they read physical
 // cells only), so one launch covers every surface of the block: blockIdx.y is
 // the surface, blockIdx.x * blockDim.x + threadIdx.x the ghost cell on it.
@@ -2099,7 +2131,9 @@ k_bc_faces(BlockDev b, GasDev g, int viscous, int* err) {
     load5(b.state, qs, in);
     // wall functions: the wall data of the face belong to the first layer's call
     WallVars* wv = nullptr;
-    if (AGX_NEQ > 5 && viscous && layer == 1 && sf.state.is_wall_law && b.wall_off &&
+    // (viscous = 2, the ghost fill of an output step: the stored wall data stay the last
+    // residual's)
+    if (AGX_NEQ > 5 && viscous == 1 && layer == 1 && sf.state.is_wall_law && b.wall_off &&
         b.wall_off[sn] >= 0)
       wv = b.wallv + b.wall_off[sn] + (long)(a2 - lo2) * n1 + (a1 - lo1);
     if (!ghost_state(g, in, bc, area, st, sf.state, layer, wd, gh, is_nr ? &nr : nullptr, nu_w,
@@ -3510,6 +3544,100 @@ k_output_pack(BlockDev b, GasDev g, OutSpec sp, const double* __restrict__ grads
         }
     }
     out[(long)v * ncell + p] = val;
+  }
+}
+// WriteWallFun (output.cpp:472-571): the wall variables of the block's viscousWall surfaces,
+// one thread per wall face, all surfaces in one launch through a table (surface -> index
+// range, side, offset of its faces in the payload), variable by variable into
+// out[v * total + face] (a wave's stores of a variable are contiguous).  Low-Re faces: the
+// wallVars of viscousFlux::CalcWallFlux (viscousFlux.cpp:137-211) as CalcViscFluxI/J/K forms
+// them (procBlock.cpp:1303-1376) from the state and ghost cells the device holds now, with
+// the device functions of the viscous residual.  Wall-law faces (y+ >= 10): the wall data the
+// last residual's viscous ghost fill stored.  On i-walls consecutive faces are a row pitch
+// apart: surface-sized work, read as it lies.
+struct WallSurfDev {
+  int lo[3], n[3];     // first face / cell index and count per direction (1 across the wall)
+  int side;            // surface type 1..6
+  long off;            // first face of the surface in a variable's row
+};
+__global__ void __launch_bounds__(256)
+k_wall_pack(BlockDev b, GasDev g, OutSpec sp, const WallSurfDev* __restrict__ tab, int nsurf,
+            long total, int fourth, double* __restrict__ out) {
+  const long t = (long)blockIdx.x * blockDim.x + threadIdx.x;
+  if (t >= total) return;
+  int sn = 0;
+  while (sn + 1 < nsurf && t >= tab[sn + 1].off) ++sn;
+  const WallSurfDev ws = tab[sn];
+  const long r = t - ws.off;
+  const int fi = ws.lo[0] + (int)(r % ws.n[0]);
+  const int fj = ws.lo[1] + (int)((r / ws.n[0]) % ws.n[1]);
+  const int fk = ws.lo[2] + (int)(r / ((long)ws.n[0] * ws.n[1]));
+  const int d = (ws.side - 1) / 2;
+  const long qU = b.idx(fi, fj, fk), qL = qU - b.stride(d);
+  WallVars w;
+  const WallVars* stored = nullptr;
+#if AGX_NEQ == 7
+  const agx_bc_surface* bs;
+  stored = rans_wall_face(b, d, fi, fj, fk, bs);
+#endif
+  if (stored) {
+    w = *stored;
+  } else {
+    double sf[AGX_NEQ], muf, tau[3], qn, mut = 0.0;
+#if AGX_NEQ == 7
+    double grad[3][4], n[4], G[9], kg[3], wg[3], f1, f2;
+    visc_face_terms(b, g, d, qU, fourth != 0, grad, sf, muf);
+    load_area(b, d, qU, n);
+    turb_face_grads(b, d, qU, kg, wg);
+    for (int rr = 0; rr < 3; ++rr)
+      for (int cc = 0; cc < 3; ++cc) G[3 * rr + cc] = grad[rr][cc];
+    rans_face_state(g, nullptr, nullptr, sf, muf);
+    rans_face_eddy(b, g, d, qU, sf, G, kg, wg, muf, mut, f1, f2);
+    rans_tau_q(g, grad, sf, muf, mut, n, tau, qn);
+    w.tke = sf[5]; w.sdr = sf[6];
+#else
+    double flux[AGX_NEQ];
+    ViscWallOut wo;
+    visc_face<true>(b, g, d, qU, flux, fourth != 0, &wo);
+    for (int e = 0; e < AGX_NEQ; ++e) sf[e] = wo.sf[e];
+    for (int c = 0; c < 3; ++c) tau[c] = wo.tau[c];
+    muf = wo.muf; qn = wo.qn;
+    w.tke = 0.0; w.sdr = 0.0;
+#endif
+    // plain division / sqrt: an output path, the values go to a file
+    w.viscosity = g.scaling * muf;
+    w.turb_eddy_visc = g.scaling * mut;
+    for (int c = 0; c < 3; ++c) w.shear[c] = tau[c];
+    w.heat_flux = qn;
+    w.density = sf[0];
+    w.temperature = sf[4] / (sf[0] * g.R);
+    w.friction_velocity = sqrt(sqrt(dot3(tau, tau)) / w.density);
+    // y+ from the wall distance of the wall-adjacent cell, procBlock.cpp:1372-1375
+    const double y = ws.side % 2 == 1 ? b.wdist[qU] : b.wdist[qL];
+    w.yplus = y * w.friction_velocity * w.density / (w.viscosity + w.turb_eddy_visc);
+  }
+  // the factors of output.cpp:519-553
+  const double rR = sp.rho_ref, aR = sp.a_ref, lR = sp.l_ref, tR = sp.t_ref, muR = sp.mu_ref;
+  const double tau_sc = (1.0 / g.scaling) * muR * aR / lR;
+  for (int v = 0; v < sp.nvar; ++v) {
+    double val = 0.0;
+    switch (sp.var[v]) {
+      case AGX_WALL_YPLUS: val = w.yplus; break;
+      case AGX_WALL_SHEAR_STRESS: val = sqrt(dot3(w.shear, w.shear)) * tau_sc; break;
+      case AGX_WALL_VISCOSITY_RATIO: val = w.turb_eddy_visc / (w.viscosity + AGX_EPS); break;
+      case AGX_WALL_HEAT_FLUX: val = w.heat_flux * (muR * tR / lR); break;
+      case AGX_WALL_FRICTION_VELOCITY: val = w.friction_velocity * aR; break;
+      case AGX_WALL_DENSITY: val = w.density * rR; break;
+      case AGX_WALL_PRESSURE: val = w.density * g.R * w.temperature * (rR * aR * aR); break;
+      case AGX_WALL_TEMPERATURE: val = w.temperature * tR; break;
+      case AGX_WALL_VISCOSITY: val = w.viscosity * (muR * (1.0 / g.scaling)); break;
+      case AGX_WALL_TKE: val = w.tke * (aR * aR); break;
+      case AGX_WALL_SDR: val = w.sdr * (aR * aR * rR / muR); break;
+      case AGX_WALL_SHEAR_X: val = w.shear[0] * tau_sc; break;
+      case AGX_WALL_SHEAR_Y: val = w.shear[1] * tau_sc; break;
+      case AGX_WALL_SHEAR_Z: val = w.shear[2] * tau_sc; break;
+    }
+    out[(long)v * total + t] = val;
   }
 }
 // WriteRestart (output.cpp:651-752): n_eq + 1 dimensional values per cell, cell by cell;

@@ -220,6 +220,43 @@ class Solver:
                                             out.ctypes.data_as(abi.c_dp)), "output_pack")
         return out
 
+    def wall_surfaces(self, gb):
+        """The viscousWall surfaces of block gb in the order of the wall payload (the order
+        the library got them in, which is the order of the reference's wallData_): per surface
+        its side (surface type 1..6), its index range and the shape (nk, nj, ni) of its faces."""
+        out = []
+        for s in self.case.blocks[gb].surfaces:
+            if s.bc_type != "viscousWall":
+                continue
+            side = s.surface_type()
+            d = (side - 1) // 2
+            n = [s.imax - s.imin, s.jmax - s.jmin, s.kmax - s.kmin]
+            n[d] = 1
+            out.append(dict(side=side, tag=s.tag, range=(s.imin, s.imax, s.jmin, s.jmax,
+                                                         s.kmin, s.kmax),
+                            shape=(n[2], n[1], n[0])))
+        return out
+
+    def wall_pack(self, gb, names):
+        """WriteWallFun's variables of block gb (reference names, abi.WALL_OUT), packed by the
+        library: {name: [one array per wall surface, shaped (nk, nj, ni) of its range]},
+        dimensional.  A name given twice keeps its last row."""
+        surfs = self.wall_surfaces(gb)
+        total = sum(int(np.prod(s["shape"])) for s in surfs)
+        ids = (C.c_int32 * len(names))(*[abi.WALL_OUT[n] for n in names])
+        out = np.empty((len(names), total))
+        self.api.check(self.api.output_pack(self.ctx, self.block_ids[gb], len(names), ids,
+                                            out.ctypes.data_as(abi.c_dp)), "output_pack")
+        res = {}
+        for q, name in enumerate(names):
+            off, rows = 0, []
+            for s in surfs:
+                cnt = int(np.prod(s["shape"]))
+                rows.append(out[q, off:off + cnt].reshape(s["shape"]).copy())
+                off += cnt
+            res[name] = rows
+        return res
+
     def restart_pack(self, gb, which=0):
         """WriteRestart's payload of block gb: [nk, nj, ni, n_eq + 1], dimensional."""
         g = self.case.blocks[gb].geom

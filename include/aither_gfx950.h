@@ -121,6 +121,34 @@ enum { AGX_OUT_DENSITY = 0, AGX_OUT_VEL_X, AGX_OUT_VEL_Y, AGX_OUT_VEL_Z, AGX_OUT
        AGX_OUT_RESID = 47,        /* .. 53: mass, mom_x, mom_y, mom_z, energy, tke, sdr */
        AGX_OUT_COUNT = 54 };
 
+/* variables of the wall function file, WriteWallFun (output.cpp:472-571): the wallData_ of
+ * the block's viscousWall surfaces (wallVars, wallData.hpp:33-62), dimensional with the
+ * factors of output.cpp:519-553.  A range of its own in agx_output_pack: a call asks for cell
+ * variables (< AGX_OUT_COUNT) or for wall variables, never both.
+ *   yplus              wallVars::yplus_             procBlock.cpp:1372-1375   output.cpp:519
+ *   shearStress        |shearStress_|, TauNormal    utility.cpp:426-436       :521-524
+ *   viscosityRatio     turbEddyVisc_ / (viscosity_ + EPS)                     :525-527
+ *   heatFlux           (k + kt) grad T . n          viscousFlux.cpp:170-178   :528-530
+ *   frictionVelocity   sqrt(|tau| / rho)            viscousFlux.cpp:187       :531-533
+ *   density, pressure (PressureRT, wallData.cpp:140-144), temperature, viscosity,
+ *   tke, sdr           the face state of CalcWallFlux                         :534-553
+ * AGX_WALL_SHEAR_X/Y/Z are an extension: the components of shearStress_ with the factor of
+ * shearStress (the reference writes the magnitude only; integrated forces need the vector).
+ * As in the reference the vector is TauNormal on the face's area vector, which points in the
+ * direction of increasing index on both sides of a block.
+ * Timing.  Low-Re faces (every wall face of the 5-equation libraries; in the rans libraries the
+ * faces of low-Re surfaces and those faces of a wall-law surface whose stored y+ < 10,
+ * SwitchToLowRe): evaluated from the state the device holds when the call is made, with the
+ * ghost cells the next residual would see, like the gradients above (the reference writes
+ * what its last residual stored, procBlock.cpp:1367-1376, i.e. of the state before the last
+ * update).  Wall-law faces: the wall data the last residual's viscous ghost fill stored, as
+ * they are (like eddy viscosity, f1 and f2 of the cell variables). */
+enum { AGX_WALL_YPLUS = 64, AGX_WALL_SHEAR_STRESS, AGX_WALL_VISCOSITY_RATIO, AGX_WALL_HEAT_FLUX,
+       AGX_WALL_FRICTION_VELOCITY, AGX_WALL_DENSITY, AGX_WALL_PRESSURE, AGX_WALL_TEMPERATURE,
+       AGX_WALL_VISCOSITY, AGX_WALL_TKE, AGX_WALL_SDR,        /* the reference's eleven */
+       AGX_WALL_SHEAR_X, AGX_WALL_SHEAR_Y, AGX_WALL_SHEAR_Z,  /* not in the reference's list */
+       AGX_WALL_END };
+
 /* what a halo exchange carries (gridLevel.cpp:299-313, utility.cpp:400-423) */
 enum { AGX_HALO_STATE = 0, AGX_HALO_UPDATE = 1,
        /* velocityGrad_ of the cells across connection surfaces, swapped after the
@@ -346,7 +374,16 @@ int agx_phase_implicit_update(agx_ctx *ctx, int mm, double *l2, agx_linf *linf);
  * fastest, variable by variable: out[v * ni*nj*nk + cell], dimensional as the reference
  * writes them (reference quantities from agx_config.gas).  Variables a build does not hold
  * (tke, sdr, eddy viscosity, f1, f2 and their gradients in the 5-equation library) come
- * out as the reference's laminar values (0), viscosity in inviscid runs is refused. */
+ * out as the reference's laminar values (0), viscosity in inviscid runs is refused.
+ * WriteWallFun (output.cpp:472-571): with wall variables (AGX_WALL_*) the payload of the wall
+ * file of one block instead -- variable by variable in the caller's order; within a variable
+ * the block's viscousWall surfaces in the order agx_block_set_bcs got them (the order of
+ * wallData_, procBlock.cpp:76-85); within a surface its faces, i fastest, then j, then k over
+ * the surface's index range (the loop nest of output.cpp:505-516):
+ * out[v * nfaces + offset(surface) + face].  The caller sizes `out` from its own surfaces.
+ * Refused: cell and wall variables in one call, an id in neither range, a block without a
+ * viscousWall surface, an inviscid context, wall-law surfaces before the first residual, nvar
+ * beyond the number of ids of its range (repeated ids are allowed in both). */
 int agx_output_pack(agx_ctx *ctx, int block, int nvar, const int32_t *vars, double *out);
 /* WriteRestart (output.cpp:651-752), the payload of one block: cell by cell (i fastest)
  * n_eq + 1 dimensional values -- density, velocity, pressure, [tke, sdr,] mass fraction of

@@ -156,6 +156,14 @@ class hotPath {
     Check(AGX_SYM(output_pack)(ctx_, block, static_cast<int>(vars.size()), vars.data(), out),
           "hotPath::OutputPack");
   }
+  // WriteWallFun (output.cpp:472-571): the block's payload of the wall function file -- the
+  // listed variables (AGX_WALL_*), variable by variable, within each the block's viscousWall
+  // surfaces in the order SetBCs got them, within a surface its faces i fastest, then j, then
+  // k; `out` holds vars.size() * (faces of all its wall surfaces) values
+  void WallPack(int block, const std::vector<int32_t> &vars, double *out) const {
+    Check(AGX_SYM(output_pack)(ctx_, block, static_cast<int>(vars.size()), vars.data(), out),
+          "hotPath::WallPack");
+  }
   // WriteRestart (output.cpp:651-752): the block's payload, numEqns + 1 values per cell;
   // secondSolution: consVarsNm1 (multilevel time integration)
   void RestartPack(int block, bool secondSolution, double *out) const {
