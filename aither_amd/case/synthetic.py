@@ -26,7 +26,11 @@ def box_nodes(ni, nj, nk, stretch=1.0, lengths=(1.0, 1.0, 1.0),
 
 def perturbed_state(case, amplitude=0.05):
     """q * (1 + a sin(2 pi x) sin(2 pi y) sin(2 pi z)) on the cell centres of
-    every block (physical and ghost cells; ghosts are overwritten by BCs)."""
+    every block (physical and ghost cells; ghosts are overwritten by BCs).
+
+    A Mach-0.16 stream with three positive velocity components: it selects one side of every
+    flow-dependent branch (supersonic flux splits, reversed flow, limiter clips, boundary
+    arms).  tests/flow_fields.py has the transonic, sign-changing counterpart."""
     two_pi = 2.0 * math.pi
     for blk in case.blocks:
         c = blk.geom.center.a
