@@ -51,6 +51,9 @@ WALL_OUT = {"yplus": 64, "shearStress": 65, "viscosityRatio": 66, "heatFlux": 67
             "frictionVelocity": 68, "density": 69, "pressure": 70, "temperature": 71,
             "viscosity": 72, "tke": 73, "sdr": 74,
             "shearStress_x": 75, "shearStress_y": 76, "shearStress_z": 77}
+# variables of the nodal function file (AGX_NODE_BASE + AGX_OUT_*): the names of OUT
+NODE_BASE = 128
+NODE_OUT = {_n: NODE_BASE + _v for _n, _v in OUT.items()}
 
 c_dp = C.POINTER(C.c_double)
 

@@ -2431,19 +2431,75 @@ int wall_pack(agx_ctx* c, int id, int nvar, const int32_t* vars, double* out) {
   HIPCHK(hipStreamSynchronize(c->stream));
   return 0;
 }
+// WriteNodeFun's payload of one block (vars: cell ids, AGX_NODE_BASE taken off)
+int node_pack(agx_ctx* c, int id, int nvar, const int32_t* vars, double* out) {
+  Block& b = c->blocks[id];
+  if (!c->finalized) return fail("agx_setup_finalize has not been called");
+  OutSpec sp = out_spec(c, b);
+  sp.nvar = nvar;
+  bool need_grads = false;
+  for (int v = 0; v < nvar; ++v) {
+    const int var = vars[v];
+    if (var == AGX_OUT_VISCOSITY && !c->sp.viscous)
+      return fail("viscosity_ is only kept for viscous runs (procBlock.cpp:6171)");
+#if AGX_NEQ == 7
+    if (var == AGX_OUT_VISCOSITY_RATIO || var == AGX_OUT_TURB_VISCOSITY || var == AGX_OUT_F1 ||
+        var == AGX_OUT_F2)
+      return fail("agx_output_pack: node variable %d (viscosityRatio, turbulentViscosity, f1, f2) "
+                  "is not formed at nodes: the reference averages eddyViscosity_, f1_, f2_ with "
+                  "their ghost cells, which hold what the residual's accumulation at boundary "
+                  "faces and the corner initial values left; the library keeps them in physical "
+                  "cells and connection ghost cells only", AGX_NODE_BASE + var);
+#endif
+    sp.var[v] = var;
+    need_grads = need_grads || (var >= AGX_OUT_VELGRAD && var < AGX_OUT_RESID);
+  }
+  const long nnode = (long)(b.d.ni + 1) * (b.d.nj + 1) * (b.d.nk + 1);
+  double* tmp = nullptr;
+  const size_t gdoubles = need_grads ? (size_t)3 * NGF * nnode : 0;
+  if (stage_buffer(c, gdoubles + (size_t)nvar * nnode, &tmp)) return 1;
+  // every nodal variable reads ghost cells: those the next residual would see
+  if (ghosts_for_output(c)) return 1;
+  const dim3 grid((b.d.ni + CELL_BLOCK.x) / CELL_BLOCK.x, (b.d.nj + CELL_BLOCK.y) / CELL_BLOCK.y,
+                  b.d.nk + 1);
+  if (need_grads)
+    hipLaunchKernelGGL(k_node_grads, grid, CELL_BLOCK, 0, c->stream, b.d, c->gas, tmp);
+  double* packed = tmp + gdoubles;
+  hipLaunchKernelGGL(k_node_pack, grid, CELL_BLOCK, 0, c->stream, b.d, c->gas, sp,
+                     need_grads ? tmp : nullptr, packed);
+  HIPCHK(hipGetLastError());
+  HIPCHK(hipMemcpyAsync(out, packed, sizeof(double) * nvar * nnode, hipMemcpyDeviceToHost,
+                        c->stream));
+  HIPCHK(hipStreamSynchronize(c->stream));
+  return 0;
+}
 }  // namespace
 
 int agx_output_pack(agx_ctx* c, int id, int nvar, const int32_t* vars, double* out) {
   if (flush_consn(c)) return 1;
   if (id < 0 || id >= (int)c->blocks.size()) return fail("bad block id %d", id);
   if (nvar < 1 || nvar > AGX_OUT_COUNT) return fail("agx_output_pack: nvar %d out of range", nvar);
-  // cell variables or wall variables (WriteWallFun), each range with its own bound on nvar
-  int n_wall = 0;
+  // cell variables, wall variables (WriteWallFun) or node variables (WriteNodeFun), each range
+  // with its own bound on nvar
+  int n_wall = 0, n_node = 0;
   for (int v = 0; v < nvar; ++v) {
     const bool cell = vars[v] >= 0 && vars[v] < AGX_OUT_COUNT;
     const bool wall = vars[v] >= AGX_WALL_YPLUS && vars[v] < AGX_WALL_END;
-    if (!cell && !wall) return fail("unknown output variable %d", vars[v]);
+    const bool node = vars[v] >= AGX_NODE_BASE && vars[v] < AGX_NODE_END;
+    if (!cell && !wall && !node) return fail("unknown output variable %d", vars[v]);
     n_wall += wall;
+    n_node += node;
+  }
+  if (n_node > 0) {
+    if (n_wall > 0)
+      return fail("agx_output_pack: node and wall variables in one call (a function file holds "
+                  "one kind)");
+    if (n_node != nvar)
+      return fail("agx_output_pack: cell and node variables in one call (a function file holds "
+                  "one kind)");
+    int32_t ids[AGX_OUT_COUNT];
+    for (int v = 0; v < nvar; ++v) ids[v] = vars[v] - AGX_NODE_BASE;
+    return node_pack(c, id, nvar, ids, out);
   }
   if (n_wall > 0) {
     if (n_wall != nvar)

@@ -3640,6 +3640,186 @@ k_wall_pack(BlockDev b, GasDev g, OutSpec sp, const WallSurfDev* __restrict__ ta
     out[(long)v * total + t] = val;
   }
 }
+// ---------------------------------------------------------------------------
+// WriteNodeFun (output.cpp:452-469): the nodal function file, procBlock::CellToNode
+// (procBlock.cpp:6607-6845) with ConvertCellToNode (utility.hpp:186-334), one thread per node
+// (i, j, k), 0 <= i <= ni ..., whose eight cells are (i-1..i, j-1..j, k-1..k).  Gathers where the
+// reference scatters: a node adds what reaches it in the order the reference's loops reach it
+// (k, j, i ascending), so there is no atomic and the payload is the same on every call.
+//
+// The state of a cell of the first ghost layer or of the block.  The eight corner ghost cells
+// are never stored: AssignCornerGhostCells (procBlock.cpp:2716-2753) on the fly, a third of the
+// three edge ghost cells towards the block, in the reference's order (i, j, k neighbour).
+__device__ __forceinline__ void node_cell_state(const BlockDev& b, int ci, int cj, int ck,
+                                                double* s) {
+  const bool gi = ci < 0 || ci >= b.ni, gj = cj < 0 || cj >= b.nj, gk = ck < 0 || ck >= b.nk;
+  if (gi && gj && gk) {
+    const long qa = b.idx(ci < 0 ? ci + 1 : ci - 1, cj, ck);
+    const long qb = b.idx(ci, cj < 0 ? cj + 1 : cj - 1, ck);
+    const long qc = b.idx(ci, cj, ck < 0 ? ck + 1 : ck - 1);
+#pragma unroll
+    for (int e = 0; e < AGX_NEQ; ++e)
+      s[e] = (1.0 / 3.0) * (b.state[e][qa] + b.state[e][qb] + b.state[e][qc]);
+  } else {
+    load5(b.state, b.idx(ci, cj, ck), s);
+  }
+}
+// The nodal gradients (procBlock.cpp:6622-6780): the Green-Gauss gradient of every physical
+// face (CalcGradsI/J/K, boundary faces included) goes to the four nodes of the face -- here a
+// node collects its up to twelve faces, i-faces, then j-faces, then k-faces, each direction in
+// the order k, j, i -- times 1/3 at the block's corners, 1/5 on its edges, 1/8 on its boundary
+// faces, 1/12 inside (:6782-6785).  out: [node][3 NGF] in the layout of cell_grads18.  The
+// face loops are kept rolled: one copy of face_grad6, an output path.
+__global__ void __launch_bounds__(256) k_node_grads(BlockDev b, GasDev g, double* out) {
+  const int i = blockIdx.x * blockDim.x + threadIdx.x;
+  const int j = blockIdx.y * blockDim.y + threadIdx.y;
+  const int k = blockIdx.z;
+  if (i > b.ni || j > b.nj) return;
+  double acc[3 * NGF];
+  for (int m = 0; m < 3 * NGF; ++m) acc[m] = 0.0;
+#pragma unroll 1
+  for (int d = 0; d < 3; ++d) {
+#pragma unroll 1
+    for (int m = 0; m < 4; ++m) {
+      // the face's index across d is the node's; along the two others (the lower one runs
+      // fastest) it is the node's or one less
+      const int o1 = (m & 1) - 1, o2 = (m >> 1) - 1;
+      const int ci = d == 0 ? i : i + o1;
+      const int cj = d == 0 ? j + o1 : d == 1 ? j : j + o2;
+      const int ck = d == 2 ? k : k + o2;
+      if ((d != 0 && (ci < 0 || ci >= b.ni)) || (d != 1 && (cj < 0 || cj >= b.nj)) ||
+          (d != 2 && (ck < 0 || ck >= b.nk)))
+        continue;
+      double g6[3][NGF];
+      face_grad6(b, g, d, b.idx(ci, cj, ck), g6);
+      for (int r = 0; r < 3; ++r) {
+        for (int f = 0; f < 3; ++f) acc[3 * r + f] += g6[r][f];
+        for (int f = 3; f < NGF; ++f) acc[9 + 3 * (f - 3) + r] += g6[r][f];
+      }
+    }
+  }
+  const int nb = (i == 0 || i == b.ni) + (j == 0 || j == b.nj) + (k == 0 || k == b.nk);
+  const double fac = nb == 3 ? 1.0 / 3.0 : nb == 2 ? 1.0 / 5.0 : nb == 1 ? 1.0 / 8.0 : 1.0 / 12.0;
+  double* o = out + 3 * NGF * (((long)k * (b.nj + 1) + j) * (b.ni + 1) + i);
+  for (int m = 0; m < 3 * NGF; ++m) o[m] = acc[m] * fac;
+}
+// The variables of the nodal file, variable by variable into out[v * nnode + node] (a wave's
+// stores of a variable are a contiguous row); sp.var holds cell ids (AGX_NODE_BASE taken off).
+//   node state        1/8 of the eight cells of the ghost-inclusive state (ConvertCellToNode
+//                     without ignoreEdge); density .. sdr, mach, sos, energy, enthalpy are
+//                     k_output_pack's functions of it
+//   temperature, viscosity   1/8 of the eight cells' temperature_ / viscosity_ (the corner
+//                     ghost cells evaluated from their corner-rule state); cp, cv of that
+//                     temperature
+//   dt, resid_*       no ghost cells: the physical cells, times 1 at the block's corners, 1/2
+//                     on its edges, 1/8 elsewhere (k_mg_nodes)
+//   wallDistance      physical and face ghost cells, times 1/4, 1/6, 1/8
+//   gradients         k_node_grads' output
+__global__ void __launch_bounds__(256)
+k_node_pack(BlockDev b, GasDev g, OutSpec sp, const double* __restrict__ grads,
+            double* __restrict__ out) {
+  const int i = blockIdx.x * blockDim.x + threadIdx.x;
+  const int j = blockIdx.y * blockDim.y + threadIdx.y;
+  const int k = blockIdx.z;
+  if (i > b.ni || j > b.nj) return;
+  const long nnode = (long)(b.ni + 1) * (b.nj + 1) * (b.nk + 1);
+  const long p = ((long)k * (b.nj + 1) + j) * (b.ni + 1) + i;
+  const double rR = sp.rho_ref, aR = sp.a_ref, lR = sp.l_ref, tR = sp.t_ref, muR = sp.mu_ref;
+  double s[AGX_NEQ], tsum = 0.0, musum = 0.0;
+#pragma unroll
+  for (int e = 0; e < AGX_NEQ; ++e) s[e] = 0.0;
+  for (int dk = -1; dk <= 0; ++dk)
+    for (int dj = -1; dj <= 0; ++dj)
+      for (int di = -1; di <= 0; ++di) {
+        double c[AGX_NEQ];
+        node_cell_state(b, i + di, j + dj, k + dk, c);
+#pragma unroll
+        for (int e = 0; e < AGX_NEQ; ++e) s[e] += c[e];
+        // plain division / sqrt: an output path, the values go to a file
+        const double tc = c[4] / (c[0] * g.R), temp = tc * g.t_ref;
+        tsum += tc;
+        musum += (g.visc_c1 * temp * sqrt(temp)) / ((temp + g.visc_s) * g.mu_ref);
+      }
+#pragma unroll
+  for (int e = 0; e < AGX_NEQ; ++e) s[e] *= 0.125;
+  const double tavg = tsum * 0.125, muavg = musum * 0.125;
+  const double v2 = dot3(s + 1, s + 1);
+#if AGX_TPG
+  const double t = s[4] / (s[0] * g.R);      // of the node state: primitive::SoS / Energy
+  const double cvs = cv_of(g, t);
+  const double cs = sqrt((cvs + g.R) / cvs * s[4] / s[0]);
+  const double en = spec_energy(g, t) + 0.5 * v2;
+  const double cv = cv_of(g, tavg), cp = cv + g.R;
+#else
+  const double cp = g.cp, cv = g.cv;
+  const double cs = sqrt(g.gamma * s[4] / s[0]);
+  const double en = g.hf + g.n * s[4] / s[0] + 0.5 * v2;
+#endif
+  const bool xi = i == 0 || i == b.ni, xj = j == 0 || j == b.nj, xk = k == 0 || k == b.nk;
+  const int nb = xi + xj + xk;
+  // a plane without ghost cells (ghosts = false) or with its face ghost cells
+  auto gather = [&](const double* pl, bool ghosts) {
+    double a = 0.0;
+    for (int dk = -1; dk <= 0; ++dk)
+      for (int dj = -1; dj <= 0; ++dj)
+        for (int di = -1; di <= 0; ++di) {
+          const int ci = i + di, cj = j + dj, ck = k + dk;
+          const int ng = (ci < 0 || ci >= b.ni) + (cj < 0 || cj >= b.nj) + (ck < 0 || ck >= b.nk);
+          if (ng > (ghosts ? 1 : 0)) continue;
+          a += pl[b.idx(ci, cj, ck)];
+        }
+    return a * (nb == 3 ? (ghosts ? 0.25 : 1.0) : nb == 2 ? (ghosts ? 1.0 / 6.0 : 0.5) : 0.125);
+  };
+  for (int v = 0; v < sp.nvar; ++v) {
+    const int var = sp.var[v];
+    double val = 0.0;
+    switch (var) {
+      case AGX_OUT_DENSITY: val = s[0] * rR; break;
+      case AGX_OUT_VEL_X: val = s[1] * aR; break;
+      case AGX_OUT_VEL_Y: val = s[2] * aR; break;
+      case AGX_OUT_VEL_Z: val = s[3] * aR; break;
+      case AGX_OUT_PRESSURE: val = s[4] * rR * aR * aR; break;
+      case AGX_OUT_MACH: val = sqrt(v2) / cs; break;
+      case AGX_OUT_SOS: val = cs * aR; break;
+      case AGX_OUT_DT: val = gather(b.dt, false) / (aR * lR); break;
+      case AGX_OUT_TEMPERATURE: val = tavg * tR; break;
+      case AGX_OUT_ENERGY: val = en * aR * aR; break;
+      case AGX_OUT_ENTHALPY: val = (en + s[4] / s[0]) * aR * aR; break;
+      case AGX_OUT_CP: val = cp * aR * aR / tR; break;
+      case AGX_OUT_CV: val = cv * aR * aR / tR; break;
+      case AGX_OUT_RANK: val = (double)sp.rank; break;
+      case AGX_OUT_GLOBAL_POSITION: val = (double)sp.global_pos; break;
+      case AGX_OUT_VISCOSITY: val = muavg * muR; break;
+      case AGX_OUT_WALL_DISTANCE: val = gather(b.wdist, true) * lR; break;
+#if AGX_NEQ == 7
+      case AGX_OUT_TKE: val = s[5] * aR * aR; break;
+      case AGX_OUT_SDR: val = s[6] * aR * aR * rR / muR; break;
+#endif
+      default:
+        if (var >= AGX_OUT_RESID) {
+          const int e = var - AGX_OUT_RESID;
+          if (e < AGX_NEQ) {
+            const double l2 = lR * lR;
+            const double sc = e == 0 ? rR * aR * l2
+                              : e < 4 ? rR * aR * aR * l2
+                              : e < 6 ? rR * aR * aR * aR * l2
+                                      : rR * rR * aR * aR * aR * aR * l2 / muR;
+            val = gather(b.resid[e], false) * sc;
+          }
+        } else if (var >= AGX_OUT_VELGRAD) {
+          const int gidx = var - AGX_OUT_VELGRAD;
+          const double sc = gidx < 9 ? aR / lR
+                            : gidx < 12 ? tR / lR
+                            : gidx < 15 ? rR / lR
+                            : gidx < 18 ? rR * aR * aR / lR
+                            : gidx < 21 ? aR * aR / lR
+                                        : aR * aR * rR / (muR * lR);
+          val = gidx < 3 * NGF ? grads[3 * NGF * p + gidx] * sc : 0.0;
+        }
+    }
+    out[(long)v * nnode + p] = val;
+  }
+}
 // WriteRestart (output.cpp:651-752): n_eq + 1 dimensional values per cell, cell by cell;
 // which = 0: the state, 1: consVarsNm1.  The payload is cell-major, so a wave's stores of
 // one variable are (n_eq + 1) * 8 bytes apart -- the restart interval is thousands of

@@ -220,6 +220,18 @@ class Solver:
                                             out.ctypes.data_as(abi.c_dp)), "output_pack")
         return out
 
+    def node_pack(self, gb, names):
+        """WriteNodeFun's variables of block gb (reference names, abi.NODE_OUT), converted to
+        the block's nodes and packed by the library: [nvar, nk + 1, nj + 1, ni + 1],
+        dimensional."""
+        g = self.case.blocks[gb].geom
+        ni, nj, nk = g.n
+        ids = (C.c_int32 * len(names))(*[abi.NODE_OUT[n] for n in names])
+        out = np.empty((len(names), nk + 1, nj + 1, ni + 1))
+        self.api.check(self.api.output_pack(self.ctx, self.block_ids[gb], len(names), ids,
+                                            out.ctypes.data_as(abi.c_dp)), "output_pack")
+        return out
+
     def wall_surfaces(self, gb):
         """The viscousWall surfaces of block gb in the order of the wall payload (the order
         the library got them in, which is the order of the reference's wallData_): per surface

@@ -149,6 +149,52 @@ enum { AGX_WALL_YPLUS = 64, AGX_WALL_SHEAR_STRESS, AGX_WALL_VISCOSITY_RATIO, AGX
        AGX_WALL_SHEAR_X, AGX_WALL_SHEAR_Y, AGX_WALL_SHEAR_Z,  /* not in the reference's list */
        AGX_WALL_END };
 
+/* variables of the nodal function file, WriteNodeFun (output.cpp:452-469): the cell data
+ * converted to the (ni+1)(nj+1)(nk+1) nodes of the block by procBlock::AssignCornerGhostCells
+ * (procBlock.cpp:2716-2753), procBlock::CellToNode (:6607-6845) and ConvertCellToNode
+ * (utility.hpp:186-334), dimensional with the factors of output.cpp:235-410.  A third range of
+ * agx_output_pack: node variable AGX_NODE_BASE + v exists for every cell id v < AGX_OUT_COUNT,
+ * and a call holds cell ids, wall ids or node ids, never a mixture.  Node (i, j, k),
+ * 0 <= i <= ni ..., lies between the cells (i-1..i, j-1..j, k-1..k); sums run over them in the
+ * order k, j, i ascending.
+ *   density, vel_*, pressure, tke, sdr   the node state: 1/8 of the eight cells of the state
+ *       with its first ghost layer.  Face and edge ghost cells as the device holds them; the
+ *       eight corner ghost cells by the rule of AssignCornerGhostCells (a third of the three
+ *       edge ghost cells towards the block), formed on the fly and never stored.
+ *   mach, sos, energy, enthalpy   functions of the node state (thermally perfect builds: with
+ *       T = p / (rho R) of the node state, primitive::SoS / Energy).
+ *   temperature, viscosity   1/8 of the eight cells' temperature_ = p / (rho R) and Sutherland
+ *       viscosity_ of it (the reference averages the arrays; it does not evaluate them at the
+ *       node state); cp, cv at that node temperature.
+ *       Departure: UpdateAuxillaryVariables (procBlock.cpp:6176) skips the eight corner ghost
+ *       cells, so the reference's temperature_ / viscosity_ there are whatever the initial
+ *       condition or a restart left -- they depend on history.  Here those eight cells are
+ *       evaluated from their corner-rule state.  Only the eight corner nodes of a block differ.
+ *   dt, resid_*   arrays without ghost cells (ConvertCellToNode, ignoreEdge, no-ghost path):
+ *       the physical cells around the node, times 1 at the block's eight corners, 1/2 on its
+ *       edges, 1/8 everywhere else -- boundary-face nodes, where four cells contribute,
+ *       included (the reference's factor, reproduced).
+ *   wallDistance   ignoreEdge with ghost cells: physical cells and first-layer face ghost
+ *       cells (edge and corner ghost cells skipped), times 1/4, 1/6, 1/8.
+ *   velGrad_*, tempGrad_*, densityGrad_*, pressGrad_*, tkeGrad_*, omegaGrad_*   the Green-Gauss
+ *       gradient of every physical face (CalcGradsI/J/K, boundary faces included) added to the
+ *       four nodes of the face -- i-faces, j-faces, k-faces, each in the order k, j, i -- times
+ *       1/3 at corners, 1/5 on edges, 1/8 on boundary faces, 1/12 inside (:6782-6785).
+ *   rank, globalPosition   the block's constants.
+ * Refused by name: viscosityRatio, turbulentViscosity, f1, f2 in the rans libraries.  The
+ * reference averages eddyViscosity_, f1_, f2_ including their ghost cells, whose content is
+ * what the residual's accumulation at boundary faces and the corner initial values left; the
+ * library keeps these in physical cells and connection ghost cells only and substitutes
+ * nothing.  (The 5-equation libraries write the laminar 0, as for cells.)  viscosity in an
+ * inviscid context is refused as for cells.
+ * Timing: every nodal call first fills the ghost cells the next residual would see, like the
+ * cell gradients above, so the values are those of the state the device holds when the call
+ * is made; ghost cells of connections to other ranks stay as last exchanged.  dt and the
+ * residuals are the last residual's.  No atomics: two calls give the same bits.  A library
+ * block is one procBlock: on a split plane the values are the above with connection ghost
+ * cells (the reference converts the recombined block). */
+enum { AGX_NODE_BASE = 128, AGX_NODE_END = AGX_NODE_BASE + AGX_OUT_COUNT };
+
 /* what a halo exchange carries (gridLevel.cpp:299-313, utility.cpp:400-423) */
 enum { AGX_HALO_STATE = 0, AGX_HALO_UPDATE = 1,
        /* velocityGrad_ of the cells across connection surfaces, swapped after the
@@ -381,9 +427,14 @@ int agx_phase_implicit_update(agx_ctx *ctx, int mm, double *l2, agx_linf *linf);
  * wallData_, procBlock.cpp:76-85); within a surface its faces, i fastest, then j, then k over
  * the surface's index range (the loop nest of output.cpp:505-516):
  * out[v * nfaces + offset(surface) + face].  The caller sizes `out` from its own surfaces.
- * Refused: cell and wall variables in one call, an id in neither range, a block without a
- * viscousWall surface, an inviscid context, wall-law surfaces before the first residual, nvar
- * beyond the number of ids of its range (repeated ids are allowed in both). */
+ * WriteNodeFun (output.cpp:452-469): with node variables (AGX_NODE_BASE + AGX_OUT_*) the
+ * payload of the nodal function file of one block instead -- variable by variable in the
+ * caller's order, within a variable the (nk+1)(nj+1)(ni+1) nodes, i fastest (the loop nest of
+ * output.cpp:231-233 over the node block): out[v * nnodes + node].
+ * Refused: variables of two ranges in one call, an id in no range, a block without a
+ * viscousWall surface, an inviscid context, wall-law surfaces before the first residual (the
+ * three: wall variables), the four node variables named above, nvar beyond the number of ids
+ * of its range (repeated ids are allowed in all three). */
 int agx_output_pack(agx_ctx *ctx, int block, int nvar, const int32_t *vars, double *out);
 /* WriteRestart (output.cpp:651-752), the payload of one block: cell by cell (i fastest)
  * n_eq + 1 dimensional values -- density, velocity, pressure, [tke, sdr,] mass fraction of

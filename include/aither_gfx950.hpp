@@ -164,6 +164,17 @@ class hotPath {
     Check(AGX_SYM(output_pack)(ctx_, block, static_cast<int>(vars.size()), vars.data(), out),
           "hotPath::WallPack");
   }
+  // WriteNodeFun (output.cpp:452-469): the block's payload of the nodal function file -- the
+  // listed variables by their cell ids (AGX_OUT_*; AGX_NODE_BASE is added here), converted to
+  // the (nk+1)(nj+1)(ni+1) nodes on the device (procBlock::CellToNode), variable by variable,
+  // i fastest, dimensional; `out` holds vars.size() * nodes values.  viscosityRatio,
+  // turbulentViscosity, f1, f2 are refused in the rans libraries (see the header)
+  void OutputPackNodes(int block, const std::vector<int32_t> &vars, double *out) const {
+    std::vector<int32_t> ids(vars);
+    for (auto &v : ids) v += AGX_NODE_BASE;
+    Check(AGX_SYM(output_pack)(ctx_, block, static_cast<int>(ids.size()), ids.data(), out),
+          "hotPath::OutputPackNodes");
+  }
   // WriteRestart (output.cpp:651-752): the block's payload, numEqns + 1 values per cell;
   // secondSolution: consVarsNm1 (multilevel time integration)
   void RestartPack(int block, bool secondSolution, double *out) const {
