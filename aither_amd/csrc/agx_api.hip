@@ -335,6 +335,14 @@ static int stage_buffer(agx_ctx* c, size_t doubles, double** out) {
   *out = c->stage_buf;
   return 0;
 }
+// the tail of a call that hands a payload out: the launches' error, n doubles to the host,
+// synchronise
+static int copy_out(agx_ctx* c, double* out, const double* dev, size_t n) {
+  HIPCHK(hipGetLastError());
+  HIPCHK(hipMemcpyAsync(out, dev, sizeof(double) * n, hipMemcpyDeviceToHost, c->stream));
+  HIPCHK(hipStreamSynchronize(c->stream));
+  return 0;
+}
 int upload_aos(agx_ctx* c, Block& b, const double* host, double* const* dst,
                int ncomp, int ci, int cj, int ck, int gsrc) {
   const long n = (long)ci * cj * ck;
@@ -2393,9 +2401,11 @@ int agx_field_download(agx_ctx* c, int id, int field, double* out) {
 }
 // ---- output: WriteFunFile / WriteRestart payloads packed on the device ------
 namespace {
-OutSpec out_spec(const agx_ctx* c, const Block& b) {
+OutSpec out_spec(const agx_ctx* c, const Block& b, int nvar = 0, const int32_t* vars = nullptr) {
   OutSpec sp;
   memset(&sp, 0, sizeof sp);
+  sp.nvar = nvar;
+  for (int v = 0; v < nvar; ++v) sp.var[v] = vars[v];
   const agx_gas& a = c->cfg.gas;
   sp.rho_ref = a.rho_ref; sp.a_ref = a.a_ref; sp.l_ref = a.l_ref; sp.t_ref = a.t_ref;
   sp.mu_ref = c->gas.mu_ref;                  // transport::MuRef, transport.cpp:58-66
@@ -2415,63 +2425,54 @@ int wall_pack(agx_ctx* c, int id, int nvar, const int32_t* vars, double* out) {
   if (b.d.wallv && !c->have_wall_data)
     return fail("agx_output_pack: the wall-law surfaces hold no wall data before the first "
                 "residual");
-  OutSpec sp = out_spec(c, b);
-  sp.nvar = nvar;
-  for (int v = 0; v < nvar; ++v) sp.var[v] = vars[v];
   const long total = b.wall_faces;
   double* tmp = nullptr;
   if (stage_buffer(c, (size_t)nvar * total, &tmp)) return 1;
   if (ghosts_for_output(c)) return 1;
   const int fourth = c->cfg.viscous_recon == AGX_VISC_RECON_CENTRAL_4TH ? 1 : 0;
   hipLaunchKernelGGL(k_wall_pack, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, c->stream,
-                     b.d, c->gas, sp, b.wall_tab_dev, (int)b.wall_tab.size(), total, fourth, tmp);
-  HIPCHK(hipGetLastError());
-  HIPCHK(hipMemcpyAsync(out, tmp, sizeof(double) * nvar * total, hipMemcpyDeviceToHost,
-                        c->stream));
-  HIPCHK(hipStreamSynchronize(c->stream));
-  return 0;
+                     b.d, c->gas, out_spec(c, b, nvar, vars), b.wall_tab_dev,
+                     (int)b.wall_tab.size(), total, fourth, tmp);
+  return copy_out(c, out, tmp, (size_t)nvar * total);
 }
-// WriteNodeFun's payload of one block (vars: cell ids, AGX_NODE_BASE taken off)
-int node_pack(agx_ctx* c, int id, int nvar, const int32_t* vars, double* out) {
+// WriteFunFile's payload of one block, or (node) WriteNodeFun's: one value per physical cell
+// or per node; vars: cell ids
+int point_pack(agx_ctx* c, int id, bool node, int nvar, const int32_t* vars, double* out) {
   Block& b = c->blocks[id];
-  if (!c->finalized) return fail("agx_setup_finalize has not been called");
-  OutSpec sp = out_spec(c, b);
-  sp.nvar = nvar;
+  if (node && !c->finalized) return fail("agx_setup_finalize has not been called");
   bool need_grads = false;
   for (int v = 0; v < nvar; ++v) {
     const int var = vars[v];
     if (var == AGX_OUT_VISCOSITY && !c->sp.viscous)
       return fail("viscosity_ is only kept for viscous runs (procBlock.cpp:6171)");
 #if AGX_NEQ == 7
-    if (var == AGX_OUT_VISCOSITY_RATIO || var == AGX_OUT_TURB_VISCOSITY || var == AGX_OUT_F1 ||
-        var == AGX_OUT_F2)
+    if (node && (var == AGX_OUT_VISCOSITY_RATIO || var == AGX_OUT_TURB_VISCOSITY ||
+                 var == AGX_OUT_F1 || var == AGX_OUT_F2))
       return fail("agx_output_pack: node variable %d (viscosityRatio, turbulentViscosity, f1, f2) "
                   "is not formed at nodes: the reference averages eddyViscosity_, f1_, f2_ with "
                   "their ghost cells, which hold what the residual's accumulation at boundary "
                   "faces and the corner initial values left; the library keeps them in physical "
                   "cells and connection ghost cells only", AGX_NODE_BASE + var);
 #endif
-    sp.var[v] = var;
     need_grads = need_grads || (var >= AGX_OUT_VELGRAD && var < AGX_OUT_RESID);
   }
-  const long nnode = (long)(b.d.ni + 1) * (b.d.nj + 1) * (b.d.nk + 1);
+  const int n1 = node ? 1 : 0;      // one node more than cells along each direction
+  const long npoint = (long)(b.d.ni + n1) * (b.d.nj + n1) * (b.d.nk + n1);
   double* tmp = nullptr;
-  const size_t gdoubles = need_grads ? (size_t)3 * NGF * nnode : 0;
-  if (stage_buffer(c, gdoubles + (size_t)nvar * nnode, &tmp)) return 1;
-  // every nodal variable reads ghost cells: those the next residual would see
-  if (ghosts_for_output(c)) return 1;
-  const dim3 grid((b.d.ni + CELL_BLOCK.x) / CELL_BLOCK.x, (b.d.nj + CELL_BLOCK.y) / CELL_BLOCK.y,
-                  b.d.nk + 1);
+  const size_t gdoubles = need_grads ? (size_t)3 * NGF * npoint : 0;
+  if (stage_buffer(c, gdoubles + (size_t)nvar * npoint, &tmp)) return 1;
+  // every nodal variable reads ghost cells, of the cell variables the gradients do: those the
+  // next residual would see
+  if ((node || need_grads) && ghosts_for_output(c)) return 1;
+  const dim3 grid((b.d.ni + n1 + CELL_BLOCK.x - 1) / CELL_BLOCK.x,
+                  (b.d.nj + n1 + CELL_BLOCK.y - 1) / CELL_BLOCK.y, b.d.nk + n1);
   if (need_grads)
-    hipLaunchKernelGGL(k_node_grads, grid, CELL_BLOCK, 0, c->stream, b.d, c->gas, tmp);
+    hipLaunchKernelGGL(node ? k_node_grads : k_cell_grads, grid, CELL_BLOCK, 0, c->stream, b.d,
+                       c->gas, tmp);
   double* packed = tmp + gdoubles;
-  hipLaunchKernelGGL(k_node_pack, grid, CELL_BLOCK, 0, c->stream, b.d, c->gas, sp,
-                     need_grads ? tmp : nullptr, packed);
-  HIPCHK(hipGetLastError());
-  HIPCHK(hipMemcpyAsync(out, packed, sizeof(double) * nvar * nnode, hipMemcpyDeviceToHost,
-                        c->stream));
-  HIPCHK(hipStreamSynchronize(c->stream));
-  return 0;
+  hipLaunchKernelGGL(node ? k_node_pack : k_output_pack, grid, CELL_BLOCK, 0, c->stream, b.d,
+                     c->gas, out_spec(c, b, nvar, vars), need_grads ? tmp : nullptr, packed);
+  return copy_out(c, out, packed, (size_t)nvar * npoint);
 }
 }  // namespace
 
@@ -2499,7 +2500,7 @@ int agx_output_pack(agx_ctx* c, int id, int nvar, const int32_t* vars, double* o
                   "one kind)");
     int32_t ids[AGX_OUT_COUNT];
     for (int v = 0; v < nvar; ++v) ids[v] = vars[v] - AGX_NODE_BASE;
-    return node_pack(c, id, nvar, ids, out);
+    return point_pack(c, id, true, nvar, ids, out);
   }
   if (n_wall > 0) {
     if (n_wall != nvar)
@@ -2509,34 +2510,7 @@ int agx_output_pack(agx_ctx* c, int id, int nvar, const int32_t* vars, double* o
       return fail("agx_output_pack: nvar %d out of range", nvar);
     return wall_pack(c, id, nvar, vars, out);
   }
-  Block& b = c->blocks[id];
-  OutSpec sp = out_spec(c, b);
-  sp.nvar = nvar;
-  bool need_grads = false;
-  for (int v = 0; v < nvar; ++v) {
-    if (vars[v] < 0 || vars[v] >= AGX_OUT_COUNT) return fail("unknown output variable %d", vars[v]);
-    if (vars[v] == AGX_OUT_VISCOSITY && !c->sp.viscous)
-      return fail("viscosity_ is only kept for viscous runs (procBlock.cpp:6171)");
-    sp.var[v] = vars[v];
-    need_grads = need_grads || (vars[v] >= AGX_OUT_VELGRAD && vars[v] < AGX_OUT_RESID);
-  }
-  const long ncell = (long)b.d.ni * b.d.nj * b.d.nk;
-  double* tmp = nullptr;
-  const size_t gdoubles = need_grads ? (size_t)3 * NGF * ncell : 0;
-  if (stage_buffer(c, gdoubles + (size_t)nvar * ncell, &tmp)) return 1;
-  if (need_grads) {
-    if (ghosts_for_output(c)) return 1;
-    hipLaunchKernelGGL(k_cell_grads, cell_grid(b.d, CELL_BLOCK), CELL_BLOCK, 0, c->stream, b.d,
-                       c->gas, tmp);
-  }
-  double* packed = tmp + gdoubles;
-  hipLaunchKernelGGL(k_output_pack, cell_grid(b.d, CELL_BLOCK), CELL_BLOCK, 0, c->stream, b.d,
-                     c->gas, sp, need_grads ? tmp : nullptr, packed);
-  HIPCHK(hipGetLastError());
-  HIPCHK(hipMemcpyAsync(out, packed, sizeof(double) * nvar * ncell, hipMemcpyDeviceToHost,
-                        c->stream));
-  HIPCHK(hipStreamSynchronize(c->stream));
-  return 0;
+  return point_pack(c, id, false, nvar, vars, out);
 }
 
 int agx_restart_pack(agx_ctx* c, int id, int which, double* out) {
@@ -2549,11 +2523,7 @@ int agx_restart_pack(agx_ctx* c, int id, int which, double* out) {
   if (stage_buffer(c, (size_t)(AGX_NEQ + 1) * ncell, &tmp)) return 1;
   hipLaunchKernelGGL(k_restart_pack, cell_grid(b.d, CELL_BLOCK), CELL_BLOCK, 0, c->stream, b.d,
                      out_spec(c, b), which, tmp);
-  HIPCHK(hipGetLastError());
-  HIPCHK(hipMemcpyAsync(out, tmp, sizeof(double) * (AGX_NEQ + 1) * ncell, hipMemcpyDeviceToHost,
-                        c->stream));
-  HIPCHK(hipStreamSynchronize(c->stream));
-  return 0;
+  return copy_out(c, out, tmp, (size_t)(AGX_NEQ + 1) * ncell);
 }
 
 // ---- set-up helpers -------------------------------------------------
@@ -2608,10 +2578,7 @@ int agx_nearest_wall_distance(agx_ctx* c, int64_t ncell, const double* cen, int6
   HIPCHK(hipMemcpyAsync(dw, wall, sizeof(double) * 3 * nwall, hipMemcpyHostToDevice, c->stream));
   hipLaunchKernelGGL(k_nearest_wall, dim3((unsigned)((ncell + 255) / 256)), dim3(256), 0, c->stream,
                      (long)ncell, dc, (long)nwall, dw, dd);
-  HIPCHK(hipGetLastError());
-  HIPCHK(hipMemcpyAsync(dist, dd, sizeof(double) * ncell, hipMemcpyDeviceToHost, c->stream));
-  HIPCHK(hipStreamSynchronize(c->stream));
-  return 0;
+  return copy_out(c, dist, dd, (size_t)ncell);
 }
 
 int agx_field_upload(agx_ctx* c, int id, int field, const double* in) {

@@ -3424,17 +3424,18 @@ __device__ inline void face_grad6(const BlockDev& b, const GasDev& g, int d, lon
   }
 }
 // acc: [3 NGF]; velocity gradient [3 r + c] first, then per field f >= 3 its three
-// derivatives at 9 + 3 (f - 3)
+// derivatives at 9 + 3 (f - 3).  Adds row r (d/dx_r of every field) of a face's g6 times w.
+__device__ __forceinline__ void grad_acc(double* acc, const double* g6r, int r, double w) {
+  for (int f = 0; f < 3; ++f) acc[3 * r + f] += w * g6r[f];
+  for (int f = 3; f < NGF; ++f) acc[9 + 3 * (f - 3) + r] += w * g6r[f];
+}
 __device__ inline void cell_grads18(const BlockDev& b, const GasDev& g, long q, double* acc) {
   for (int n = 0; n < 3 * NGF; ++n) acc[n] = 0.0;
   for (int d = 0; d < 3; ++d)
     for (int up = 0; up < 2; ++up) {
       double g6[3][NGF];
       face_grad6(b, g, d, q + (up ? b.stride(d) : 0), g6);
-      for (int r = 0; r < 3; ++r) {
-        for (int f = 0; f < 3; ++f) acc[3 * r + f] += (1.0 / 6.0) * g6[r][f];
-        for (int f = 3; f < NGF; ++f) acc[9 + 3 * (f - 3) + r] += (1.0 / 6.0) * g6[r][f];
-      }
+      for (int r = 0; r < 3; ++r) grad_acc(acc, g6[r], r, 1.0 / 6.0);
     }
 }
 __global__ void __launch_bounds__(256) k_cell_grads(BlockDev b, GasDev g, double* out) {
@@ -3449,16 +3450,123 @@ __global__ void __launch_bounds__(256) k_cell_grads(BlockDev b, GasDev g, double
 }
 
 // ---------------------------------------------------------------------------
-// Output: the per-cell variables of a function file, WriteFunFile (output.cpp:235-407),
-// formed and re-dimensionalised on the device; one thread per physical cell, variable by
-// variable into out[v * ncell + cell] (each store of a wave is a contiguous row).  grads:
-// k_cell_grads' output, or null when no gradient is asked for.
+// Output: the variables of a function file, WriteFunFile (output.cpp:235-407), formed and
+// re-dimensionalised on the device for a point -- a cell (k_output_pack) or a node
+// (k_node_pack).
 struct OutSpec {
   int nvar;
   int var[AGX_OUT_COUNT];
   double rho_ref, a_ref, l_ref, t_ref, mu_ref;
   int rank, global_pos;
 };
+// Sutherland's law with plain division / sqrt: an output path, the values go to a file
+// (viscosity() is the iteration's, with fast_sqrt / fast_rcp)
+__device__ __forceinline__ double out_sutherland(const GasDev& g, double t) {
+  const double temp = t * g.t_ref;
+  return (g.visc_c1 * temp * sqrt(temp)) / ((temp + g.visc_s) * g.mu_ref);
+}
+// A point of a function file: its state, the temperature that temperature, cp and cv are of
+// (a cell: that of the state; a node: the average of its eight cells'), the laminar viscosity,
+// and what out_point derives.  cs and en are of the temperature of the point's own state
+// (primitive::SoS / Energy), which only the thermally perfect gas tells from t.
+struct OutPoint {
+  double s[AGX_NEQ], t, mu;
+  double v2, cs, en, cp, cv;
+};
+__device__ __forceinline__ void out_point(const GasDev& g, OutPoint& pt) {
+  const double* s = pt.s;
+  pt.v2 = dot3(s + 1, s + 1);
+#if AGX_TPG
+  // output.cpp:236-274 with the gas properties of T
+  const double ts = s[4] / (s[0] * g.R), cvs = cv_of(g, ts);
+  pt.cs = sqrt((cvs + g.R) / cvs * s[4] / s[0]);
+  pt.en = spec_energy(g, ts) + 0.5 * pt.v2;
+  pt.cv = cv_of(g, pt.t); pt.cp = pt.cv + g.R;
+#else
+  pt.cp = g.cp; pt.cv = g.cv;
+  pt.cs = sqrt(g.gamma * s[4] / s[0]);
+  pt.en = g.hf + g.n * s[4] / s[0] + 0.5 * pt.v2;       // Energy: e(T) + |v|^2 / 2
+#endif
+}
+// the factors of resid_* (equation e) and of the gradient entries (gidx: 9 of the velocity,
+// then 3 each of T, rho, p, k, omega), output.cpp:235-407
+__device__ __forceinline__ double resid_scale(const OutSpec& sp, int e) {
+  const double rR = sp.rho_ref, aR = sp.a_ref, l2 = sp.l_ref * sp.l_ref;
+  return e == 0 ? rR * aR * l2
+         : e < 4 ? rR * aR * aR * l2
+         : e < 6 ? rR * aR * aR * aR * l2
+                 : rR * rR * aR * aR * aR * aR * l2 / sp.mu_ref;
+}
+__device__ __forceinline__ double grad_scale(const OutSpec& sp, int gidx) {
+  const double rR = sp.rho_ref, aR = sp.a_ref, lR = sp.l_ref;
+  return gidx < 9 ? aR / lR
+         : gidx < 12 ? sp.t_ref / lR
+         : gidx < 15 ? rR / lR
+         : gidx < 18 ? rR * aR * aR / lR
+         : gidx < 21 ? aR * aR / lR
+                     : aR * aR * rR / (sp.mu_ref * lR);
+}
+// Variable `var` at a point.  src is where the point takes what is not a function of its state:
+// src.plane(pl, ghosts), a plane (dt, resid[e]: physical cells only; wdist: with its face ghost
+// cells); src.grad(gidx), its row of the gradient kernel's output; src.turb(n), turb3[n] (rans).
+template <class Source>
+__device__ __forceinline__ double out_value(int var, const OutPoint& pt, const OutSpec& sp,
+                                            const Source& src) {
+  const BlockDev& b = src.b;
+  const double* s = pt.s;
+  const double rR = sp.rho_ref, aR = sp.a_ref, lR = sp.l_ref, tR = sp.t_ref, muR = sp.mu_ref;
+  switch (var) {
+    case AGX_OUT_DENSITY: return s[0] * rR;
+    case AGX_OUT_VEL_X: return s[1] * aR;
+    case AGX_OUT_VEL_Y: return s[2] * aR;
+    case AGX_OUT_VEL_Z: return s[3] * aR;
+    case AGX_OUT_PRESSURE: return s[4] * rR * aR * aR;
+    case AGX_OUT_MACH: return sqrt(pt.v2) / pt.cs;
+    case AGX_OUT_SOS: return pt.cs * aR;
+    case AGX_OUT_DT: return src.plane(b.dt, false) / (aR * lR);
+    case AGX_OUT_TEMPERATURE: return pt.t * tR;
+    case AGX_OUT_ENERGY: return pt.en * aR * aR;
+    case AGX_OUT_ENTHALPY: return (pt.en + s[4] / s[0]) * aR * aR;
+    case AGX_OUT_CP: return pt.cp * aR * aR / tR;
+    case AGX_OUT_CV: return pt.cv * aR * aR / tR;
+    case AGX_OUT_RANK: return (double)sp.rank;
+    case AGX_OUT_GLOBAL_POSITION: return (double)sp.global_pos;
+    case AGX_OUT_VISCOSITY: return pt.mu * muR;
+    case AGX_OUT_WALL_DISTANCE: return src.plane(b.wdist, true) * lR;
+#if AGX_NEQ == 7
+    case AGX_OUT_VISCOSITY_RATIO: return src.turb(0) / pt.mu;
+    case AGX_OUT_TURB_VISCOSITY: return src.turb(0) * muR;
+    case AGX_OUT_TKE: return s[5] * aR * aR;
+    case AGX_OUT_SDR: return s[6] * aR * aR * rR / muR;
+    case AGX_OUT_F1: return src.turb(1);
+    case AGX_OUT_F2: return src.turb(2);
+#endif
+  }
+  if (var >= AGX_OUT_RESID) {
+    const int e = var - AGX_OUT_RESID;
+    return e < AGX_NEQ ? src.plane(b.resid[e], false) * resid_scale(sp, e) : 0.0;
+  }
+  if (var >= AGX_OUT_VELGRAD) {
+    const int gidx = var - AGX_OUT_VELGRAD;
+    return gidx < 3 * NGF ? src.grad(gidx) * grad_scale(sp, gidx) : 0.0;
+  }
+  return 0.0;
+}
+// A cell reads its planes where it lies; q: its index in the planes, grow: its row of
+// k_cell_grads' output
+struct CellSource {
+  const BlockDev& b;
+  long q;
+  const double* grow;
+  __device__ double plane(const double* pl, bool) const { return pl[q]; }
+  __device__ double grad(int gidx) const { return grow[gidx]; }
+#if AGX_NEQ == 7
+  __device__ double turb(int n) const { return b.turb3[n][q]; }
+#endif
+};
+// One thread per physical cell, variable by variable into out[v * ncell + cell] (each store of
+// a wave is a contiguous row).  grads: k_cell_grads' output, or null when no gradient is asked
+// for.
 __global__ void __launch_bounds__(256)
 k_output_pack(BlockDev b, GasDev g, OutSpec sp, const double* __restrict__ grads,
               double* __restrict__ out) {
@@ -3468,83 +3576,13 @@ k_output_pack(BlockDev b, GasDev g, OutSpec sp, const double* __restrict__ grads
   if (i >= b.ni || j >= b.nj) return;
   const long q = b.idx(i, j, k);
   const long ncell = (long)b.ni * b.nj * b.nk, p = ((long)k * b.nj + j) * b.ni + i;
-  double s[AGX_NEQ];
-  load5(b.state, q, s);
-  const double rR = sp.rho_ref, aR = sp.a_ref, lR = sp.l_ref, tR = sp.t_ref, muR = sp.mu_ref;
-  // plain division / sqrt: an output path, the values go to a file
-  const double t = s[4] / (s[0] * g.R);
-  const double v2 = dot3(s + 1, s + 1);
-#if AGX_TPG
-  // output.cpp:236-274 with the gas properties of T
-  const double cv = cv_of(g, t), cp = cv + g.R;
-  const double cs = sqrt(cp / cv * s[4] / s[0]);
-  const double en = spec_energy(g, t) + 0.5 * v2;
-#else
-  const double cp = g.cp, cv = g.cv;
-  const double cs = sqrt(g.gamma * s[4] / s[0]);
-  const double en = g.hf + g.n * s[4] / s[0] + 0.5 * v2;       // Energy: e(T) + |v|^2 / 2
-#endif
-  for (int v = 0; v < sp.nvar; ++v) {
-    const int var = sp.var[v];
-    double val = 0.0;
-    switch (var) {
-      case AGX_OUT_DENSITY: val = s[0] * rR; break;
-      case AGX_OUT_VEL_X: val = s[1] * aR; break;
-      case AGX_OUT_VEL_Y: val = s[2] * aR; break;
-      case AGX_OUT_VEL_Z: val = s[3] * aR; break;
-      case AGX_OUT_PRESSURE: val = s[4] * rR * aR * aR; break;
-      case AGX_OUT_MACH: val = sqrt(v2) / cs; break;
-      case AGX_OUT_SOS: val = cs * aR; break;
-      case AGX_OUT_DT: val = b.dt[q] / (aR * lR); break;
-      case AGX_OUT_TEMPERATURE: val = t * tR; break;
-      case AGX_OUT_ENERGY: val = en * aR * aR; break;
-      case AGX_OUT_ENTHALPY: val = (en + s[4] / s[0]) * aR * aR; break;
-      case AGX_OUT_CP: val = cp * aR * aR / tR; break;
-      case AGX_OUT_CV: val = cv * aR * aR / tR; break;
-      case AGX_OUT_RANK: val = (double)sp.rank; break;
-      case AGX_OUT_GLOBAL_POSITION: val = (double)sp.global_pos; break;
-      case AGX_OUT_VISCOSITY: {
-        const double temp = t * g.t_ref;
-        val = (g.visc_c1 * temp * sqrt(temp)) / ((temp + g.visc_s) * g.mu_ref) * muR;
-        break;
-      }
-      case AGX_OUT_WALL_DISTANCE: val = b.wdist[q] * lR; break;
-#if AGX_NEQ == 7
-      case AGX_OUT_VISCOSITY_RATIO: {
-        const double temp = t * g.t_ref;
-        val = b.turb3[0][q] / ((g.visc_c1 * temp * sqrt(temp)) / ((temp + g.visc_s) * g.mu_ref));
-        break;
-      }
-      case AGX_OUT_TURB_VISCOSITY: val = b.turb3[0][q] * muR; break;
-      case AGX_OUT_TKE: val = s[5] * aR * aR; break;
-      case AGX_OUT_SDR: val = s[6] * aR * aR * rR / muR; break;
-      case AGX_OUT_F1: val = b.turb3[1][q]; break;
-      case AGX_OUT_F2: val = b.turb3[2][q]; break;
-#endif
-      default:
-        if (var >= AGX_OUT_RESID) {
-          const int e = var - AGX_OUT_RESID;
-          if (e < AGX_NEQ) {
-            const double l2 = lR * lR;
-            const double sc = e == 0 ? rR * aR * l2
-                              : e < 4 ? rR * aR * aR * l2
-                              : e < 6 ? rR * aR * aR * aR * l2
-                                      : rR * rR * aR * aR * aR * aR * l2 / muR;
-            val = b.resid[e][q] * sc;
-          }
-        } else if (var >= AGX_OUT_VELGRAD) {
-          const int gidx = var - AGX_OUT_VELGRAD;
-          const double sc = gidx < 9 ? aR / lR
-                            : gidx < 12 ? tR / lR
-                            : gidx < 15 ? rR / lR
-                            : gidx < 18 ? rR * aR * aR / lR
-                            : gidx < 21 ? aR * aR / lR
-                                        : aR * aR * rR / (muR * lR);
-          val = gidx < 3 * NGF ? grads[3 * NGF * p + gidx] * sc : 0.0;
-        }
-    }
-    out[(long)v * ncell + p] = val;
-  }
+  OutPoint pt;
+  load5(b.state, q, pt.s);
+  pt.t = pt.s[4] / (pt.s[0] * g.R);
+  pt.mu = out_sutherland(g, pt.t);
+  out_point(g, pt);
+  const CellSource src{b, q, grads ? grads + 3 * NGF * p : nullptr};
+  for (int v = 0; v < sp.nvar; ++v) out[(long)v * ncell + p] = out_value(sp.var[v], pt, sp, src);
 }
 // WriteWallFun (output.cpp:472-571): the wall variables of the block's viscousWall surfaces,
 // one thread per wall face, all surfaces in one launch through a table (surface -> index
@@ -3692,10 +3730,7 @@ __global__ void __launch_bounds__(256) k_node_grads(BlockDev b, GasDev g, double
         continue;
       double g6[3][NGF];
       face_grad6(b, g, d, b.idx(ci, cj, ck), g6);
-      for (int r = 0; r < 3; ++r) {
-        for (int f = 0; f < 3; ++f) acc[3 * r + f] += g6[r][f];
-        for (int f = 3; f < NGF; ++f) acc[9 + 3 * (f - 3) + r] += g6[r][f];
-      }
+      for (int r = 0; r < 3; ++r) grad_acc(acc, g6[r], r, 1.0);
     }
   }
   const int nb = (i == 0 || i == b.ni) + (j == 0 || j == b.nj) + (k == 0 || k == b.nk);
@@ -3707,7 +3742,7 @@ __global__ void __launch_bounds__(256) k_node_grads(BlockDev b, GasDev g, double
 // stores of a variable are a contiguous row); sp.var holds cell ids (AGX_NODE_BASE taken off).
 //   node state        1/8 of the eight cells of the ghost-inclusive state (ConvertCellToNode
 //                     without ignoreEdge); density .. sdr, mach, sos, energy, enthalpy are
-//                     k_output_pack's functions of it
+//                     out_value's functions of it
 //   temperature, viscosity   1/8 of the eight cells' temperature_ / viscosity_ (the corner
 //                     ghost cells evaluated from their corner-rule state); cp, cv of that
 //                     temperature
@@ -3715,50 +3750,13 @@ __global__ void __launch_bounds__(256) k_node_grads(BlockDev b, GasDev g, double
 //                     on its edges, 1/8 elsewhere (k_mg_nodes)
 //   wallDistance      physical and face ghost cells, times 1/4, 1/6, 1/8
 //   gradients         k_node_grads' output
-__global__ void __launch_bounds__(256)
-k_node_pack(BlockDev b, GasDev g, OutSpec sp, const double* __restrict__ grads,
-            double* __restrict__ out) {
-  const int i = blockIdx.x * blockDim.x + threadIdx.x;
-  const int j = blockIdx.y * blockDim.y + threadIdx.y;
-  const int k = blockIdx.z;
-  if (i > b.ni || j > b.nj) return;
-  const long nnode = (long)(b.ni + 1) * (b.nj + 1) * (b.nk + 1);
-  const long p = ((long)k * (b.nj + 1) + j) * (b.ni + 1) + i;
-  const double rR = sp.rho_ref, aR = sp.a_ref, lR = sp.l_ref, tR = sp.t_ref, muR = sp.mu_ref;
-  double s[AGX_NEQ], tsum = 0.0, musum = 0.0;
-#pragma unroll
-  for (int e = 0; e < AGX_NEQ; ++e) s[e] = 0.0;
-  for (int dk = -1; dk <= 0; ++dk)
-    for (int dj = -1; dj <= 0; ++dj)
-      for (int di = -1; di <= 0; ++di) {
-        double c[AGX_NEQ];
-        node_cell_state(b, i + di, j + dj, k + dk, c);
-#pragma unroll
-        for (int e = 0; e < AGX_NEQ; ++e) s[e] += c[e];
-        // plain division / sqrt: an output path, the values go to a file
-        const double tc = c[4] / (c[0] * g.R), temp = tc * g.t_ref;
-        tsum += tc;
-        musum += (g.visc_c1 * temp * sqrt(temp)) / ((temp + g.visc_s) * g.mu_ref);
-      }
-#pragma unroll
-  for (int e = 0; e < AGX_NEQ; ++e) s[e] *= 0.125;
-  const double tavg = tsum * 0.125, muavg = musum * 0.125;
-  const double v2 = dot3(s + 1, s + 1);
-#if AGX_TPG
-  const double t = s[4] / (s[0] * g.R);      // of the node state: primitive::SoS / Energy
-  const double cvs = cv_of(g, t);
-  const double cs = sqrt((cvs + g.R) / cvs * s[4] / s[0]);
-  const double en = spec_energy(g, t) + 0.5 * v2;
-  const double cv = cv_of(g, tavg), cp = cv + g.R;
-#else
-  const double cp = g.cp, cv = g.cv;
-  const double cs = sqrt(g.gamma * s[4] / s[0]);
-  const double en = g.hf + g.n * s[4] / s[0] + 0.5 * v2;
-#endif
-  const bool xi = i == 0 || i == b.ni, xj = j == 0 || j == b.nj, xk = k == 0 || k == b.nk;
-  const int nb = xi + xj + xk;
+// A node gathers its planes; nb: how many of the block's boundaries it lies on
+struct NodeSource {
+  const BlockDev& b;
+  int i, j, k, nb;
+  const double* grow;
   // a plane without ghost cells (ghosts = false) or with its face ghost cells
-  auto gather = [&](const double* pl, bool ghosts) {
+  __device__ double plane(const double* pl, bool ghosts) const {
     double a = 0.0;
     for (int dk = -1; dk <= 0; ++dk)
       for (int dj = -1; dj <= 0; ++dj)
@@ -3769,56 +3767,45 @@ k_node_pack(BlockDev b, GasDev g, OutSpec sp, const double* __restrict__ grads,
           a += pl[b.idx(ci, cj, ck)];
         }
     return a * (nb == 3 ? (ghosts ? 0.25 : 1.0) : nb == 2 ? (ghosts ? 1.0 / 6.0 : 0.5) : 0.125);
-  };
-  for (int v = 0; v < sp.nvar; ++v) {
-    const int var = sp.var[v];
-    double val = 0.0;
-    switch (var) {
-      case AGX_OUT_DENSITY: val = s[0] * rR; break;
-      case AGX_OUT_VEL_X: val = s[1] * aR; break;
-      case AGX_OUT_VEL_Y: val = s[2] * aR; break;
-      case AGX_OUT_VEL_Z: val = s[3] * aR; break;
-      case AGX_OUT_PRESSURE: val = s[4] * rR * aR * aR; break;
-      case AGX_OUT_MACH: val = sqrt(v2) / cs; break;
-      case AGX_OUT_SOS: val = cs * aR; break;
-      case AGX_OUT_DT: val = gather(b.dt, false) / (aR * lR); break;
-      case AGX_OUT_TEMPERATURE: val = tavg * tR; break;
-      case AGX_OUT_ENERGY: val = en * aR * aR; break;
-      case AGX_OUT_ENTHALPY: val = (en + s[4] / s[0]) * aR * aR; break;
-      case AGX_OUT_CP: val = cp * aR * aR / tR; break;
-      case AGX_OUT_CV: val = cv * aR * aR / tR; break;
-      case AGX_OUT_RANK: val = (double)sp.rank; break;
-      case AGX_OUT_GLOBAL_POSITION: val = (double)sp.global_pos; break;
-      case AGX_OUT_VISCOSITY: val = muavg * muR; break;
-      case AGX_OUT_WALL_DISTANCE: val = gather(b.wdist, true) * lR; break;
-#if AGX_NEQ == 7
-      case AGX_OUT_TKE: val = s[5] * aR * aR; break;
-      case AGX_OUT_SDR: val = s[6] * aR * aR * rR / muR; break;
-#endif
-      default:
-        if (var >= AGX_OUT_RESID) {
-          const int e = var - AGX_OUT_RESID;
-          if (e < AGX_NEQ) {
-            const double l2 = lR * lR;
-            const double sc = e == 0 ? rR * aR * l2
-                              : e < 4 ? rR * aR * aR * l2
-                              : e < 6 ? rR * aR * aR * aR * l2
-                                      : rR * rR * aR * aR * aR * aR * l2 / muR;
-            val = gather(b.resid[e], false) * sc;
-          }
-        } else if (var >= AGX_OUT_VELGRAD) {
-          const int gidx = var - AGX_OUT_VELGRAD;
-          const double sc = gidx < 9 ? aR / lR
-                            : gidx < 12 ? tR / lR
-                            : gidx < 15 ? rR / lR
-                            : gidx < 18 ? rR * aR * aR / lR
-                            : gidx < 21 ? aR * aR / lR
-                                        : aR * aR * rR / (muR * lR);
-          val = gidx < 3 * NGF ? grads[3 * NGF * p + gidx] * sc : 0.0;
-        }
-    }
-    out[(long)v * nnode + p] = val;
   }
+  __device__ double grad(int gidx) const { return grow[gidx]; }
+#if AGX_NEQ == 7
+  // viscosityRatio, turbulentViscosity, f1, f2 are refused at nodes by agx_output_pack
+  __device__ double turb(int) const { return 0.0; }
+#endif
+};
+__global__ void __launch_bounds__(256)
+k_node_pack(BlockDev b, GasDev g, OutSpec sp, const double* __restrict__ grads,
+            double* __restrict__ out) {
+  const int i = blockIdx.x * blockDim.x + threadIdx.x;
+  const int j = blockIdx.y * blockDim.y + threadIdx.y;
+  const int k = blockIdx.z;
+  if (i > b.ni || j > b.nj) return;
+  const long nnode = (long)(b.ni + 1) * (b.nj + 1) * (b.nk + 1);
+  const long p = ((long)k * (b.nj + 1) + j) * (b.ni + 1) + i;
+  OutPoint pt;
+  double tsum = 0.0, musum = 0.0;
+#pragma unroll
+  for (int e = 0; e < AGX_NEQ; ++e) pt.s[e] = 0.0;
+  for (int dk = -1; dk <= 0; ++dk)
+    for (int dj = -1; dj <= 0; ++dj)
+      for (int di = -1; di <= 0; ++di) {
+        double c[AGX_NEQ];
+        node_cell_state(b, i + di, j + dj, k + dk, c);
+#pragma unroll
+        for (int e = 0; e < AGX_NEQ; ++e) pt.s[e] += c[e];
+        const double tc = c[4] / (c[0] * g.R);
+        tsum += tc;
+        musum += out_sutherland(g, tc);
+      }
+#pragma unroll
+  for (int e = 0; e < AGX_NEQ; ++e) pt.s[e] *= 0.125;
+  pt.t = tsum * 0.125;
+  pt.mu = musum * 0.125;
+  out_point(g, pt);
+  const int nb = (i == 0 || i == b.ni) + (j == 0 || j == b.nj) + (k == 0 || k == b.nk);
+  const NodeSource src{b, i, j, k, nb, grads ? grads + 3 * NGF * p : nullptr};
+  for (int v = 0; v < sp.nvar; ++v) out[(long)v * nnode + p] = out_value(sp.var[v], pt, sp, src);
 }
 // WriteRestart (output.cpp:651-752): n_eq + 1 dimensional values per cell, cell by cell;
 // which = 0: the state, 1: consVarsNm1.  The payload is cell-major, so a wave's stores of

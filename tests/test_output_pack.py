@@ -111,3 +111,35 @@ def test_output_and_restart_pack_parity(kind, oracle):
     for q, n in enumerate(sub):
         assert np.array_equal(z[q], a[names.index(n)])
     sg.close(), so.close()
+
+
+@pytest.mark.gpu
+def test_cell_range_refusals_leave_the_next_payload_unchanged(agx):
+    """The cell range's side of the contract the wall and node modules check for theirs: on an
+    inviscid block viscosity is refused, a list that mixes cell ids with wall or node ids is
+    refused, each by its text, and the valid call after them gives the bits of the one before."""
+    case = synthetic.single_block_case((4, 3, 2), equation_set="euler",
+                                       time_integration="implicitEuler", cfl=5.0)
+    s = Solver(agx, case)
+    s.step(0)
+    names = ["density", "velGrad_ux", "mach", "resid_energy", "pressGrad_z", "dt"]
+    before = s.output_pack(0, names)
+    assert np.isfinite(before).all() and np.abs(before[names.index("density")]).min() > 0.0
+
+    def raw(ids):
+        out = np.zeros(len(ids) * 5 * 4 * 3)
+        s.api.check(s.api.output_pack(s.ctx, s.block_ids[0], len(ids),
+                                      (abi.C.c_int32 * len(ids))(*ids),
+                                      out.ctypes.data_as(abi.c_dp)), "output_pack")
+
+    with pytest.raises(RuntimeError, match="only kept for viscous runs"):
+        s.output_pack(0, ["density", "viscosity"])
+    cell, wall, node = abi.OUT["density"], abi.WALL_OUT["density"], abi.NODE_OUT["density"]
+    for ids in ([cell, wall], [wall, cell]):
+        with pytest.raises(RuntimeError, match="cell and wall variables in one call"):
+            raw(ids)
+    for ids in ([cell, node], [node, cell]):
+        with pytest.raises(RuntimeError, match="cell and node variables in one call"):
+            raw(ids)
+    assert np.array_equal(s.output_pack(0, names), before)
+    s.close()
