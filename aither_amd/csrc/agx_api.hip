@@ -3365,7 +3365,7 @@ namespace {
 // `status`: this rank's local result of the iteration; a failure anywhere makes every
 // rank return failure (the collectives are reached by all ranks either way)
 int reduce_over_ranks(agx_ctx* c, double* l2, agx_linf* linf, double* matrix_resid,
-                      const double* l2_in, int status) {
+                      const double* l2_in, const agx_linf& linf_in, int status) {
   typedef agx_ctx::NormRecord Rec;
   const int nr = c->ex.nranks;
   Rec& mine = c->rec_host[0];
@@ -3393,9 +3393,12 @@ int reduce_over_ranks(agx_ctx* c, double* l2, agx_linf* linf, double* matrix_res
       return fail("agx_iterate: rank %d failed (status %d); its agx_last_error has the cause",
                   r, all[r].status);
     }
-  // fold in rank order: the same result on every rank
+  // fold in rank order from what the caller passed in: the same result on every rank, and
+  // of equal maxima the lowest rank's (MaxLinf resid.cpp:55-79 keeps the lower rank's on
+  // `>=`) -- starting from this rank's own record would let a rank keep its own on a tie
   double mres = 0.0;
   for (int e = 0; e < AGX_NEQ; ++e) l2[e] = l2_in[e];
+  *linf = linf_in;
   for (int r = 0; r < nr; ++r) {
     for (int e = 0; e < AGX_NEQ; ++e) l2[e] += all[r].l2[e];
     mres += all[r].mres;
@@ -3418,6 +3421,7 @@ int agx_iterate(agx_ctx* c, int mm, double cfl, double* l2, agx_linf* linf,
                 "(agx_set_exchange / agx_rccl_exchange_create) or the phase API");
   double l2_in[AGX_NEQ];
   for (int e = 0; e < AGX_NEQ; ++e) l2_in[e] = l2[e];
+  const agx_linf linf_in = *linf;
   // A local failure (a singular block, the sweep's spin limit, a refused phase) must not
   // leave the other ranks waiting in a collective: from the first failure on the compute
   // phases are skipped, the exchanges and the final all-gather are still reached, and the
@@ -3488,7 +3492,7 @@ int agx_iterate(agx_ctx* c, int mm, double cfl, double* l2, agx_linf* linf,
   // the update queues the next call's ghost fill -- an exchange -- behind its norms
   if (st && collective && c->eager_ghosts) (void)fill_ghosts(c);
   if (st) memcpy(g_err, first_err, sizeof g_err);
-  if (c->have_ex) return reduce_over_ranks(c, l2, linf, matrix_resid, l2_in, st);
+  if (c->have_ex) return reduce_over_ranks(c, l2, linf, matrix_resid, l2_in, linf_in, st);
   return st;
 }
 

@@ -3649,6 +3649,7 @@ int ora_iterate(ora_ctx *c, int mm, double cfl, double *l2, agx_linf *linf,
                 double *matrix_resid) {
   double l2_in[NEQM];
   for (int e = 0; e < NEQ; ++e) l2_in[e] = l2[e];
+  const agx_linf linf_in = *linf;
   if (!c->have_ex)
     for (int n = 0; n < c->nconn; ++n)
       if (my_side(c, &c->conn[n]) >= 0)
@@ -3694,8 +3695,11 @@ int ora_iterate(ora_ctx *c, int mm, double cfl, double *l2, agx_linf *linf,
       free(all);
       return fail("the exchange's allgather operation failed");
     }
+    /* from what the caller passed in: of equal maxima the lowest rank's on every rank
+     * (MaxLinf resid.cpp:55-79), not each rank's own */
     double mres = 0.0;
     for (int e = 0; e < NEQ; ++e) l2[e] = l2_in[e];
+    *linf = linf_in;
     for (int r = 0; r < nr; ++r) {
       for (int e = 0; e < NEQ; ++e) l2[e] += all[r].l2[e];
       mres += all[r].mres;

@@ -64,6 +64,10 @@ def _make_case(kind, world, builder):
         from aither_amd.case.builder import build_case
         inp = os.path.join(ROOT, "tests", "golden", "cases", kind, kind + ".inp")
         return lambda rank: build_case(inp, ranks=list(range(world)))
+    if builder == "tie":         # equal maxima of the residual in every block
+        from tie_fields import TIE_DECKS, extruded_case, tie_box
+        return lambda rank: extruded_case(tie_box("k"), "k", world, ranks=list(range(world)),
+                                          **TIE_DECKS[kind])
     if builder == "stacked":
         return lambda rank: synthetic.stacked_blocks_case(
             (6, 5, 4), nblocks=world, axis="k", stretch=1.1,
@@ -87,7 +91,7 @@ def _worker(rank, world, port, kind, builder, steps, q, in_library=False):
         sol.step(nn)
     (gb,) = sol.block_ids
     q.put((rank, sol.download("state", gb), sol.download("residual", gb),
-           np.array([h["l2"] ** 2 for h in sol.history])))
+           np.array([h["l2"] ** 2 for h in sol.history]), [h["linf"] for h in sol.history]))
     dist.barrier()
     sol.close()
     dist.destroy_process_group()
@@ -104,12 +108,28 @@ def _run(world, kind, builder, steps=2, in_library=False):
         p.start()
     res = {}
     for _ in range(world):
-        rank, st, rs, l2 = q.get(timeout=300)
-        res[rank] = (st, rs, l2)
+        rank, st, rs, l2, linf = q.get(timeout=300)
+        res[rank] = (st, rs, l2, linf)
     for p in procs:
         p.join(timeout=60)
         assert p.exitcode == 0
     return res
+
+
+def test_tied_maximum_over_ranks_goes_to_the_lowest_rank(oracle):
+    """The rank merge of the L-inf record (main.cpp:254-264, MaxLinf resid.cpp:55-79): three
+    blocks with bit-equal maxima on three ranks -- every rank returns the single-process
+    record, block 0's, also the ranks whose own record is as large."""
+    from tie_fields import TIE_DECKS, extruded_case, tie_box
+    res = _run(3, "visc_explicit", "tie", steps=1, in_library=True)
+    ref = Solver(oracle, extruded_case(tie_box("k"), "k", 3, **TIE_DECKS["visc_explicit"]))
+    ref.step(0)
+    want = [h["linf"] for h in ref.history]
+    ref.close()
+    assert want[0][0] > 0.0 and want[0][1] == 0
+    for r in range(3):
+        assert res[r][1].max() == res[0][1].max()        # the blocks' maxima are equal
+        assert res[r][3] == want, (r, res[r][3], want)
 
 
 @pytest.mark.parametrize("world,kind", [(2, "rk4"), (2, "dplur"), (2, "lusgs"),

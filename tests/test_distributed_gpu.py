@@ -14,7 +14,8 @@ import torch.distributed as dist
 import torch.multiprocessing as mp
 
 from conftest import _oracle_lib
-from parity_utils import rel_err, RTOL
+from parity_utils import (rel_err, assert_components, flux_scale, step_with_residuals,
+                          tied_set, LINF_MARGIN, RTOL)
 from aither_amd import abi
 from aither_amd.case import synthetic
 from aither_amd.solver import Solver, PhasedSolver, DistExchange
@@ -41,9 +42,66 @@ def _case(kind, ranks):
         root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
         return build_case(os.path.join(root, "tests", "golden", "cases", kind, kind + ".inp"),
                           ranks=ranks)
+    if kind == "tie":         # tests/test_norm_record_gpu.py: equal maxima in both blocks
+        import tie_fields
+        return tie_fields.tie_case("k_update_d2", "k", 2, ranks=ranks)
     dims = (20, 9, 8) if kind == "rans" else DIMS
     return synthetic.stacked_blocks_case(dims, nblocks=2, axis="k", stretch=1.1,
                                          ranks=ranks, **KW[kind])
+
+
+def _reference(oracle, case, steps=2):
+    """The single-process oracle, keeping with every history entry the residual of its
+    iteration and the state its time step started with ("start": the floors' input)."""
+    ref = Solver(oracle, case)
+    for nn in range(steps):
+        start = [ref.download("state", gb) for gb in ref.block_ids]
+        n = len(ref.history)
+        step_with_residuals(ref, nn)
+        for h in ref.history[n:]:
+            h["start"] = start
+    return ref
+
+
+def _check_records(case, ref, records, every_rank_global):
+    """The L-inf records of the ranks against the single-process oracle's, entry by entry:
+    the value to RTOL (on the flux floor where it is below it); the location wherever the
+    oracle's residual separates its maximum by LINF_MARGIN (parity_utils.run_pair).
+    every_rank_global: each rank returned the merged record (agx_iterate with an exchange);
+    otherwise the ranks' own records are merged here as main.cpp:254 does -- the larger
+    value, the lower rank where they are equal."""
+    rfloor = 1.0e-3 * flux_scale(case)
+    for n, ho in enumerate(ref.history):
+        lo = ho["linf"]
+        if every_rank_global:
+            got = [rec[n] for rec in records]
+        else:
+            best = records[0][n]
+            for rec in records[1:]:
+                if rec[n][0] > best[0]:
+                    best = rec[n]
+            got = [best]
+        tied, gap = tied_set(ho["residual"])
+        margin = LINF_MARGIN * max(lo[0], rfloor)
+        for lg in got:
+            assert abs(lg[0] - lo[0]) <= RTOL * max(abs(lo[0]), rfloor), (n, lg, lo)
+            if lo[0] > margin and gap > margin:
+                assert tuple(lg[1:]) in tied, (n, lg, lo)
+                if len(tied) == 1:
+                    assert tuple(lg[1:]) == tuple(lo[1:]), (n, lg, lo)
+
+
+def _check_components(case, ref, l2sq, states):
+    """Norms and states of the whole case, every component on its own scale
+    (parity_utils.component_err).  states: {global block: state with ghost cells}."""
+    ng = case.ng
+    core = lambda a: a[ng:-ng, ng:-ng, ng:-ng]
+    gbs = sorted(states)
+    b = [ref.download("state", gb) for gb in gbs]
+    for n, ho in enumerate(ref.history):
+        assert_components(case, "l2", np.sqrt(l2sq[n])[None, :], ho["l2"][None, :],
+                          ho["start"], (n,))
+    assert_components(case, "state", [core(states[gb]) for gb in gbs], [core(x) for x in b], b)
 
 
 def _exchange(items):
@@ -72,14 +130,16 @@ def _worker(rank, port, kind, q, in_library=False):
     import aither_amd
     agx = aither_amd.load(7 if kind in ("rans", "wallLaw") else 5)
     case = _case(kind, [0, 1])
+    steps = 1 if kind == "tie" else 2
     if in_library:   # agx_iterate drives the remote connection (host-staged slabs over gloo)
         sol = Solver(agx, case, rank=rank, exchange=DistExchange(2))
     else:
         sol = PhasedSolver(agx, case, rank, _exchange, _alloc)
-    for nn in range(2):
+    for nn in range(steps):
         sol.step(nn)
     (gb,) = sol.block_ids
-    q.put((rank, sol.download("state", gb), np.array([h["l2"] ** 2 for h in sol.history])))
+    q.put((rank, sol.download("state", gb), np.array([h["l2"] ** 2 for h in sol.history]),
+           [h["linf"] for h in sol.history]))
     dist.barrier()
     sol.close()
     dist.destroy_process_group()
@@ -101,6 +161,9 @@ def test_rccl_transport_single_rank(agx, oracle):
         sg.step(nn), so.step(nn)
     assert rel_err(np.array([h["l2"] for h in sg.history]),
                    np.array([h["l2"] for h in so.history])) < RTOL
+    rfloor = 1.0e-3 * flux_scale(case)
+    for hg, ho in zip(sg.history, so.history):
+        assert abs(hg["linf"][0] - ho["linf"][0]) <= RTOL * max(ho["linf"][0], rfloor)
     ng = case.ng
     for gb in range(2):
         assert rel_err(sg.download("state", gb)[ng:-ng, ng:-ng, ng:-ng],
@@ -108,11 +171,8 @@ def test_rccl_transport_single_rank(agx, oracle):
     sg.close(), so.close()
 
 
-@pytest.mark.gpu
-@pytest.mark.parametrize("kind,in_library", [(k, False) for k in sorted(KW)] +
-                         [("rk4", True), ("lusgs", True), ("dplur", True), ("rans", True),
-                          ("wallLaw", False), ("wallLaw", True)])
-def test_two_ranks_on_one_gpu(oracle, kind, in_library):
+def two_ranks_on_one_gpu(kind, in_library):
+    """{rank: (state of its block, l2^2 history, L-inf history)} of two processes on cuda:0."""
     ctx = mp.get_context("spawn")
     q = ctx.Queue()
     with socket.socket() as s:
@@ -123,23 +183,34 @@ def test_two_ranks_on_one_gpu(oracle, kind, in_library):
         p.start()
     res = {}
     for _ in range(2):
-        rank, st, l2 = q.get(timeout=300)
-        res[rank] = (st, l2)
+        rank, st, l2, linf = q.get(timeout=300)
+        res[rank] = (st, l2, linf)
     for p in procs:
         p.join(timeout=60)
         assert p.exitcode == 0
+    return res
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("kind,in_library", [(k, False) for k in sorted(KW)] +
+                         [("rk4", True), ("lusgs", True), ("dplur", True), ("rans", True),
+                          ("wallLaw", False), ("wallLaw", True)])
+def test_two_ranks_on_one_gpu(oracle, kind, in_library):
+    res = two_ranks_on_one_gpu(kind, in_library)
     case = _case(kind, None)
-    ref = Solver(oracle, case)
-    for nn in range(2):
-        ref.step(nn)
+    ref = _reference(oracle, case)
     ng = case.ng
     core = lambda a: a[ng:-ng, ng:-ng, ng:-ng]
     l2ref = np.array([h["l2"] ** 2 for h in ref.history])
     # the phase API returns rank-local norms, iterate-with-exchange the global ones
     got = res[0][1] if in_library else res[0][1] + res[1][1]
     assert rel_err(got, l2ref) < RTOL
+    if in_library:
+        assert np.array_equal(res[0][1], res[1][1]) and res[0][2] == res[1][2]
     for r in range(2):
         assert rel_err(core(res[r][0]), core(ref.download("state", r))) < RTOL
+    _check_components(case, ref, got, {r: res[r][0] for r in range(2)})
+    _check_records(case, ref, [res[0][2], res[1][2]], in_library)
     ref.close()
 
 
@@ -158,7 +229,8 @@ def _rccl_worker(rank, port, kind, q):
     for nn in range(2):
         sol.step(nn)
     (gb,) = sol.block_ids
-    q.put((rank, sol.download("state", gb), np.array([h["l2"] ** 2 for h in sol.history])))
+    q.put((rank, sol.download("state", gb), np.array([h["l2"] ** 2 for h in sol.history]),
+           [h["linf"] for h in sol.history]))
     dist.barrier()
     sol.close()
     dist.destroy_process_group()
@@ -182,15 +254,13 @@ def test_two_gpus_rccl_transport(oracle, kind):
         p.start()
     res = {}
     for _ in range(2):
-        rank, st, l2 = q.get(timeout=300)
-        res[rank] = (st, l2)
+        rank, st, l2, linf = q.get(timeout=300)
+        res[rank] = (st, l2, linf)
     for p in procs:
         p.join(timeout=60)
         assert p.exitcode == 0
     case = _case(kind, None)
-    ref = Solver(oracle, case)
-    for nn in range(2):
-        ref.step(nn)
+    ref = _reference(oracle, case)
     ng = case.ng
     core = lambda a: a[ng:-ng, ng:-ng, ng:-ng]
     l2ref = np.array([h["l2"] ** 2 for h in ref.history])
@@ -198,6 +268,8 @@ def test_two_gpus_rccl_transport(oracle, kind):
     assert rel_err(res[1][1], l2ref) < RTOL
     for r in range(2):
         assert rel_err(core(res[r][0]), core(ref.download("state", r))) < RTOL
+    _check_components(case, ref, res[0][1], {r: res[r][0] for r in range(2)})
+    _check_records(case, ref, [res[0][2], res[1][2]], True)
     ref.close()
 
 
@@ -219,7 +291,7 @@ def _cube_worker(rank, port, overlap, solver, div, q):
     for nn in range(2):
         sol.step(nn)
     q.put((rank, {gb: sol.download("state", gb) for gb in sol.block_ids},
-           np.array([h["l2"] ** 2 for h in sol.history])))
+           np.array([h["l2"] ** 2 for h in sol.history]), [h["linf"] for h in sol.history]))
     dist.barrier()
     sol.close()
     dist.destroy_process_group()
@@ -237,8 +309,8 @@ def _cube_run(overlap, solver, div):
         p.start()
     res = {}
     for _ in range(2):
-        rank, st, l2 = q.get(timeout=300)
-        res[rank] = (st, l2)
+        rank, st, l2, linf = q.get(timeout=300)
+        res[rank] = (st, l2, linf)
     for p in procs:
         p.join(timeout=60)
         assert p.exitcode == 0
@@ -256,9 +328,7 @@ def test_dplur_interior_boundary_split(oracle, solver, div):
     split, seq = _cube_run("1", solver, div), _cube_run("0", solver, div)
     kw = dict(CUBE_KW, matrix_solver=solver)
     case = synthetic.cube_blocks_case(n=(12, 10, 9), splits=(2, 2, 2), **kw)
-    ref = Solver(oracle, case)
-    for nn in range(2):
-        ref.step(nn)
+    ref = _reference(oracle, case)
     ng = case.ng
     core = lambda a: a[ng:-ng, ng:-ng, ng:-ng]
     l2ref = np.array([h["l2"] ** 2 for h in ref.history])
@@ -267,4 +337,6 @@ def test_dplur_interior_boundary_split(oracle, solver, div):
         for gb, st in split[r][0].items():
             assert np.array_equal(core(st), core(seq[r][0][gb]))
             assert rel_err(core(st), core(ref.download("state", gb))) < RTOL
+    _check_components(case, ref, split[0][1], {**split[0][0], **split[1][0]})
+    _check_records(case, ref, [split[0][2], split[1][2]], True)
     ref.close()

@@ -10,7 +10,7 @@ import numpy as np
 import pytest
 
 from conftest import golden_case
-from parity_utils import run_pair, rel_err, RTOL
+from parity_utils import run_pair, rel_err, assert_components, RTOL
 from aither_amd.case import synthetic
 from aither_amd.solver import Solver
 
@@ -84,7 +84,9 @@ def test_uniformflow_all_orientations_parity(agx, oracle, perturb):
     case = golden_case("uniformFlow")
     if perturb:
         synthetic.perturbed_state(case, perturb)
-    sg, so = run_pair(agx, oracle, case, 3)
+    # (L-inf: the perturbation has period 1 and the ten blocks lie whole periods apart, so
+    # at step 0 the maxima of several blocks agree to round-off: one of three undecided)
+    sg, so = run_pair(agx, oracle, case, 3, linf_undecided=1 / 3)
     if not perturb:
         for gb in sg.block_ids:
             assert np.abs(sg.download("residual", gb)).max() < 1e-10 * flux_scale(case)
@@ -415,6 +417,13 @@ def test_synthetic_single_block_parity(agx, oracle, name):
     _close(*run_pair(agx, oracle, case, 3))
 
 
+# The L-inf location of stacked blocks at step 0: the blocks lie one period of
+# synthetic.perturbed_state apart, so the maxima of two blocks agree to round-off and the
+# oracle's own residual does not say which is first -- that one entry (of two or three) is
+# undecided by run_pair's margin condition; every later entry is compared.  The callers pass
+# that share: one entry of the steps they run.
+
+
 @pytest.mark.gpu
 def test_stacked_blocks_parity_blusgs(agx, oracle):
     """Block-matrix LU-SGS across interblock connections (inviscid: the ghost update
@@ -435,7 +444,7 @@ def test_stacked_blocks_parity_block_viscous(agx, oracle, solver, axis):
                                          bcs=WALL_J, equation_set="navierStokes",
                                          time_integration="implicitEuler",
                                          matrix_solver=solver, matrix_sweeps=3, cfl=10.0)
-    _close(*run_pair(agx, oracle, case, 2))
+    _close(*run_pair(agx, oracle, case, 2, linf_undecided=1 / 2))
 
 
 @pytest.mark.parametrize("axis", ["i", "j", "k"])
@@ -445,7 +454,7 @@ def test_stacked_blocks_parity_dplur(agx, oracle, axis):
         (8, 7, 6), nblocks=3, axis=axis, stretch=1.1, bcs=FARFIELD,
         inviscid_flux="ausm", limiter="none", time_integration="implicitEuler",
         matrix_solver="dplur", matrix_sweeps=4, cfl=20.0)
-    _close(*run_pair(agx, oracle, case, 3))
+    _close(*run_pair(agx, oracle, case, 3, linf_undecided=1 / 3))
 
 
 def test_stacked_blocks_parity_lusgs_weno(agx, oracle):
@@ -706,13 +715,12 @@ def test_rae2822_rans_parity(agx_rans, oracle):
     case = golden_case("rae2822")
     sg, so = run_pair(agx_rans, oracle, case, 4, fields=("state", "residual", "dt"))
     # k and omega are orders of magnitude away from the flow variables: every
-    # component against its OWN scale as well
+    # component against its OWN scale (run_pair holds state, residual and norms that way
+    # after every step; once more here on the final state)
     g = case.ng
-    a = sg.download("state", 0)[g:-g, g:-g, g:-g]
-    b = so.download("state", 0)[g:-g, g:-g, g:-g]
-    for e in range(7):
-        scale = np.abs(b[..., e]).max() or 1.0
-        assert np.abs(a[..., e] - b[..., e]).max() <= 1e-10 * scale, e
+    b = so.download("state", 0)
+    assert_components(case, "state", [sg.download("state", 0)[g:-g, g:-g, g:-g]],
+                      [b[g:-g, g:-g, g:-g]], [b])
     _close(sg, so)
 
 
@@ -744,7 +752,7 @@ def test_turbflatplate_wilcox_parity_and_truth(agx_rans, oracle):
     import json
     from conftest import GOLDEN
     case = golden_case("turbFlatPlate")
-    _close(*run_pair(agx_rans, oracle, case, 3, fields=("state", "residual", "dt")))
+    _close(*run_pair(agx_rans, oracle, case, 4, fields=("state", "residual", "dt")))
     with open(os.path.join(GOLDEN, "regression_truths.json")) as fh:
         spec = json.load(fh)["turbFlatPlate"]
     sol = Solver(agx_rans, golden_case("turbFlatPlate"))
@@ -766,7 +774,7 @@ def test_walllaw_parity_and_truth(agx_rans, oracle):
     import json
     from conftest import GOLDEN
     case = golden_case("wallLaw")
-    _close(*run_pair(agx_rans, oracle, case, 3, fields=("state", "residual", "dt")))
+    _close(*run_pair(agx_rans, oracle, case, 4, fields=("state", "residual", "dt")))
     with open(os.path.join(GOLDEN, "regression_truths.json")) as fh:
         spec = json.load(fh)["wallLaw"]
     sol = Solver(agx_rans, golden_case("wallLaw"))
@@ -1049,7 +1057,7 @@ def test_rans_stacked_blocks_parity(agx_rans, oracle, solver):
                                          turbulence_model="sst2003",
                                          time_integration="implicitEuler",
                                          matrix_solver=solver, matrix_sweeps=2, cfl=10.0)
-    _close(*run_pair(agx_rans, oracle, case, 2))
+    _close(*run_pair(agx_rans, oracle, case, 2, linf_undecided=1 / 2))
 
 
 @pytest.mark.gpu
@@ -1061,7 +1069,7 @@ def test_rans4_config_parity(agx_rans, oracle):
     import bench
     case = bench.rank_local_chain_case(0, 1, 24, "rans4")
     assert case.n_eq == 7 and len(case.blocks) == 4
-    _close(*run_pair(agx_rans, oracle, case, 2))
+    _close(*run_pair(agx_rans, oracle, case, 2, linf_undecided=1 / 2))
 
 
 @pytest.mark.gpu

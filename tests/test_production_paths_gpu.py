@@ -22,7 +22,7 @@ import numpy as np
 import pytest
 
 from conftest import GOLDEN
-from parity_utils import run_pair, rel_err, RTOL
+from parity_utils import run_pair, rel_err, assert_components, RTOL
 from aither_amd import abi
 from aither_amd.case import connections as conn_mod
 from aither_amd.case import synthetic
@@ -247,14 +247,22 @@ def test_kp_tag_wrap_under_multigrid(agx, oracle):
 
     (l2g, sg), (l2o, so), (l2r, sr) = run(agx), run(oracle), run(agx)
     g = synthetic.make_deck(**KP_WRAP_MG).num_ghost_layers()
+    fine = synthetic.multigrid_levels(**KP_WRAP_MG)[0][0]
     for nn in range(3):
         e = rel_err(l2g[nn][None, :], l2o[nn][None, :])
         print("mg l2", nn, e)
         assert e < RTOL, (nn, e)
+        # (floors: from the finest level's state at the start of the step)
+        start = [b.state for b in fine.blocks] if nn == 0 else so[nn - 1][:2]
+        assert_components(fine, "l2", l2g[nn][None, :], l2o[nn][None, :], start, (nn,))
         for a, b in zip(sg[nn], so[nn]):
             e = rel_err(a[g:-g, g:-g, g:-g], b[g:-g, g:-g, g:-g])
             print("mg state", nn, e)
             assert e < RTOL, (nn, e)
+        for lev in range(3):      # every component on its own scale, per level
+            core = lambda x: [a[g:-g, g:-g, g:-g] for a in x[2 * lev:2 * lev + 2]]
+            assert_components(fine, "state", core(sg[nn]), core(so[nn]),
+                              so[nn][2 * lev:2 * lev + 2], (nn, lev))
         for a, b in zip(sg[nn], sr[nn]):
             assert np.array_equal(a, b)
         assert np.array_equal(l2g[nn], l2r[nn])
@@ -394,7 +402,9 @@ def test_all_orientations_under_every_halo(agx, agx_rans, oracle, name):
     case = uniform_flow_case(**ORIENT_DECKS[name])
     assert sorted({c.orientation for c in case.connections}) == list(range(1, 9))
     lib = agx_rans if case.n_eq == 7 else agx
-    _pair(lib, oracle, case, 2)
+    # (L-inf: the ten blocks lie whole periods of the perturbation apart; at step 0 the
+    # maxima of several blocks agree to round-off -- one entry of two is undecided)
+    _pair(lib, oracle, case, 2, linf_undecided=1 / 2)
 
 
 @pytest.mark.parametrize("what,field", [(abi.HALO_STATE, "state"), (abi.HALO_UPDATE, "update")])

@@ -24,7 +24,7 @@ from aither_amd.case import fluid, synthetic
 from aither_amd.case.builder import build_case, config_struct
 from aither_amd.case.inputfile import parse_input
 from aither_amd.solver import MultigridSolver, Solver
-from parity_utils import RTOL, flux_scale, rel_err, run_pair
+from parity_utils import RTOL, assert_components, flux_scale, rel_err, run_pair
 import tp_cases
 
 pytestmark = pytest.mark.gpu
@@ -187,12 +187,22 @@ def _pair(n_eq, make, steps=3, outputs=False):
                     st.upload(f, gb, sc.download(f, gb))
                 sc.upload("state", gb, sc.download("state", gb))
             st.l2_first = None if sc.l2_first is None else sc.l2_first.copy()
+        # (the floors of the norms and the residual: from the state the step starts with)
+        start = [sc.download("state", gb) for gb in sc.block_ids]
         sc.step(nn), st.step(nn)
         assert len(sc.history) == len(st.history)
+        ref = [sc.download("state", gb) for gb in sc.block_ids]
         for hc, ht in zip(sc.history[nh:], st.history[nh:]):
             e = rel_err(ht["l2"][None, :], hc["l2"][None, :], nfloor)
             assert e < RTOL, ("L2", nn, e)
+            assert_components(c_cp, "l2", ht["l2"][None, :], hc["l2"][None, :], start, (nn,))
         nh = len(sc.history)
+        # every component on its own scale (parity_utils.component_err), over all blocks
+        core = lambda x: x[ng:-ng, ng:-ng, ng:-ng]
+        assert_components(c_cp, "state", [core(st.download("state", gb)) for gb in sc.block_ids],
+                          [core(x) for x in ref], ref, (nn,))
+        assert_components(c_cp, "residual", [st.download("residual", gb) for gb in sc.block_ids],
+                          [sc.download("residual", gb) for gb in sc.block_ids], start, (nn,))
         for gb in sc.block_ids:
             for f in ("state", "residual", "dt"):
                 a, b = st.download(f, gb), sc.download(f, gb)
@@ -307,8 +317,13 @@ def _report(name, sg, so, case):
     print("TP-PARITY", name, " ".join(f"{k}={v:.2e}" for k, v in worst.items()))
 
 
-def _run(name, n_eq, oracle, case, steps=3):
-    sg, so = run_pair(aither_amd.load(n_eq, TP), oracle, case, steps)
+# (stacked blocks lie one period of the perturbation apart: at step 0 the maxima of the two
+# blocks agree to round-off, the L-inf location of that entry -- one of two -- is undecided)
+STACKED_UNDECIDED = 1 / 2
+
+
+def _run(name, n_eq, oracle, case, steps=3, **kw):
+    sg, so = run_pair(aither_amd.load(n_eq, TP), oracle, case, steps, **kw)
     _report(name, sg, so, case)
     sg.close(), so.close()
 
@@ -346,11 +361,13 @@ def test_tp_wall_law_parity(oracle, tag, solver):
 
 
 def test_tp_stacked_blocks_parity_five(oracle):
-    _run("stacked_blusgs_visc", 5, oracle, tp_cases.stacked_five(), steps=2)
+    _run("stacked_blusgs_visc", 5, oracle, tp_cases.stacked_five(), steps=2,
+         linf_undecided=STACKED_UNDECIDED)
 
 
 def test_tp_stacked_blocks_parity_rans(oracle):
-    _run("stacked_rans_lusgs", 7, oracle, tp_cases.stacked_rans(), steps=2)
+    _run("stacked_rans_lusgs", 7, oracle, tp_cases.stacked_rans(), steps=2,
+         linf_undecided=STACKED_UNDECIDED)
 
 
 def _multigrid(n_eq, oracle, make, matrix_rtol, update_by_largest):
