@@ -7,6 +7,7 @@
 // path here: every entry point fails loudly if HIP is unavailable.
 #include "agx_kernels.hpp"
 #include "agx_geometry.hpp"
+#include "agx_mem.hpp"
 #include <rccl/rccl.h>
 #include <cstdarg>
 #include <cstdio>
@@ -46,33 +47,46 @@ static int fail(const char* fmt, ...) {
 
 namespace {
 
+// The sweep graphs of one block, or of all blocks in one launch: a slot per direction,
+// triangle set and value of un_is_u.  They hold the BlockDev they were captured with.
+struct SweepGraphs {
+  hipGraphExec_t g[2][2][2] = {};
+  SweepGraphs() = default;
+  SweepGraphs(SweepGraphs&& o) noexcept { memcpy(g, o.g, sizeof g); memset(o.g, 0, sizeof g); }
+  ~SweepGraphs() { drop(); }
+  hipGraphExec_t& at(bool forward, bool full, bool un_is_u) { return g[forward][full][un_is_u]; }
+  void drop() {
+    for (auto& g1 : g) for (auto& g2 : g1) for (auto& g3 : g2)
+      if (g3) { hipGraphExecDestroy(g3); g3 = nullptr; }
+  }
+};
+
+// Block, Conn and agx_ctx own their device and pinned memory through DevBuf / PinnedBuf
+// (agx_mem.hpp); BlockDev and HaloSide are views of it that travel to the kernels
 struct Block {
   BlockDev d;
   int global_pos = 0;
-  double* slab = nullptr;
-  double* d2 = nullptr;       // D2 arrays of the LU-SGS path (agx_lusgs.hpp)
-  double* blockmat = nullptr; // block-matrix solvers: a_ | aInv_ | velocityGrad_ planes
-  double* sweep_rec = nullptr; // plane-by-plane sweeps: geo | dyn | rhs records (k_sweep_records)
+  DevBuf<double> slab;
+  DevBuf<double> d2;          // D2 arrays of the LU-SGS path (agx_lusgs.hpp)
+  DevBuf<double> blockmat;    // block-matrix solvers: a_ | aInv_ | velocityGrad_ planes
+  DevBuf<double> sweep_rec;   // plane-by-plane sweeps: geo | dyn | rhs records (k_sweep_records)
   bool sweep_geo_built = false; // the (static) geometry records exist
   bool x_planes_current = false; // D2 path: the planes of x equal the D2 arrays (multigrid calls)
   // multigrid: forcing | matrix residual | saved update planes (each allocated on first
   // use); the transfer maps of this block as the FINE side (device copies, keyed by the
   // host pointers they were uploaded from); node values of this block as the coarse side
-  double *mg_forcing = nullptr, *mg_mres = nullptr, *mg_xsave = nullptr, *mg_nodes = nullptr;
-  int* mg_tc = nullptr;
-  int* mg_start = nullptr;
-  double *mg_vf = nullptr, *mg_cf = nullptr;
+  DevBuf<double> mg_forcing, mg_mres, mg_xsave, mg_nodes;
+  DevBuf<int> mg_tc, mg_start;
+  DevBuf<double> mg_vf, mg_cf;
   const void *mg_tc_key = nullptr, *mg_vf_key = nullptr, *mg_cf_key = nullptr;
   // node-built blocks (agx_block_geom.nodes): the node coordinates and the face-centre
   // planes, both on the device until agx_setup_finalize has completed the geometry
   bool node_built = false;
-  double* nodes_dev = nullptr;
-  double* fcen = nullptr;
-  int* d2_tab = nullptr;      // device: dstart[Pi + Pj] | ij_of_pos[Pi * Pj]
+  DevBuf<double> nodes_dev, fcen;
+  DevBuf<int> d2_tab;         // device: dstart[Pi + Pj] | ij_of_pos[Pi * Pj]
   std::vector<int> dstart;    // host copy (halo index maps)
-  // hyperplane-per-launch sweeps captured as graphs: [forward][both triangles][un_is_u]
-  hipGraphExec_t sweep_graph[2][2][2] = {};
-  int* kp_mem = nullptr;      // k_lusgs_kp: ticket counter
+  SweepGraphs sweep_graph;    // hyperplane-per-launch sweeps captured as graphs
+  DevBuf<int> kp_mem;         // k_lusgs_kp: ticket counter
   unsigned kp_epoch = 0;      // writer launches of the D2 x so far (its low bits tag the values)
   // D2 index of padded cell (i, j, k), host side
   long d2idx(int i, int j, int k) const {
@@ -80,37 +94,35 @@ struct Block {
     return (long)(k + d.ng) * d.d2.ps + dstart[de] + je - std::max(0, de - (d.d2.Pi - 1));
   }
   bool state_is_a = true;
-  agx_bc_surface* surf_dev = nullptr;
+  DevBuf<agx_bc_surface> surf_dev;
   std::vector<agx_bc_surface> surf_host;
   // nonreflecting inlet / outlet surfaces: offsets | gradients | Mach (BlockDev)
-  int* nr_off_dev = nullptr;
-  double* nr_mem = nullptr;
+  DevBuf<int> nr_off_dev;
+  DevBuf<double> nr_mem;
   long nr_max = 0;            // cells of the largest such surface (0: none)
   // wall-law surfaces (rans): offsets | wallData_ of their faces (BlockDev)
-  int* wall_off_dev = nullptr;
-  double* wall_mem = nullptr;
+  DevBuf<int> wall_off_dev;
+  DevBuf<WallVars> wall_mem;
   // viscousWall surfaces in the order given (the order of wallData_): what k_wall_pack
   // walks, and the faces of all of them
   std::vector<WallSurfDev> wall_tab;
-  WallSurfDev* wall_tab_dev = nullptr;
+  DevBuf<WallSurfDev> wall_tab_dev;
   long wall_faces = 0;
 };
 
 struct ConnSide {          // what side s receives / sends
   std::vector<long> h_dst, h_src;   // host copies (SoA index space) until agx_setup_finalize is done
   long n = 0;              // cells inserted into side s
-  long* dst = nullptr;     // device: ghost cells of side s (this rank's block)
-  long* src = nullptr;     // device: partner cells that fill them
-  long* dst2 = nullptr;    // the same cells in D2 index space (x of the LU-SGS path)
-  long* src2 = nullptr;
+  // device, per index space (0: SoA planes, 1: the D2 arrays, x of the LU-SGS path;
+  // halo_in_d2): ghost cells of side s (this rank's block) and the partner cells that fill them
+  struct { DevBuf<long> dst, src; } map[2];
 };
 struct Conn {
   agx_connection c;
   ConnSide side[2];
   // for remote connections: cells of MY block that the partner's ghosts read
   long n_send = 0;
-  long* send_src = nullptr;
-  long* send_src2 = nullptr;
+  DevBuf<long> send_src[2];   // per index space, as ConnSide::map
 };
 
 // timing groups of agx_timing_get (include/aither_gfx950.h)
@@ -132,27 +144,25 @@ struct agx_ctx {
   // connection, and the norm records of all ranks
   agx_exchange ex = {};
   bool have_ex = false;
-  struct Remote { int cid; long count; double *send = nullptr, *recv = nullptr;
-                  double *hsend = nullptr, *hrecv = nullptr; };
+  struct Remote { int cid; long count; DevBuf<double> send, recv;
+                  PinnedBuf<double> hsend, hrecv; };
   std::vector<Remote> remote;
   std::vector<agx_slab> slabs;
   struct NormRecord { double l2[8]; double mres, linf; int32_t block, i, j, k, eqn, status;
                       double fill[3]; };     // 128 bytes
-  NormRecord* rec_dev = nullptr;        // [1 + nranks] device (RCCL)
-  NormRecord* rec_host = nullptr;       // [1 + nranks] pinned
+  DevBuf<NormRecord> rec_dev;           // [1 + nranks] (RCCL)
+  PinnedBuf<NormRecord> rec_host;       // [1 + nranks]
   ncclComm_t nccl = nullptr;
-  NormPartial* partials = nullptr;
+  DevBuf<NormPartial> partials;
   long n_partials = 0;
-  NormPartial* norm_out = nullptr;      // device, one per block
-  NormPartial* norm_host = nullptr;     // pinned
-  int* err_dev = nullptr;
-  int* err_host = nullptr;              // pinned
-  double* halo_buf = nullptr;
-  long halo_cap = 0;
-  double* stage_buf = nullptr;   // AoS staging of uploads / downloads (stage_buffer)
-  size_t stage_cap = 0;
-  double* rans_rec = nullptr;    // face records of the rans viscous residual (k_rans_faces),
-  size_t rans_rec_cap = 0;       // sized for the largest block, shared by all of them
+  DevBuf<NormPartial> norm_out;         // one per block
+  PinnedBuf<NormPartial> norm_host;
+  DevBuf<int> err_dev;
+  PinnedBuf<int> err_host;
+  DevBuf<double> halo_buf;
+  DevBuf<double> stage_buf;      // AoS staging of uploads / downloads (stage_buffer)
+  DevBuf<double> rans_rec;       // face records of the rans viscous residual (k_rans_faces),
+                                 // sized for the largest block, shared by all of them
   bool use_gather = false;   // AGX_KERNEL=gather: one-thread-per-cell gather kernel
   bool use_tile = true;      // AGX_KERNEL=tile (default) | march
   int num_cu = 256;          // persistent workgroups of the tile kernel
@@ -182,18 +192,17 @@ struct agx_ctx {
   // table of their BlockDev in device memory, one graph per direction / triangle set /
   // un_is_u (AGX_SWEEP_ALL=0: the branch streams)
   bool sweep_all_launch = true;
-  BlockDev* blocks_tab = nullptr;        // device
-  BlockDev* blocks_tab_host = nullptr;   // pinned
-  size_t blocks_tab_n = 0;
-  hipGraphExec_t sweep_graph_all[2][2][2] = {};
+  DevBuf<BlockDev> blocks_tab;
+  PinnedBuf<BlockDev> blocks_tab_host;
+  SweepGraphs sweep_graph_all;
   // the pipelined half sweep (k_lusgs_pipe): a workgroup per k-plane of every block
   bool mg_coarse = false;                // a coarse multigrid level (agx_mg_restrict made it one)
   bool mres_plane_form = false;          // agx_mg_matrix_residual: k_matrix_resid on every block
   bool sweep_pipe = true;                // AGX_SWEEP_PIPE=0: one launch per hyperplane
-  PipeJob* pipe_jobs[2] = {nullptr, nullptr};   // device: pipeline order back / forward
-  int* pipe_slot0 = nullptr;             // device
-  long long* pipe_progress = nullptr;    // device, 16 words per plane
-  unsigned long long* pipe_ticket = nullptr;
+  DevBuf<PipeJob> pipe_jobs[2];          // pipeline order back / forward
+  DevBuf<int> pipe_slot0;
+  DevBuf<long long> pipe_progress;       // 16 words per plane
+  DevBuf<unsigned long long> pipe_ticket;
   size_t pipe_nblocks = 0;
   int pipe_njobs = 0, pipe_maxsteps = 0, pipe_waves = 4;
   long long pipe_launches = 0;
@@ -211,10 +220,10 @@ struct agx_ctx {
   std::vector<HaloLevel> halo_levels;
   // the state (fused explicit stages) and x (DPLUR) alternate between two sets of planes:
   // one table pair per set, built once each
-  HaloSide* halo_tab_dev[5][2][2] = {};   // [what][plane set][gather | scatter]
+  DevBuf<HaloSide> halo_tab_dev[5][2][2];   // [what][plane set][gather | scatter]
   bool halo_tab_valid[5][2] = {};
   int halo_set[5] = {};
-  HaloSide* halo_tab_host = nullptr;      // pinned staging, 2 * sides entries
+  PinnedBuf<HaloSide> halo_tab_host;      // staging, 2 * sides entries
   int mresid_split = 1;      // bands of diagonals per XCD in k_matrix_resid_d2 (AGX_MRESID_SPLIT)
   bool mresid_march = true;  // AGX_MRESID=plane: one plane position per thread (comparison form)
   bool have_time_n = false;  // agx_store_time_n has run (nonreflecting BCs read consVarsN)
@@ -323,16 +332,13 @@ Planes5 planes(double* const* p, int n = AGX_NEQ) {
 
 // upload an AoS host array (dims (ci,cj,ck) incl. gsrc ghosts, ncomp per cell)
 // device staging of the AoS <-> SoA conversions: one buffer per context that only grows
-// (an output step downloads a dozen fields per block; no hipMalloc / hipFree per call)
+// (an output step downloads a dozen fields per block; no allocation per call)
 static int stage_buffer(agx_ctx* c, size_t doubles, double** out) {
-  if (doubles > c->stage_cap) {
-    HIPCHK(hipStreamSynchronize(c->stream));
-    if (c->stage_buf) HIPCHK(hipFree(c->stage_buf));
-    c->stage_buf = nullptr; c->stage_cap = 0;
-    HIPCHK(hipMalloc((void**)&c->stage_buf, sizeof(double) * doubles));
-    c->stage_cap = doubles;
+  if (doubles > c->stage_buf.size()) {
+    HIPCHK(hipStreamSynchronize(c->stream));     // (before the old one is freed)
+    HIPCHK(c->stage_buf.alloc(doubles));
   }
-  *out = c->stage_buf;
+  *out = c->stage_buf.get();
   return 0;
 }
 // the tail of a call that hands a payload out: the launches' error, n doubles to the host,
@@ -435,26 +441,17 @@ void build_side_map(const agx_connection& cc, int recv, int ng, FR idxR, FS idxS
       }
 }
 
-int to_device(const std::vector<long>& v, long** out) {
-  *out = nullptr;
-  if (v.empty()) return 0;
-  HIPCHK(hipMalloc((void**)out, sizeof(long) * v.size()));
-  HIPCHK(hipMemcpy(*out, v.data(), sizeof(long) * v.size(), hipMemcpyHostToDevice));
-  return 0;
-}
-
 int ensure_halo_buf(agx_ctx* c, long ndoubles) {
-  if (ndoubles <= c->halo_cap) return 0;
-  if (c->halo_buf) HIPCHK(hipFree(c->halo_buf));
-  HIPCHK(hipMalloc((void**)&c->halo_buf, sizeof(double) * ndoubles));
-  c->halo_cap = ndoubles;
-  for (auto& v : c->halo_tab_valid) v[0] = v[1] = false;   // (the tables hold slices of this buffer)
+  bool grew;
+  HIPCHK(c->halo_buf.reserve((size_t)ndoubles, &grew));
+  if (grew)   // (the tables hold slices of this buffer)
+    for (auto& v : c->halo_tab_valid) v[0] = v[1] = false;
   return 0;
 }
 
 // what a halo exchange moves: the state planes, or x -- which the D2 LU-SGS path
-// keeps in its own arrays and index space (maps dst2 / src2)
-bool halo_in_d2(const Block& b, int what) { return what == AGX_HALO_UPDATE && b.d.d2.base; }
+// keeps in its own arrays and index space (1; 0: the planes -- the index of ConnSide::map)
+int halo_in_d2(const Block& b, int what) { return what == AGX_HALO_UPDATE && b.d.d2.base ? 1 : 0; }
 // something is about to write x where it lives (the D2 arrays on the diagonal-ordered path)
 void x_changed(agx_ctx* c) {
   for (auto& blk : c->blocks) blk.x_planes_current = false;
@@ -463,7 +460,7 @@ Planes5 halo_planes(Block& b, int what) {
   Planes5 r;
   // (the scatter of an exchange of x also refreshes the sweep records' copy)
   r.rec = what == AGX_HALO_UPDATE ? b.d.sw_dyn : nullptr;
-  const bool z2 = halo_in_d2(b, what);
+  const bool z2 = halo_in_d2(b, what) != 0;
   r.stride = z2 ? 2 : 1;     // x of the D2 path sits in pair arrays (x0,x1) (x2,x3) (x4,-)
 #if AGX_NEQ == 7
   if (what == AGX_HALO_TURB) {     // eddyViscosity_, f1_, f2_ in the first three slots
@@ -487,10 +484,11 @@ Planes5 halo_planes(Block& b, int what) {
 }
 
 int check_device_error(agx_ctx* c) {
-  if (*c->err_host) {
-    const int code = *c->err_host;
-    *c->err_host = 0;
-    hipMemsetAsync(c->err_dev, 0, sizeof(int), c->stream);
+  int* const err_host = c->err_host.get();
+  if (*err_host) {
+    const int code = *err_host;
+    *err_host = 0;
+    hipMemsetAsync(c->err_dev.get(), 0, sizeof(int), c->stream);
     if (code == 3)
       return fail("Singular matrix in Gauss-Jordan elimination!");   // matrix.cpp:81
     if (code == AGX_ERR_TPG_ENERGY)
@@ -665,12 +663,12 @@ template <bool FWD, bool FULL, bool CONN, int CH>
 int lusgs_kp_launch(agx_ctx* c, Block& blk) {
   const BlockDev& b = blk.d;
   if (!blk.kp_mem) {                      // the ticket counter
-    HIPCHK(hipMalloc((void**)&blk.kp_mem, sizeof(int) * 32));
-    HIPCHK(hipMemsetAsync(blk.kp_mem, 0, sizeof(int) * 32, c->stream));
+    HIPCHK(blk.kp_mem.alloc(32));
+    HIPCHK(hipMemsetAsync(blk.kp_mem.get(), 0, sizeof(int) * 32, c->stream));
   }
   KpArgs kp;
-  kp.ticket = blk.kp_mem;
-  kp.err = c->err_dev;
+  kp.ticket = blk.kp_mem.get();
+  kp.err = c->err_dev.get();
   // the launch's tag of the values it stores (agx_lusgs_kernels.hpp: KpArgs); every
   // writer of x advances the block's epoch
   kp.tag = (unsigned)(++blk.kp_epoch) & 3u;
@@ -779,35 +777,45 @@ static bool plane_sweep_all_applicable(const agx_ctx* c) {
   return true;
 }
 int lusgs_sweep(agx_ctx* c, Block& blk, bool forward, int full, hipStream_t st = nullptr);
-static void drop_sweep_graphs_all(agx_ctx* c) {
-  for (auto& g1 : c->sweep_graph_all) for (auto& g2 : g1) for (auto& g3 : g2)
-    if (g3) { hipGraphExecDestroy(g3); g3 = nullptr; }
+// The launches of a half sweep are the same every iteration: captured once into the slot's
+// hipGraph, replayed on st.  (Recorded on a stream of its own: the library's stream may be
+// the legacy default stream, which cannot capture; a graph is launched on any stream.)
+template <class F>
+static int replay_captured(agx_ctx* c, hipGraphExec_t& ge, F launch_all, hipStream_t st) {
+  if (!ge) {
+    if (!c->cap_stream) HIPCHK(hipStreamCreateWithFlags(&c->cap_stream, hipStreamNonBlocking));
+    hipGraph_t graph = nullptr;
+    HIPCHK(hipStreamBeginCapture(c->cap_stream, hipStreamCaptureModeThreadLocal));
+    launch_all(c->cap_stream);
+    HIPCHK(hipStreamEndCapture(c->cap_stream, &graph));
+    HIPCHK(hipGraphInstantiate(&ge, graph, nullptr, nullptr, 0));
+    HIPCHK(hipGraphDestroy(graph));
+  }
+  HIPCHK(hipGraphLaunch(ge, st));
+  return 0;
 }
 // the device copy of the blocks' descriptors, for kernels that serve all blocks in one launch
 static int sync_blocks_tab(agx_ctx* c) {
   const size_t nb = c->blocks.size();
-  if (c->blocks_tab && c->blocks_tab_n != nb) {      // (blocks were added since)
+  if (c->blocks_tab && c->blocks_tab.size() != nb) {   // (blocks were added since)
     HIPCHK(hipStreamSynchronize(c->stream));
-    HIPCHK(hipFree(c->blocks_tab));
-    HIPCHK(hipHostFree(c->blocks_tab_host));
-    c->blocks_tab = nullptr; c->blocks_tab_host = nullptr;
-    drop_sweep_graphs_all(c);                        // (their grids cover nb blocks)
+    c->sweep_graph_all.drop();                       // (their grids cover nb blocks)
   }
-  if (!c->blocks_tab) {
-    HIPCHK(hipMalloc((void**)&c->blocks_tab, sizeof(BlockDev) * nb));
-    HIPCHK(hipHostMalloc((void**)&c->blocks_tab_host, sizeof(BlockDev) * nb));
-    memset(c->blocks_tab_host, 0, sizeof(BlockDev) * nb);
-    c->blocks_tab_n = nb;
+  if (c->blocks_tab.size() != nb) {
+    HIPCHK(c->blocks_tab.alloc(nb));
+    HIPCHK(c->blocks_tab_host.alloc(nb));
+    memset(c->blocks_tab_host.get(), 0, sizeof(BlockDev) * nb);
   }
+  BlockDev* const host = c->blocks_tab_host.get();
   // the table follows the blocks (pointers that change roles, new surfaces): if it
   // differs from what the device holds, upload it
   bool same = true;
   for (size_t n = 0; n < nb; ++n)
-    same = same && memcmp(&c->blocks_tab_host[n], &c->blocks[n].d, sizeof(BlockDev)) == 0;
+    same = same && memcmp(&host[n], &c->blocks[n].d, sizeof(BlockDev)) == 0;
   if (!same) {
     HIPCHK(hipStreamSynchronize(c->stream));      // (nobody reads the pinned copy any more)
-    for (size_t n = 0; n < nb; ++n) memcpy(&c->blocks_tab_host[n], &c->blocks[n].d, sizeof(BlockDev));
-    HIPCHK(hipMemcpyAsync(c->blocks_tab, c->blocks_tab_host, sizeof(BlockDev) * nb,
+    for (size_t n = 0; n < nb; ++n) memcpy(&host[n], &c->blocks[n].d, sizeof(BlockDev));
+    HIPCHK(hipMemcpyAsync(c->blocks_tab.get(), host, sizeof(BlockDev) * nb,
                           hipMemcpyHostToDevice, c->stream));
   }
   return 0;
@@ -821,18 +829,10 @@ static bool pipe_sweep_applicable(const agx_ctx* c) {
     if (blk.d.d2.base || !blk.d.sw_geo) return false;
   return true;
 }
-static void pipe_free(agx_ctx* c) {
-  for (auto& p : c->pipe_jobs) { if (p) hipFree(p); p = nullptr; }
-  if (c->pipe_slot0) hipFree(c->pipe_slot0);
-  if (c->pipe_progress) hipFree(c->pipe_progress);
-  if (c->pipe_ticket) hipFree(c->pipe_ticket);
-  c->pipe_slot0 = nullptr; c->pipe_progress = nullptr; c->pipe_ticket = nullptr;
-  c->pipe_nblocks = 0; c->pipe_njobs = 0; c->pipe_launches = 0;
-}
 static int pipe_setup(agx_ctx* c) {
   const size_t nb = c->blocks.size();
   HIPCHK(hipStreamSynchronize(c->stream));
-  pipe_free(c);
+  c->pipe_nblocks = 0; c->pipe_njobs = 0; c->pipe_launches = 0;
   // pipeline order: plane k of every block before plane k + 1 of any (going back: from the top)
   std::vector<PipeJob> fwd, bwd;
   std::vector<int> slot0(nb);
@@ -853,17 +853,12 @@ static int pipe_setup(agx_ctx* c) {
     }
   c->pipe_njobs = (int)fwd.size();
   c->pipe_waves = std::max(1, std::min(8, (diag + PL3_CELLS - 1) / PL3_CELLS));
-  for (int dir = 0; dir < 2; ++dir) {
-    HIPCHK(hipMalloc((void**)&c->pipe_jobs[dir], sizeof(PipeJob) * fwd.size()));
-    HIPCHK(hipMemcpy(c->pipe_jobs[dir], (dir ? fwd : bwd).data(), sizeof(PipeJob) * fwd.size(),
-                     hipMemcpyHostToDevice));
-  }
-  HIPCHK(hipMalloc((void**)&c->pipe_slot0, sizeof(int) * nb));
-  HIPCHK(hipMemcpy(c->pipe_slot0, slot0.data(), sizeof(int) * nb, hipMemcpyHostToDevice));
-  HIPCHK(hipMalloc((void**)&c->pipe_progress, sizeof(long long) * 16 * slots));
-  HIPCHK(hipMemset(c->pipe_progress, 0, sizeof(long long) * 16 * slots));
-  HIPCHK(hipMalloc((void**)&c->pipe_ticket, 128));
-  HIPCHK(hipMemset(c->pipe_ticket, 0, 128));
+  for (int dir = 0; dir < 2; ++dir) HIPCHK(c->pipe_jobs[dir].upload(dir ? fwd : bwd));
+  HIPCHK(c->pipe_slot0.upload(slot0));
+  HIPCHK(c->pipe_progress.alloc((size_t)16 * slots));
+  HIPCHK(hipMemset(c->pipe_progress.get(), 0, sizeof(long long) * 16 * slots));
+  HIPCHK(c->pipe_ticket.alloc(16));           // (a 128-byte line of its own)
+  HIPCHK(hipMemset(c->pipe_ticket.get(), 0, 128));
   c->pipe_nblocks = nb;
   return 0;
 }
@@ -878,15 +873,15 @@ static int lusgs_sweep_pipe(agx_ctx* c, bool forward, int full) {
   if (!same && pipe_setup(c)) return 1;
   if (sync_blocks_tab(c)) return 1;
   PipeArgs pa;
-  pa.jobs = c->pipe_jobs[forward ? 1 : 0];
-  pa.slot0 = c->pipe_slot0;
-  pa.progress = c->pipe_progress;
-  pa.ticket = c->pipe_ticket;
+  pa.jobs = c->pipe_jobs[forward ? 1 : 0].get();
+  pa.slot0 = c->pipe_slot0.get();
+  pa.progress = c->pipe_progress.get();
+  pa.ticket = c->pipe_ticket.get();
   pa.base = c->pipe_launches * (long long)(c->pipe_maxsteps + 1);
   pa.tbase = (unsigned long long)c->pipe_launches * (unsigned long long)c->pipe_njobs;
   pa.njobs = c->pipe_njobs;
   pa.spin_limit = c->spin_limit;
-  pa.err = c->err_dev;
+  pa.err = c->err_dev.get();
   pa.trace = nullptr;
 #ifdef AGX_PIPE_TRACE
   static long long* trace_dev = nullptr;
@@ -901,9 +896,9 @@ static int lusgs_sweep_pipe(agx_ctx* c, bool forward, int full) {
   const dim3 grid((unsigned)c->pipe_njobs);
   const dim3 tb(64, c->pipe_waves);
   if (forward)
-    hipLaunchKernelGGL((k_lusgs_pipe<true>), grid, tb, 0, c->stream, c->blocks_tab, c->gas, c->sp, full, pa);
+    hipLaunchKernelGGL((k_lusgs_pipe<true>), grid, tb, 0, c->stream, c->blocks_tab.get(), c->gas, c->sp, full, pa);
   else
-    hipLaunchKernelGGL((k_lusgs_pipe<false>), grid, tb, 0, c->stream, c->blocks_tab, c->gas, c->sp, full, pa);
+    hipLaunchKernelGGL((k_lusgs_pipe<false>), grid, tb, 0, c->stream, c->blocks_tab.get(), c->gas, c->sp, full, pa);
   HIPCHK(hipGetLastError());
 #ifdef AGX_PIPE_TRACE
   if (pa.trace) {   // diagnostic build only: dump the step timestamps of this launch
@@ -934,33 +929,24 @@ static int lusgs_sweep_all_one_launch(agx_ctx* c, bool forward, int full) {
     gy = std::max(gy, (unsigned)(blk.d.nk + 3) / 4);
   }
   const dim3 tb(64, 4), grid(gx, gy, (unsigned)nb);
+  const BlockDev* const tab = c->blocks_tab.get();
   auto launch_all = [&](hipStream_t st) {
     for (int t = 0; t < steps; ++t) {
       if (three) {
         if (forward)
-          hipLaunchKernelGGL((k_lusgs_plane_all3<true>), grid, tb, 0, st, c->blocks_tab, c->gas, c->sp, t, full);
+          hipLaunchKernelGGL((k_lusgs_plane_all3<true>), grid, tb, 0, st, tab, c->gas, c->sp, t, full);
         else
-          hipLaunchKernelGGL((k_lusgs_plane_all3<false>), grid, tb, 0, st, c->blocks_tab, c->gas, c->sp, t, full);
+          hipLaunchKernelGGL((k_lusgs_plane_all3<false>), grid, tb, 0, st, tab, c->gas, c->sp, t, full);
         continue;
       }
       if (forward)
-        hipLaunchKernelGGL((k_lusgs_plane_all<true>), grid, tb, 0, st, c->blocks_tab, c->gas, c->sp, t, full);
+        hipLaunchKernelGGL((k_lusgs_plane_all<true>), grid, tb, 0, st, tab, c->gas, c->sp, t, full);
       else
-        hipLaunchKernelGGL((k_lusgs_plane_all<false>), grid, tb, 0, st, c->blocks_tab, c->gas, c->sp, t, full);
+        hipLaunchKernelGGL((k_lusgs_plane_all<false>), grid, tb, 0, st, tab, c->gas, c->sp, t, full);
     }
   };
-  hipGraphExec_t& ge = c->sweep_graph_all[forward ? 1 : 0][full ? 1 : 0][c->sp.un_is_u ? 1 : 0];
-  if (!ge) {
-    if (!c->cap_stream) HIPCHK(hipStreamCreateWithFlags(&c->cap_stream, hipStreamNonBlocking));
-    hipGraph_t graph = nullptr;
-    HIPCHK(hipStreamBeginCapture(c->cap_stream, hipStreamCaptureModeThreadLocal));
-    launch_all(c->cap_stream);
-    HIPCHK(hipStreamEndCapture(c->cap_stream, &graph));
-    HIPCHK(hipGraphInstantiate(&ge, graph, nullptr, nullptr, 0));
-    HIPCHK(hipGraphDestroy(graph));
-  }
-  HIPCHK(hipGraphLaunch(ge, c->stream));
-  return 0;
+  return replay_captured(c, c->sweep_graph_all.at(forward, full != 0, c->sp.un_is_u != 0),
+                         launch_all, c->stream);
 }
 static int lusgs_sweep_all(agx_ctx* c, bool forward, int full) {
   if (c->sweep_all_launch) return lusgs_sweep_all_one_launch(c, forward, full);
@@ -994,29 +980,16 @@ int lusgs_sweep(agx_ctx* c, Block& blk, bool forward, int full, hipStream_t st) 
   if (!st) st = c->stream;
   if (!b.d2.base) {
     // One launch per hyperplane i + j + k = p: ni + nj + nk - 2 short launches per half
-    // sweep, bound by launch latency.  The sequence is the same every iteration, so it is
-    // captured once into a hipGraph (per direction / triangle set / value of un_is_u, the
-    // one solver parameter that changes between iterations) and replayed.
+    // sweep, bound by launch latency: replayed as a graph (per direction / triangle set /
+    // value of un_is_u, the one solver parameter that changes between iterations).
     const int nplanes = b.ni + b.nj + b.nk - 2;
     auto launch_all = [&](hipStream_t st) { launch_plane_sweep(c, b, forward, full, st); };
     if (!c->use_graphs || nplanes < 8) {
       launch_all(st);
       return 0;
     }
-    hipGraphExec_t& ge = blk.sweep_graph[forward ? 1 : 0][full ? 1 : 0][c->sp.un_is_u ? 1 : 0];
-    if (!ge) {
-      // (recorded on a stream of its own: the library's stream may be the legacy default
-      // stream, which cannot capture; a graph is launched on any stream)
-      if (!c->cap_stream) HIPCHK(hipStreamCreateWithFlags(&c->cap_stream, hipStreamNonBlocking));
-      hipGraph_t graph = nullptr;
-      HIPCHK(hipStreamBeginCapture(c->cap_stream, hipStreamCaptureModeThreadLocal));
-      launch_all(c->cap_stream);
-      HIPCHK(hipStreamEndCapture(c->cap_stream, &graph));
-      HIPCHK(hipGraphInstantiate(&ge, graph, nullptr, nullptr, 0));
-      HIPCHK(hipGraphDestroy(graph));
-    }
-    HIPCHK(hipGraphLaunch(ge, st));
-    return 0;
+    return replay_captured(c, blk.sweep_graph.at(forward, full != 0, c->sp.un_is_u != 0),
+                           launch_all, st);
   }
 #if AGX_FAST
   return forward ? lusgs_kp_variant<true>(c, blk, full) : lusgs_kp_variant<false>(c, blk, full);
@@ -1059,11 +1032,11 @@ int bc_pass(agx_ctx* c, bool faces, int viscous) {
       }
       if (nmax > 0)
         hipLaunchKernelGGL(k_bc_faces, dim3((nmax + 255) / 256, b.nsurf), dim3(256), 0,
-                           c->stream, b, c->gas, viscous, c->err_dev);
+                           c->stream, b, c->gas, viscous, c->err_dev.get());
     } else {
       const long n = 4L * (b.ni + b.nj + b.nk);
       hipLaunchKernelGGL(k_bc_edges, dim3((n + 127) / 128), dim3(128), 0,
-                         c->stream, b, c->gas, viscous, c->err_dev);
+                         c->stream, b, c->gas, viscous, c->err_dev.get());
     }
   }
   HIPCHK(hipGetLastError());
@@ -1071,15 +1044,15 @@ int bc_pass(agx_ctx* c, bool faces, int viscous) {
 }
 
 int reduce_norms(agx_ctx* c, size_t blk_index, long nparts, NormPartial* out = nullptr) {
-  if (!out) out = c->norm_out + blk_index;
+  if (!out) out = c->norm_out.get() + blk_index;
   if (nparts > 4096) {
     // two levels: 64 workgroups fold slices into the scratch behind norm_out
-    NormPartial* tmp = c->norm_out + c->blocks.size();
-    hipLaunchKernelGGL(k_norm_final, dim3(64), dim3(256), 0, c->stream, c->partials, nparts, tmp);
+    NormPartial* tmp = c->norm_out.get() + c->blocks.size();
+    hipLaunchKernelGGL(k_norm_final, dim3(64), dim3(256), 0, c->stream, c->partials.get(), nparts, tmp);
     hipLaunchKernelGGL(k_norm_final, dim3(1), dim3(256), 0, c->stream, tmp, 64L, out);
   } else {
     hipLaunchKernelGGL(k_norm_final, dim3(1), dim3(256), 0, c->stream,
-                       c->partials, nparts, out);
+                       c->partials.get(), nparts, out);
   }
   HIPCHK(hipGetLastError());
   return 0;
@@ -1103,7 +1076,7 @@ int update_pass(agx_ctx* c, int mode, int mm, double* l2, agx_linf* linf) {
       BlockDev& b = c->blocks[n].d;
       const MarchPlan mp = march_plan(c, b);
       hipLaunchKernelGGL(k_norm_final, dim3(1), dim3(256), 0, c->stream,
-                         c->partials + off, mp.nparts, c->norm_out + n);
+                         c->partials.get() + off, mp.nparts, c->norm_out.get() + n);
       off += mp.nparts;
       for (int e = 0; e < AGX_NEQ; ++e) std::swap(b.state[e], b.state2[e]);
     }
@@ -1119,7 +1092,7 @@ int update_pass(agx_ctx* c, int mode, int mm, double* l2, agx_linf* linf) {
       if (mode == 2 && b.d2.base) {
         const dim3 tg((b.ni + TT - 1) / TT, (b.nj + TT - 1) / TT, b.nk);
         hipLaunchKernelGGL(k_update_d2, tg, dim3(256), 0, c->stream, b, c->gas, c->sp, last,
-                           c->partials);
+                           c->partials.get());
         if (reduce_norms(c, n, (long)tg.x * tg.y * tg.z)) return 1;
         continue;
       }
@@ -1127,18 +1100,19 @@ int update_pass(agx_ctx* c, int mode, int mm, double* l2, agx_linf* linf) {
       const dim3 grid = cell_grid(b, CELL_BLOCK);
       hipLaunchKernelGGL(k_update, grid, CELL_BLOCK, 0, c->stream, b, c->gas,
                          c->sp, mode, mode == 1 ? alpha[mm & 3] : 1.0, last,
-                         c->partials);
+                         c->partials.get());
       if (reduce_norms(c, n, (long)grid.x * grid.y * grid.z)) return 1;
     }
   }
-  HIPCHK(hipMemcpyAsync(c->norm_host, c->norm_out,
+  HIPCHK(hipMemcpyAsync(c->norm_host.get(), c->norm_out.get(),
                         sizeof(NormPartial) * c->blocks.size(),
                         hipMemcpyDeviceToHost, c->stream));
   if (c->mres_deferred)
-    HIPCHK(hipMemcpyAsync(c->norm_host + c->blocks.size(), c->norm_out + c->blocks.size() + 64,
+    HIPCHK(hipMemcpyAsync(c->norm_host.get() + c->blocks.size(),
+                          c->norm_out.get() + c->blocks.size() + 64,
                           sizeof(NormPartial) * c->blocks.size(), hipMemcpyDeviceToHost,
                           c->stream));
-  HIPCHK(hipMemcpyAsync(c->err_host, c->err_dev, sizeof(int),
+  HIPCHK(hipMemcpyAsync(c->err_host.get(), c->err_dev.get(), sizeof(int),
                         hipMemcpyDeviceToHost, c->stream));
   if (c->in_iterate && c->eager_ghosts) {
     // the host waits for the norms only; the ghost fill of the next iteration is
@@ -1153,7 +1127,7 @@ int update_pass(agx_ctx* c, int mode, int mm, double* l2, agx_linf* linf) {
   }
   if (check_device_error(c)) return 1;
   for (size_t n = 0; n < c->blocks.size(); ++n) {
-    const NormPartial& p = c->norm_host[n];
+    const NormPartial& p = c->norm_host.get()[n];
     const BlockDev& b = c->blocks[n].d;
     for (int e = 0; e < AGX_NEQ; ++e) l2[e] += p.l2[e];
     if (p.vmax > linf->linf) {           // procBlock.cpp:863-866
@@ -1185,7 +1159,7 @@ GeoPlanes geo_planes(Block& b) {
     g.cen[q] = d.cen[q];
     for (int cc = 0; cc < 4; ++cc) g.fa[q][cc] = d.fa[q][cc];
     for (int cc = 0; cc < 3; ++cc)
-      g.fc[q][cc] = b.fcen ? b.fcen + (long)(3 * q + cc) * d.nplane : nullptr;
+      g.fc[q][cc] = b.fcen ? b.fcen.get() + (long)(3 * q + cc) * d.nplane : nullptr;
   }
   return g;
 }
@@ -1203,21 +1177,22 @@ void surface_range(const agx_bc_surface& s, int* lo, int* hi) {
 int geo_block_metrics(agx_ctx* c, Block& b, const double* nodes) {
   const BlockDev& d = b.d;
   const long nn = (long)(d.ni + 1) * (d.nj + 1) * (d.nk + 1);
-  HIPCHK(hipMalloc((void**)&b.nodes_dev, sizeof(double) * 3 * nn));
-  HIPCHK(hipMemcpyAsync(b.nodes_dev, nodes, sizeof(double) * 3 * nn, hipMemcpyHostToDevice,
+  HIPCHK(b.nodes_dev.alloc((size_t)3 * nn));
+  HIPCHK(hipMemcpyAsync(b.nodes_dev.get(), nodes, sizeof(double) * 3 * nn, hipMemcpyHostToDevice,
                         c->stream));
-  HIPCHK(hipMemsetAsync(c->err_dev, 0, sizeof(int), c->stream));
-  hipLaunchKernelGGL(k_metrics_planes, geo_grid(nn), dim3(256), 0, c->stream, d, b.nodes_dev,
-                     geo_planes(b), 1, c->err_dev);
+  HIPCHK(hipMemsetAsync(c->err_dev.get(), 0, sizeof(int), c->stream));
+  hipLaunchKernelGGL(k_metrics_planes, geo_grid(nn), dim3(256), 0, c->stream, d,
+                     b.nodes_dev.get(), geo_planes(b), 1, c->err_dev.get());
   hipLaunchKernelGGL(k_geo_fill, geo_grid(d.nplane), dim3(256), 0, c->stream, d.wdist,
                      (long)d.nplane, 1.0e10);                  // DEFAULT_WALL_DIST
   HIPCHK(hipGetLastError());
-  HIPCHK(hipMemcpyAsync(c->err_host, c->err_dev, sizeof(int), hipMemcpyDeviceToHost, c->stream));
+  HIPCHK(hipMemcpyAsync(c->err_host.get(), c->err_dev.get(), sizeof(int), hipMemcpyDeviceToHost,
+                        c->stream));
   HIPCHK(hipStreamSynchronize(c->stream));
-  const int code = *c->err_host;
+  const int code = *c->err_host.get();
   if (code) {
-    *c->err_host = 0;
-    hipMemsetAsync(c->err_dev, 0, sizeof(int), c->stream);
+    *c->err_host.get() = 0;
+    hipMemsetAsync(c->err_dev.get(), 0, sizeof(int), c->stream);
     if (code == 4) return fail("negative volume in PLOT3D block");
     return fail("negative %c-face area in PLOT3D block", "ijk"[(code - 5) % 3]);
   }
@@ -1248,16 +1223,16 @@ int geo_swap(agx_ctx* c, Conn& k) {
     if (n == 0) continue;
     // the sender's volume of every cell of the slice
     std::vector<double> svol(n);
-    long* idx_dev = nullptr;
-    double* buf = nullptr;
-    if (to_device(m.src, &idx_dev)) return 1;
-    HIPCHK(hipMalloc((void**)&buf, sizeof(double) * n));
-    hipLaunchKernelGGL(k_geo_gather1, geo_grid(n), dim3(256), 0, c->stream, S.d.vol, idx_dev, n, buf);
+    DevBuf<long> idx_dev;
+    DevBuf<double> buf;
+    HIPCHK(idx_dev.upload(m.src));
+    HIPCHK(buf.alloc((size_t)n));
+    hipLaunchKernelGGL(k_geo_gather1, geo_grid(n), dim3(256), 0, c->stream, S.d.vol,
+                       idx_dev.get(), n, buf.get());
     HIPCHK(hipGetLastError());
-    HIPCHK(hipMemcpyAsync(svol.data(), buf, sizeof(double) * n, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(hipMemcpyAsync(svol.data(), buf.get(), sizeof(double) * n, hipMemcpyDeviceToHost,
+                          c->stream));
     HIPCHK(hipStreamSynchronize(c->stream));
-    HIPCHK(hipFree(idx_dev));
-    HIPCHK(hipFree(buf));
     int orient = cc.orientation;
     if (recv == 1) { if (orient == 4) orient = 5; else if (orient == 5) orient = 4; }
     int rd1, rd2, rd3, sd1, sd2, sd3;
@@ -1316,34 +1291,31 @@ int geo_swap(agx_ctx* c, Conn& k) {
     }
   }
   // both slices are taken (gathered) before either insert (utility.cpp:232-233)
-  GeoCopy* rec_dev[2] = {nullptr, nullptr};
-  double* buf_dev[2] = {nullptr, nullptr};
+  DevBuf<GeoCopy> rec_dev[2];
+  DevBuf<double> buf_dev[2];
   for (int recv = 0; recv < 2; ++recv) {
     const long n = (long)rec[recv].size();
     if (n == 0) continue;
     Block& S = c->blocks[cc.local_block[1 - recv]];
-    HIPCHK(hipMalloc((void**)&rec_dev[recv], sizeof(GeoCopy) * n));
-    HIPCHK(hipMalloc((void**)&buf_dev[recv], sizeof(double) * 7 * n));
-    HIPCHK(hipMemcpyAsync(rec_dev[recv], rec[recv].data(), sizeof(GeoCopy) * n,
+    HIPCHK(rec_dev[recv].alloc((size_t)n));
+    HIPCHK(buf_dev[recv].alloc((size_t)7 * n));
+    HIPCHK(hipMemcpyAsync(rec_dev[recv].get(), rec[recv].data(), sizeof(GeoCopy) * n,
                           hipMemcpyHostToDevice, c->stream));
     hipLaunchKernelGGL(k_geo_gather, geo_grid(n), dim3(256), 0, c->stream, geo_planes(S),
-                       rec_dev[recv], n, buf_dev[recv]);
+                       rec_dev[recv].get(), n, buf_dev[recv].get());
   }
   for (int recv = 0; recv < 2; ++recv) {
     const long n = (long)rec[recv].size();
     if (n == 0) continue;
     Block& R = c->blocks[cc.local_block[recv]];
     hipLaunchKernelGGL(k_geo_scatter, geo_grid(n), dim3(256), 0, c->stream, geo_planes(R),
-                       rec_dev[recv], n, buf_dev[recv]);
+                       rec_dev[recv].get(), n, buf_dev[recv].get());
   }
   HIPCHK(hipGetLastError());
   HIPCHK(hipStreamSynchronize(c->stream));
-  for (int recv = 0; recv < 2; ++recv) {
-    if (rec_dev[recv]) HIPCHK(hipFree(rec_dev[recv]));
-    if (buf_dev[recv]) HIPCHK(hipFree(buf_dev[recv]));
+  for (int recv = 0; recv < 2; ++recv)
     for (int q = 0; q < 4; ++q)
       if (adj[recv][q]) k.c.patch_border[4 * recv + q] = 1;
-  }
   return 0;
 }
 
@@ -1352,9 +1324,8 @@ int geo_swap(agx_ctx* c, Conn& k) {
 int geo_swap_wall_dist(agx_ctx* c, Conn& k) {
   const int ng = c->cfg.n_ghost;
   const agx_connection& cc = k.c;
-  long* dst_dev[2] = {nullptr, nullptr};
-  long* src_dev[2] = {nullptr, nullptr};
-  double* buf[2] = {nullptr, nullptr};
+  DevBuf<long> dst_dev[2], src_dev[2];
+  DevBuf<double> buf[2];
   long n[2] = {0, 0};
   for (int recv = 0; recv < 2; ++recv) {
     Block& R = c->blocks[cc.local_block[recv]];
@@ -1365,24 +1336,20 @@ int geo_swap_wall_dist(agx_ctx* c, Conn& k) {
     build_side_map(cc, recv, ng, idxR, idxS, m);
     n[recv] = (long)m.dst.size();
     if (n[recv] == 0) continue;
-    if (to_device(m.dst, &dst_dev[recv]) || to_device(m.src, &src_dev[recv])) return 1;
-    HIPCHK(hipMalloc((void**)&buf[recv], sizeof(double) * n[recv]));
+    HIPCHK(dst_dev[recv].upload(m.dst));
+    HIPCHK(src_dev[recv].upload(m.src));
+    HIPCHK(buf[recv].alloc((size_t)n[recv]));
     hipLaunchKernelGGL(k_geo_gather1, geo_grid(n[recv]), dim3(256), 0, c->stream, S.d.wdist,
-                       src_dev[recv], n[recv], buf[recv]);
+                       src_dev[recv].get(), n[recv], buf[recv].get());
   }
   for (int recv = 0; recv < 2; ++recv) {
     if (n[recv] == 0) continue;
     Block& R = c->blocks[cc.local_block[recv]];
     hipLaunchKernelGGL(k_geo_scatter1, geo_grid(n[recv]), dim3(256), 0, c->stream, R.d.wdist,
-                       dst_dev[recv], n[recv], buf[recv]);
+                       dst_dev[recv].get(), n[recv], buf[recv].get());
   }
   HIPCHK(hipGetLastError());
-  HIPCHK(hipStreamSynchronize(c->stream));
-  for (int recv = 0; recv < 2; ++recv) {
-    if (dst_dev[recv]) HIPCHK(hipFree(dst_dev[recv]));
-    if (src_dev[recv]) HIPCHK(hipFree(src_dev[recv]));
-    if (buf[recv]) HIPCHK(hipFree(buf[recv]));
-  }
+  HIPCHK(hipStreamSynchronize(c->stream));     // (the buffers go out of scope)
   return 0;
 }
 
@@ -1406,11 +1373,11 @@ int geo_complete(agx_ctx* c) {
   for (auto& b : c->blocks) {
     const BlockDev& d = b.d;
     if (!b.nodes_dev) return fail("agx_setup_finalize: the geometry of this context is complete");
-    HIPCHK(hipMalloc((void**)&b.fcen, sizeof(double) * 9 * d.nplane));
-    HIPCHK(hipMemsetAsync(b.fcen, 0, sizeof(double) * 9 * d.nplane, c->stream));
+    HIPCHK(b.fcen.alloc((size_t)9 * d.nplane));
+    HIPCHK(hipMemsetAsync(b.fcen.get(), 0, sizeof(double) * 9 * d.nplane, c->stream));
     const long nn = (long)(d.ni + 1) * (d.nj + 1) * (d.nk + 1);
-    hipLaunchKernelGGL(k_metrics_planes, geo_grid(nn), dim3(256), 0, c->stream, d, b.nodes_dev,
-                       geo_planes(b), 2, c->err_dev);
+    hipLaunchKernelGGL(k_metrics_planes, geo_grid(nn), dim3(256), 0, c->stream, d,
+                       b.nodes_dev.get(), geo_planes(b), 2, c->err_dev.get());
   }
   HIPCHK(hipGetLastError());
   // 1. AssignGhostCellsGeom: layer by layer, surface by surface in the given order
@@ -1471,8 +1438,9 @@ int geo_complete(agx_ctx* c) {
         nwall += (long)(hi[0] - lo[0]) * (hi[1] - lo[1]) * (hi[2] - lo[2]);
       }
     if (nwall > 0) {
-      double* wall = nullptr;
-      HIPCHK(hipMalloc((void**)&wall, sizeof(double) * 3 * nwall));
+      DevBuf<double> wall_pts;
+      HIPCHK(wall_pts.alloc((size_t)3 * nwall));
+      double* const wall = wall_pts.get();
       long off = 0;
       for (auto& b : c->blocks)
         for (const agx_bc_surface& s : b.surf_host) {
@@ -1503,7 +1471,7 @@ int geo_complete(agx_ctx* c) {
       }
       HIPCHK(hipGetLastError());
       HIPCHK(hipStreamSynchronize(c->stream));
-      HIPCHK(hipFree(wall));
+      wall_pts.reset();
       for (auto& k : c->conns)
         if (k.c.rank[0] == c->rank && geo_swap_wall_dist(c, k)) return 1;
     }
@@ -1519,8 +1487,8 @@ int geo_complete(agx_ctx* c) {
 #endif
   HIPCHK(hipStreamSynchronize(c->stream));
   for (auto& b : c->blocks) {
-    HIPCHK(hipFree(b.fcen)); b.fcen = nullptr;
-    HIPCHK(hipFree(b.nodes_dev)); b.nodes_dev = nullptr;
+    b.fcen.reset();
+    b.nodes_dev.reset();
   }
   return 0;
 }
@@ -1578,10 +1546,10 @@ int agx_ctx_create(int device, int rank, agx_ctx** out) {
       c->halo_batch_required = !strcmp(w, "require");
     }
   }
-  HIPCHK(hipMalloc((void**)&c->err_dev, sizeof(int)));
-  HIPCHK(hipMemset(c->err_dev, 0, sizeof(int)));
-  HIPCHK(hipHostMalloc((void**)&c->err_host, sizeof(int)));
-  *c->err_host = 0;
+  HIPCHK(c->err_dev.alloc(1));
+  HIPCHK(hipMemset(c->err_dev.get(), 0, sizeof(int)));
+  HIPCHK(c->err_host.alloc(1));
+  *c->err_host.get() = 0;
   *out = c;
   return 0;
 }
@@ -1590,54 +1558,6 @@ void agx_ctx_destroy(agx_ctx* c) {
   if (!c) return;
   hipSetDevice(c->device);
   hipStreamSynchronize(c->stream);
-  for (auto& b : c->blocks) {
-    if (b.slab) hipFree(b.slab);
-    if (b.d2) hipFree(b.d2);
-    if (b.blockmat) hipFree(b.blockmat);
-    if (b.sweep_rec) hipFree(b.sweep_rec);
-    for (void* p : {(void*)b.mg_forcing, (void*)b.mg_mres, (void*)b.mg_xsave, (void*)b.mg_nodes,
-                    (void*)b.mg_tc, (void*)b.mg_start, (void*)b.mg_vf, (void*)b.mg_cf})
-      if (p) hipFree(p);
-    if (b.d2_tab) hipFree(b.d2_tab);
-    if (b.kp_mem) hipFree(b.kp_mem);
-    if (b.nodes_dev) hipFree(b.nodes_dev);
-    if (b.fcen) hipFree(b.fcen);
-    for (auto& g1 : b.sweep_graph) for (auto& g2 : g1) for (auto& g3 : g2)
-      if (g3) hipGraphExecDestroy(g3);
-    if (b.surf_dev) hipFree(b.surf_dev);
-    if (b.nr_off_dev) hipFree(b.nr_off_dev);
-    if (b.nr_mem) hipFree(b.nr_mem);
-    if (b.wall_off_dev) hipFree(b.wall_off_dev);
-    if (b.wall_mem) hipFree(b.wall_mem);
-    if (b.wall_tab_dev) hipFree(b.wall_tab_dev);
-  }
-  for (auto& k : c->conns) {
-    for (int s = 0; s < 2; ++s) {
-      if (k.side[s].dst) hipFree(k.side[s].dst);
-      if (k.side[s].src) hipFree(k.side[s].src);
-      if (k.side[s].dst2) hipFree(k.side[s].dst2);
-      if (k.side[s].src2) hipFree(k.side[s].src2);
-    }
-    if (k.send_src) hipFree(k.send_src);
-    if (k.send_src2) hipFree(k.send_src2);
-  }
-  if (c->partials) hipFree(c->partials);
-  if (c->norm_out) hipFree(c->norm_out);
-  if (c->norm_host) hipHostFree(c->norm_host);
-  if (c->err_dev) hipFree(c->err_dev);
-  if (c->err_host) hipHostFree(c->err_host);
-  if (c->halo_buf) hipFree(c->halo_buf);
-  if (c->stage_buf) hipFree(c->stage_buf);
-  if (c->rans_rec) hipFree(c->rans_rec);
-  pipe_free(c);
-  for (auto& r : c->remote) {
-    if (r.send) hipFree(r.send);
-    if (r.recv) hipFree(r.recv);
-    if (r.hsend) hipHostFree(r.hsend);
-    if (r.hrecv) hipHostFree(r.hrecv);
-  }
-  if (c->rec_dev) hipFree(c->rec_dev);
-  if (c->rec_host) hipHostFree(c->rec_host);
   if (c->nccl) ncclCommDestroy(c->nccl);
   for (auto& e : c->ev_pool) { hipEventDestroy(e.first); hipEventDestroy(e.second); }
   if (c->cap_stream) hipStreamDestroy(c->cap_stream);
@@ -1647,17 +1567,9 @@ void agx_ctx_destroy(agx_ctx* c) {
     hipEventDestroy(c->ov_ready);
     hipEventDestroy(c->ov_done);
   }
-  drop_sweep_graphs_all(c);
-  if (c->blocks_tab) hipFree(c->blocks_tab);
-  if (c->blocks_tab_host) hipHostFree(c->blocks_tab_host);
-  if (c->halo_tab_host) hipHostFree(c->halo_tab_host);
-  for (int w = 0; w < 5; ++w)
-    for (int st = 0; st < 2; ++st)
-      for (int q = 0; q < 2; ++q)
-        if (c->halo_tab_dev[w][st][q]) hipFree(c->halo_tab_dev[w][st][q]);
   for (auto ev : c->branch_events) hipEventDestroy(ev);
   for (auto st : c->branch_streams) hipStreamDestroy(st);
-  delete c;
+  delete c;     // (memory and graphs go with their owners, on the context's device)
 }
 
 int agx_ctx_set_stream(agx_ctx* c, void* s) {
@@ -1745,7 +1657,7 @@ int agx_config_set(agx_ctx* c, const agx_config* cfg) {
   c->gas.sstdes = cfg->turbulence_model == AGX_TURB_SST_DES ? 1 : 0;
   c->gas.turb_prandtl = c->gas.wilcox ? 8.0 / 9.0 : 0.9;
 #if AGX_TPG
-  c->gas.err = c->err_dev;
+  c->gas.err = c->err_dev.get();
 #endif
   SolverDev& sp = c->sp;
   sp.diag_add = 0;
@@ -1800,9 +1712,9 @@ int agx_block_create(agx_ctx* c, const agx_block_geom* g, int* block_id) {
   d.sxy = d.sx * (d.nj + 2 * d.ng + 1);
   d.nplane = d.sxy * (d.nk + 2 * d.ng + 1);
   // one slab for all planes of the block (see SlabDev in agx_kernels.hpp)
-  HIPCHK(hipMalloc((void**)&b.slab, sizeof(double) * d.nplane * PL_COUNT));
-  HIPCHK(hipMemsetAsync(b.slab, 0, sizeof(double) * d.nplane * PL_COUNT, c->stream));
-  auto pl = [&](int id) { return b.slab + (long)id * d.nplane; };
+  HIPCHK(b.slab.alloc((size_t)d.nplane * PL_COUNT));
+  HIPCHK(hipMemsetAsync(b.slab.get(), 0, sizeof(double) * d.nplane * PL_COUNT, c->stream));
+  auto pl = [&](int id) { return b.slab.get() + (long)id * d.nplane; };
   d.vol = pl(PL_VOL); d.specrad = pl(PL_SPECRAD); d.dt = pl(PL_DT);
   d.a = pl(PL_A); d.ainv = pl(PL_AINV); d.wdist = pl(PL_WDIST);
   for (int e = 0; e < AGX_NEQ; ++e) {
@@ -1826,11 +1738,11 @@ int agx_block_create(agx_ctx* c, const agx_block_geom* g, int* block_id) {
     // a_, aInv_ (25 planes each) and velocityGrad_ (9) of the block-matrix solvers
     // (+ 2 x 2 planes: diagonal of the turbulence block in the rans build)
     const size_t n = (size_t)d.nplane * (2 * AGX_NJ + 9 + 4);
-    HIPCHK(hipMalloc((void**)&b.blockmat, sizeof(double) * n));
-    HIPCHK(hipMemsetAsync(b.blockmat, 0, sizeof(double) * n, c->stream));
-    d.am = b.blockmat;
-    d.aminv = b.blockmat + (size_t)d.nplane * AGX_NJ;
-    d.vg = b.blockmat + (size_t)d.nplane * 2 * AGX_NJ;
+    HIPCHK(b.blockmat.alloc(n));
+    HIPCHK(hipMemsetAsync(b.blockmat.get(), 0, sizeof(double) * n, c->stream));
+    d.am = b.blockmat.get();
+    d.aminv = d.am + (size_t)d.nplane * AGX_NJ;
+    d.vg = d.am + (size_t)d.nplane * 2 * AGX_NJ;
     d.am_t = d.vg + (size_t)d.nplane * 9;
     d.aminv_t = d.am_t + (size_t)d.nplane * 2;
   }
@@ -1838,9 +1750,9 @@ int agx_block_create(agx_ctx* c, const agx_block_geom* g, int* block_id) {
   d.mg_forcing = d.mg_mres = d.mg_xsave = nullptr;
   if (c->sp.implicit && is_lusgs_solver(c) && !use_d2(c) && c->sweep_records) {
     const size_t n = (size_t)d.nplane * (SW_GEO + SW_DYN + SW_RHS);
-    HIPCHK(hipMalloc((void**)&b.sweep_rec, sizeof(double) * n));
-    HIPCHK(hipMemsetAsync(b.sweep_rec, 0, sizeof(double) * n, c->stream));
-    d.sw_geo = b.sweep_rec;
+    HIPCHK(b.sweep_rec.alloc(n));
+    HIPCHK(hipMemsetAsync(b.sweep_rec.get(), 0, sizeof(double) * n, c->stream));
+    d.sw_geo = b.sweep_rec.get();
     d.sw_dyn = d.sw_geo + (size_t)d.nplane * SW_GEO;
     d.sw_rhs = d.sw_dyn + (size_t)d.nplane * SW_DYN;
   }
@@ -1864,13 +1776,12 @@ int agx_block_create(agx_ctx* c, const agx_block_geom* g, int* block_id) {
     }
     b.dstart[z.Pi + z.Pj] = b.dstart[z.Pi + z.Pj - 1];
     std::copy(b.dstart.begin(), b.dstart.end(), tab.begin());
-    HIPCHK(hipMalloc((void**)&b.d2_tab, sizeof(int) * tab.size()));
-    HIPCHK(hipMemcpy(b.d2_tab, tab.data(), sizeof(int) * tab.size(), hipMemcpyHostToDevice));
-    z.dstart = b.d2_tab;
-    z.ij_of_pos = b.d2_tab + z.Pi + z.Pj + 1;
-    HIPCHK(hipMalloc((void**)&b.d2, sizeof(double) * z.nd2 * D2_DOUBLES));
-    HIPCHK(hipMemsetAsync(b.d2, 0, sizeof(double) * z.nd2 * D2_DOUBLES, c->stream));
-    z.base = b.d2;
+    HIPCHK(b.d2_tab.upload(tab));
+    z.dstart = b.d2_tab.get();
+    z.ij_of_pos = z.dstart + z.Pi + z.Pj + 1;
+    HIPCHK(b.d2.alloc((size_t)z.nd2 * D2_DOUBLES));
+    HIPCHK(hipMemsetAsync(b.d2.get(), 0, sizeof(double) * z.nd2 * D2_DOUBLES, c->stream));
+    z.base = b.d2.get();
   }
   b.node_built = from_nodes;
   if (from_nodes) {
@@ -1908,13 +1819,15 @@ int agx_block_create(agx_ctx* c, const agx_block_geom* g, int* block_id) {
 int agx_block_set_bcs(agx_ctx* c, int id, int n, const agx_bc_surface* s) {
   if (id < 0 || id >= (int)c->blocks.size()) return fail("bad block id %d", id);
   Block& b = c->blocks[id];
-  for (auto& g1 : b.sweep_graph) for (auto& g2 : g1) for (auto& g3 : g2)
-    if (g3) { hipGraphExecDestroy(g3); g3 = nullptr; }     // (they hold the old BlockDev)
+  b.sweep_graph.drop();                      // (they hold the old BlockDev)
   b.surf_host.assign(s, s + n);
-  if (b.surf_dev) HIPCHK(hipFree(b.surf_dev));
-  HIPCHK(hipMalloc((void**)&b.surf_dev, sizeof(agx_bc_surface) * (n > 0 ? n : 1)));
-  HIPCHK(hipMemcpy(b.surf_dev, s, sizeof(agx_bc_surface) * n, hipMemcpyHostToDevice));
-  b.d.surf = b.surf_dev;
+  // (a view in b.d follows its owner only once the owner holds the new memory: a failing
+  // call leaves none dangling)
+  b.d.surf = nullptr;
+  b.d.nsurf = 0;
+  HIPCHK(b.surf_dev.alloc(n > 0 ? n : 1));
+  HIPCHK(hipMemcpy(b.surf_dev.get(), s, sizeof(agx_bc_surface) * n, hipMemcpyHostToDevice));
+  b.d.surf = b.surf_dev.get();
   b.d.nsurf = n;
   b.d.nsurf_i = b.d.nsurf_j = b.d.nsurf_k = 0;
   int n_conn[6] = {0, 0, 0, 0, 0, 0}, n_other[6] = {0, 0, 0, 0, 0, 0};
@@ -1933,12 +1846,12 @@ int agx_block_set_bcs(agx_ctx* c, int id, int n, const agx_bc_surface* s) {
     b.d.side_conn[q] = n_conn[q] == 0 ? 0 : (n_other[q] == 0 ? 1 : 2);
   // nonreflecting inlet / outlet surfaces keep the gradients of their adjacent cells
   // and their Mach mean / maximum between a residual and the next ghost fills
-  if (b.nr_off_dev) HIPCHK(hipFree(b.nr_off_dev));
-  if (b.nr_mem) HIPCHK(hipFree(b.nr_mem));
-  b.nr_off_dev = nullptr; b.nr_mem = nullptr; b.nr_max = 0;
   b.d.nr_off = nullptr; b.d.nr_grad = nullptr; b.d.nr_mach = nullptr;
+  b.nr_off_dev.reset();
+  b.nr_mem.reset();
+  b.nr_max = 0;
   std::vector<int> off(n > 0 ? n : 1, -1);
-  long total = 0;
+  long total = 0, nr_max = 0;
   for (int q = 0; q < n; ++q) {
     const int t = s[q].bc_type;
     if (!s[q].state.is_nonreflecting || (t != AGX_BC_INLET && t != AGX_BC_PRESSURE_OUTLET)) continue;
@@ -1948,24 +1861,23 @@ int agx_block_set_bcs(agx_ctx* c, int id, int n, const agx_bc_surface* s) {
     const long cells = (long)(hi[d1] - lo[d1]) * (hi[d2] - lo[d2]);
     off[q] = (int)total;
     total += cells;
-    b.nr_max = std::max(b.nr_max, cells);
+    nr_max = std::max(nr_max, cells);
   }
   if (total > 0) {
-    HIPCHK(hipMalloc((void**)&b.nr_off_dev, sizeof(int) * n));
-    HIPCHK(hipMemcpy(b.nr_off_dev, off.data(), sizeof(int) * n, hipMemcpyHostToDevice));
+    HIPCHK(b.nr_off_dev.upload(off.data(), (size_t)n));
     const size_t nd = (size_t)12 * total + 2 * (size_t)n;
-    HIPCHK(hipMalloc((void**)&b.nr_mem, sizeof(double) * nd));
-    HIPCHK(hipMemset(b.nr_mem, 0, sizeof(double) * nd));   // gradients before the first residual
-    b.d.nr_off = b.nr_off_dev;
-    b.d.nr_grad = b.nr_mem;
-    b.d.nr_mach = b.nr_mem + 12 * total;
+    HIPCHK(b.nr_mem.alloc(nd));
+    HIPCHK(hipMemset(b.nr_mem.get(), 0, sizeof(double) * nd));   // gradients before the first residual
+    b.d.nr_off = b.nr_off_dev.get();
+    b.d.nr_grad = b.nr_mem.get();
+    b.d.nr_mach = b.nr_mem.get() + 12 * total;
+    b.nr_max = nr_max;
   }
   // wall-law surfaces keep the wall data of their faces (wallData_, wallData.hpp:33-62)
   // from the viscous ghost fill to the viscous fluxes of the same residual
-  if (b.wall_off_dev) HIPCHK(hipFree(b.wall_off_dev));
-  if (b.wall_mem) HIPCHK(hipFree(b.wall_mem));
-  b.wall_off_dev = nullptr; b.wall_mem = nullptr;
   b.d.wall_off = nullptr; b.d.wallv = nullptr;
+  b.wall_off_dev.reset();
+  b.wall_mem.reset();
   std::fill(off.begin(), off.end(), -1);
   total = 0;
   for (int q = 0; q < n; ++q) {
@@ -1977,18 +1889,16 @@ int agx_block_set_bcs(agx_ctx* c, int id, int n, const agx_bc_surface* s) {
     total += (long)(hi[d1] - lo[d1]) * (hi[d2] - lo[d2]);
   }
   if (total > 0) {
-    HIPCHK(hipMalloc((void**)&b.wall_off_dev, sizeof(int) * n));
-    HIPCHK(hipMemcpy(b.wall_off_dev, off.data(), sizeof(int) * n, hipMemcpyHostToDevice));
-    const size_t nd = sizeof(WallVars) * (size_t)total;
-    HIPCHK(hipMalloc((void**)&b.wall_mem, nd));
-    HIPCHK(hipMemset(b.wall_mem, 0, nd));        // y+ = 0: low-Re until the first ghost fill
-    b.d.wall_off = b.wall_off_dev;
-    b.d.wallv = (WallVars*)b.wall_mem;
+    HIPCHK(b.wall_off_dev.upload(off.data(), (size_t)n));
+    HIPCHK(b.wall_mem.alloc((size_t)total));
+    // y+ = 0: low-Re until the first ghost fill
+    HIPCHK(hipMemset(b.wall_mem.get(), 0, sizeof(WallVars) * (size_t)total));
+    b.d.wall_off = b.wall_off_dev.get();
+    b.d.wallv = b.wall_mem.get();
     c->have_wall_data = false;
   }
   // the table of the wall-surface output (agx_output_pack with AGX_WALL_*)
-  if (b.wall_tab_dev) HIPCHK(hipFree(b.wall_tab_dev));
-  b.wall_tab_dev = nullptr;
+  b.wall_tab_dev.reset();
   b.wall_tab.clear();
   b.wall_faces = 0;
   for (int q = 0; q < n; ++q) {
@@ -2009,11 +1919,7 @@ int agx_block_set_bcs(agx_ctx* c, int id, int n, const agx_bc_surface* s) {
     b.wall_faces += (long)w.n[0] * w.n[1] * w.n[2];
     b.wall_tab.push_back(w);
   }
-  if (!b.wall_tab.empty()) {
-    HIPCHK(hipMalloc((void**)&b.wall_tab_dev, sizeof(WallSurfDev) * b.wall_tab.size()));
-    HIPCHK(hipMemcpy(b.wall_tab_dev, b.wall_tab.data(), sizeof(WallSurfDev) * b.wall_tab.size(),
-                     hipMemcpyHostToDevice));
-  }
+  HIPCHK(b.wall_tab_dev.upload(b.wall_tab));
   return 0;
 }
 
@@ -2108,44 +2014,86 @@ int halo_batch_plan(agx_ctx* c, long* max_halo) {
   c->halo_batch_sides = sides;
   c->halo_batch_nmax = nmax_all;
   *max_halo = std::max(*max_halo, (total * AGX_NEQ + 1) / 2);     // (the buffer is 2 * max_halo)
-  HIPCHK(hipHostMalloc((void**)&c->halo_tab_host, sizeof(HaloSide) * 2 * sides));
+  HIPCHK(c->halo_tab_host.alloc((size_t)2 * sides));
   return 0;
+}
+// The four records of local connection k for a halo selector: g[0], g[1] what sides 0 and 1
+// receive, gathered from the partner's block; p[0], p[1] their inserts.  buf0 / buf1: where
+// the two halves of the connection's buffer start.
+void halo_sides(agx_ctx* c, Conn& k, int what, double* buf0, double* buf1, HaloSide* g,
+                HaloSide* p) {
+  Block& b0 = c->blocks[k.c.local_block[0]];
+  Block& b1 = c->blocks[k.c.local_block[1]];
+  const int z = halo_in_d2(b0, what);
+  const auto &m0 = k.side[0].map[z], &m1 = k.side[1].map[z];
+  g[0] = HaloSide{halo_planes(b1, what), m0.src.get(), k.side[0].n, buf0};
+  g[1] = HaloSide{halo_planes(b0, what), m1.src.get(), k.side[1].n, buf1};
+  p[0] = HaloSide{halo_planes(b0, what), m0.dst.get(), k.side[0].n, buf0};
+  p[1] = HaloSide{halo_planes(b1, what), m1.dst.get(), k.side[1].n, buf1};
 }
 // the gather / scatter tables of one halo selector (plane pointers of every side)
 int halo_batch_tables(agx_ctx* c, int what) {
   const int set = c->halo_set[what];
   if (c->halo_tab_valid[what][set]) return 0;
   const int sides = c->halo_batch_sides;
+  auto& tab = c->halo_tab_dev[what][set];
   for (int q = 0; q < 2; ++q)
-    if (!c->halo_tab_dev[what][set][q])
-      HIPCHK(hipMalloc((void**)&c->halo_tab_dev[what][set][q], sizeof(HaloSide) * sides));
+    if (!tab[q]) HIPCHK(tab[q].alloc((size_t)sides));
   // (the staging entries may still be read by an earlier copy)
   HIPCHK(hipStreamSynchronize(c->stream));
-  HaloSide* g = c->halo_tab_host;
-  HaloSide* p = c->halo_tab_host + sides;
-  long off = 0;
+  HaloSide* g = c->halo_tab_host.get();
+  HaloSide* p = g + sides;
+  double* buf = c->halo_buf.get();
   int n = 0;
   for (int cid : c->halo_conn_order) {            // (level by level)
     auto& k = c->conns[cid];
-    const agx_connection& cc = k.c;
-    Block& b0 = c->blocks[cc.local_block[0]];
-    Block& b1 = c->blocks[cc.local_block[1]];
-    const bool z2 = halo_in_d2(b0, what);
     const long n0 = k.side[0].n, n1 = k.side[1].n;
-    double* buf0 = c->halo_buf + off;
-    double* buf1 = buf0 + n0 * AGX_NEQ;
-    off += (n0 + n1) * AGX_NEQ;
-    g[n] = HaloSide{halo_planes(b1, what), z2 ? k.side[0].src2 : k.side[0].src, n0, buf0};
-    g[n + 1] = HaloSide{halo_planes(b0, what), z2 ? k.side[1].src2 : k.side[1].src, n1, buf1};
-    p[n] = HaloSide{halo_planes(b0, what), z2 ? k.side[0].dst2 : k.side[0].dst, n0, buf0};
-    p[n + 1] = HaloSide{halo_planes(b1, what), z2 ? k.side[1].dst2 : k.side[1].dst, n1, buf1};
+    halo_sides(c, k, what, buf, buf + n0 * AGX_NEQ, g + n, p + n);
+    buf += (n0 + n1) * AGX_NEQ;
     n += 2;
   }
-  HIPCHK(hipMemcpyAsync(c->halo_tab_dev[what][set][0], g, sizeof(HaloSide) * sides,
-                        hipMemcpyHostToDevice, c->stream));
-  HIPCHK(hipMemcpyAsync(c->halo_tab_dev[what][set][1], p, sizeof(HaloSide) * sides,
-                        hipMemcpyHostToDevice, c->stream));
+  HIPCHK(hipMemcpyAsync(tab[0].get(), g, sizeof(HaloSide) * sides, hipMemcpyHostToDevice,
+                        c->stream));
+  HIPCHK(hipMemcpyAsync(tab[1].get(), p, sizeof(HaloSide) * sides, hipMemcpyHostToDevice,
+                        c->stream));
   c->halo_tab_valid[what][set] = true;
+  return 0;
+}
+}  // namespace
+
+namespace {
+// index of padded cell (i, j, k) of a block in an index space (0: the SoA planes, 1: D2); no
+// block -- the partner lives on another rank -- : 0
+struct CellIndex {
+  const Block* b;
+  int space;
+  long operator()(int i, int j, int k) const {
+    return !b ? 0L : space ? b->d2idx(i, j, k) : b->d.idx(i, j, k);
+  }
+};
+// The maps of side s of a connection in one index space: the ghost cells of my block and,
+// from a partner of this rank, the cells that fill them.  For a partner on another rank, the
+// cells of my block its ghost cells read, in its insertion order (what agx_halo_pack sends).
+int halo_maps(Conn& k, int s, int space, int ng, CellIndex idx_mine, CellIndex idx_partner,
+              bool partner_local, long* max_halo) {
+  MapOut m;
+  build_side_map(k.c, s, ng, idx_mine, idx_partner, m);
+  if (!partner_local) {
+    MapOut ms;
+    build_side_map(k.c, 1 - s, ng, idx_partner, idx_mine, ms);
+    k.n_send = (long)ms.src.size();
+    HIPCHK(k.send_src[space].upload(ms.src));
+    *max_halo = std::max(*max_halo, (long)ms.src.size() * AGX_NEQ);
+  }
+  ConnSide& sd = k.side[s];
+  sd.n = (long)m.dst.size();
+  HIPCHK(sd.map[space].dst.upload(m.dst));
+  if (partner_local) HIPCHK(sd.map[space].src.upload(m.src));
+  *max_halo = std::max(*max_halo, (long)m.dst.size() * AGX_NEQ);
+  if (space == 0) {      // (halo_batch_plan reads, then drops them)
+    sd.h_dst = std::move(m.dst);
+    if (partner_local) sd.h_src = std::move(m.src);
+  }
   return 0;
 }
 }  // namespace
@@ -2173,50 +2121,12 @@ int agx_setup_finalize(agx_ctx* c) {
       if (!mine) continue;
       const int lb = cc.local_block[s];
       if (lb < 0 || lb >= (int)c->blocks.size()) return fail("connection refers to unknown block");
-      const BlockDev& br = c->blocks[lb].d;
-      auto idxR = [&](int i, int j, int kk) { return br.idx(i, j, kk); };
-      MapOut m;
-      if (partner_mine) {
-        const BlockDev& bs = c->blocks[cc.local_block[1 - s]].d;
-        auto idxS = [&](int i, int j, int kk) { return bs.idx(i, j, kk); };
-        build_side_map(cc, s, ng, idxR, idxS, m);
-      } else {
-        auto idxS = [&](int, int, int) { return 0L; };
-        build_side_map(cc, s, ng, idxR, idxS, m);
-        // cells of my block the partner's ghost cells read, in the partner's
-        // insertion order (what agx_halo_pack sends)
-        MapOut ms;
-        auto idxRp = [&](int, int, int) { return 0L; };
-        build_side_map(cc, 1 - s, ng, idxRp, idxR, ms);
-        k.n_send = (long)ms.src.size();
-        if (to_device(ms.src, &k.send_src)) return 1;
-        max_halo = std::max(max_halo, (long)ms.src.size() * AGX_NEQ);
-      }
-      k.side[s].n = (long)m.dst.size();
-      k.side[s].h_dst = m.dst;
-      if (partner_mine) k.side[s].h_src = m.src;
-      if (to_device(m.dst, &k.side[s].dst)) return 1;
-      if (partner_mine && to_device(m.src, &k.side[s].src)) return 1;
-      max_halo = std::max(max_halo, (long)m.dst.size() * AGX_NEQ);
-      if (use_d2(c)) {
-        // the same maps in D2 index space: x of the LU-SGS path lives there
-        const Block& Br = c->blocks[lb];
-        auto idxR2 = [&](int i, int j, int kk) { return Br.d2idx(i, j, kk); };
-        MapOut m2;
-        if (partner_mine) {
-          const Block& Bs = c->blocks[cc.local_block[1 - s]];
-          auto idxS2 = [&](int i, int j, int kk) { return Bs.d2idx(i, j, kk); };
-          build_side_map(cc, s, ng, idxR2, idxS2, m2);
-          if (to_device(m2.src, &k.side[s].src2)) return 1;
-        } else {
-          auto idxS0 = [&](int, int, int) { return 0L; };
-          build_side_map(cc, s, ng, idxR2, idxS0, m2);
-          MapOut ms2;
-          build_side_map(cc, 1 - s, ng, idxS0, idxR2, ms2);
-          if (to_device(ms2.src, &k.send_src2)) return 1;
-        }
-        if (to_device(m2.dst, &k.side[s].dst2)) return 1;
-      }
+      const Block* partner = partner_mine ? &c->blocks[cc.local_block[1 - s]] : nullptr;
+      // in the planes' index space and, where x of the LU-SGS path lives there, in D2's
+      for (int space = 0; space < (use_d2(c) ? 2 : 1); ++space)
+        if (halo_maps(k, s, space, ng, CellIndex{&c->blocks[lb], space},
+                      CellIndex{partner, space}, partner_mine, &max_halo))
+          return 1;
     }
   }
   if (halo_batch_plan(c, &max_halo)) return 1;
@@ -2229,13 +2139,14 @@ int agx_setup_finalize(agx_ctx* c) {
     agx_ctx::Remote r;
     r.cid = (int)n;
     r.count = (long)agx_halo_count(c, (int)n, AGX_HALO_STATE);
-    HIPCHK(hipMalloc((void**)&r.send, sizeof(double) * std::max<long>(r.count, 1)));
-    HIPCHK(hipMalloc((void**)&r.recv, sizeof(double) * std::max<long>(r.count, 1)));
-    if (c->have_ex && c->ex.host_buffers) {
-      HIPCHK(hipHostMalloc((void**)&r.hsend, sizeof(double) * std::max<long>(r.count, 1)));
-      HIPCHK(hipHostMalloc((void**)&r.hrecv, sizeof(double) * std::max<long>(r.count, 1)));
+    const bool hb = c->have_ex && c->ex.host_buffers;
+    const size_t cap = (size_t)std::max<long>(r.count, 1);
+    HIPCHK(r.send.alloc(cap));
+    HIPCHK(r.recv.alloc(cap));
+    if (hb) {
+      HIPCHK(r.hsend.alloc(cap));
+      HIPCHK(r.hrecv.alloc(cap));
     }
-    c->remote.push_back(r);
     const int s = my_side(c, c->conns[n]);
     agx_slab sl;
     sl.peer = c->conns[n].c.rank[1 - s];
@@ -2247,23 +2158,23 @@ int agx_setup_finalize(agx_ctx* c) {
       if (pp.first == sl.peer) { sl.tag = pp.second++; seen = true; }
     if (!seen) per_peer.emplace_back(sl.peer, 1);
     sl.count = r.count;
-    const bool hb = c->have_ex && c->ex.host_buffers;
-    sl.send = hb ? r.hsend : r.send;
-    sl.recv = hb ? r.hrecv : r.recv;
+    sl.send = hb ? r.hsend.get() : r.send.get();
+    sl.recv = hb ? r.hrecv.get() : r.recv.get();
     c->slabs.push_back(sl);
+    c->remote.push_back(std::move(r));
   }
   if (c->have_ex) {
     const size_t nrec = 1 + (size_t)c->ex.nranks;
-    HIPCHK(hipMalloc((void**)&c->rec_dev, sizeof(agx_ctx::NormRecord) * nrec));
-    HIPCHK(hipHostMalloc((void**)&c->rec_host, sizeof(agx_ctx::NormRecord) * nrec));
+    HIPCHK(c->rec_dev.alloc(nrec));
+    HIPCHK(c->rec_host.alloc(nrec));
   }
   c->n_partials = max_parts;
-  HIPCHK(hipMalloc((void**)&c->partials, sizeof(NormPartial) * max_parts));
+  HIPCHK(c->partials.alloc((size_t)max_parts));
   const size_t nb = std::max<size_t>(c->blocks.size(), 1);
   // [0, nb): norms of the update; [nb, nb + 64): scratch of the two-level fold;
   // [nb + 64, 2 nb + 64): the matrix residual (read back with the update's norms)
-  HIPCHK(hipMalloc((void**)&c->norm_out, sizeof(NormPartial) * (2 * nb + 64)));
-  HIPCHK(hipHostMalloc((void**)&c->norm_host, sizeof(NormPartial) * 2 * nb));
+  HIPCHK(c->norm_out.alloc(2 * nb + 64));
+  HIPCHK(c->norm_host.alloc(2 * nb));
   c->finalized = true;
   return 0;
 }
@@ -2431,7 +2342,7 @@ int wall_pack(agx_ctx* c, int id, int nvar, const int32_t* vars, double* out) {
   if (ghosts_for_output(c)) return 1;
   const int fourth = c->cfg.viscous_recon == AGX_VISC_RECON_CENTRAL_4TH ? 1 : 0;
   hipLaunchKernelGGL(k_wall_pack, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, c->stream,
-                     b.d, c->gas, out_spec(c, b, nvar, vars), b.wall_tab_dev,
+                     b.d, c->gas, out_spec(c, b, nvar, vars), b.wall_tab_dev.get(),
                      (int)b.wall_tab.size(), total, fourth, tmp);
   return copy_out(c, out, tmp, (size_t)nvar * total);
 }
@@ -2548,19 +2459,19 @@ int agx_plot3d_metrics(agx_ctx* c, int ni, int nj, int nk, const double* nodes, 
   MetricsOut o;
   o.vol = dev_out[0]; o.center = dev_out[1];
   for (int d = 0; d < 3; ++d) { o.fa[d] = dev_out[2 + d]; o.fc[d] = dev_out[5 + d]; }
-  HIPCHK(hipMemsetAsync(c->err_dev, 0, sizeof(int), c->stream));
+  HIPCHK(hipMemsetAsync(c->err_dev.get(), 0, sizeof(int), c->stream));
   hipLaunchKernelGGL(k_plot3d_metrics, dim3((unsigned)((nn + 255) / 256)), dim3(256), 0, c->stream,
-                     ni, nj, nk, buf, o, c->err_dev);
+                     ni, nj, nk, buf, o, c->err_dev.get());
   HIPCHK(hipGetLastError());
   for (int q = 0; q < 8; ++q)
     if (host_out[q])
       HIPCHK(hipMemcpyAsync(host_out[q], dev_out[q], sizeof(double) * count[q],
                             hipMemcpyDeviceToHost, c->stream));
-  HIPCHK(hipMemcpyAsync(c->err_host, c->err_dev, sizeof(int), hipMemcpyDeviceToHost, c->stream));
+  HIPCHK(hipMemcpyAsync(c->err_host.get(), c->err_dev.get(), sizeof(int), hipMemcpyDeviceToHost, c->stream));
   HIPCHK(hipStreamSynchronize(c->stream));
-  if (*c->err_host == 4) {
-    *c->err_host = 0;
-    hipMemsetAsync(c->err_dev, 0, sizeof(int), c->stream);
+  if (*c->err_host.get() == 4) {
+    *c->err_host.get() = 0;
+    hipMemsetAsync(c->err_dev.get(), 0, sizeof(int), c->stream);
     return fail("negative volume in PLOT3D block");
   }
   return 0;
@@ -2634,10 +2545,13 @@ int mg_check(agx_ctx* f, agx_ctx* cz, int blk) {
     if (mg_solver_ok(c)) return 1;
   return 0;
 }
-int mg_planes(agx_ctx* c, Block& b, double** p) {     // AGX_NEQ zeroed planes, once
-  if (*p) return 0;
-  HIPCHK(hipMalloc((void**)p, sizeof(double) * AGX_NEQ * b.d.nplane));
-  HIPCHK(hipMemsetAsync(*p, 0, sizeof(double) * AGX_NEQ * b.d.nplane, c->stream));
+// AGX_NEQ zeroed planes, once; *view: the BlockDev member that shows them to the kernels
+int mg_planes(agx_ctx* c, Block& b, DevBuf<double>& p, double** view) {
+  if (!p) {
+    HIPCHK(p.alloc((size_t)AGX_NEQ * b.d.nplane));
+    HIPCHK(hipMemsetAsync(p.get(), 0, sizeof(double) * AGX_NEQ * b.d.nplane, c->stream));
+  }
+  *view = p.get();
   return 0;
 }
 // the device copies of a fine block's transfer maps (uploaded when the host pointer changes)
@@ -2647,8 +2561,8 @@ int mg_maps(agx_ctx* f, Block& b, const int32_t* tc, const double* vf, const dou
   const size_t ncell = (size_t)d.ni * d.nj * d.nk;
   if (tc && b.mg_tc_key != tc) {
     HIPCHK(hipStreamSynchronize(f->stream));
-    if (!b.mg_tc) HIPCHK(hipMalloc((void**)&b.mg_tc, sizeof(int) * 3 * ncell));
-    HIPCHK(hipMemcpy(b.mg_tc, tc, sizeof(int) * 3 * ncell, hipMemcpyHostToDevice));
+    if (!b.mg_tc) HIPCHK(b.mg_tc.alloc(3 * ncell));
+    HIPCHK(hipMemcpy(b.mg_tc.get(), tc, sizeof(int) * 3 * ncell, hipMemcpyHostToDevice));
     // first fine index of every coarse cell, per direction (the map is a product of three
     // monotone 1-D maps: procBlock.cpp:6556-6581)
     std::vector<int> st((size_t)cni + cnj + cnk + 3, 0);
@@ -2668,30 +2582,28 @@ int mg_maps(agx_ctx* f, Block& b, const int32_t* tc, const double* vf, const dou
       }
       while (cc < cn[dir]) ss[dir][++cc] = n[dir];
     }
-    if (b.mg_start) HIPCHK(hipFree(b.mg_start));
-    HIPCHK(hipMalloc((void**)&b.mg_start, sizeof(int) * st.size()));
-    HIPCHK(hipMemcpy(b.mg_start, st.data(), sizeof(int) * st.size(), hipMemcpyHostToDevice));
+    HIPCHK(b.mg_start.upload(st));
     b.mg_tc_key = tc;
   }
   if (vf && b.mg_vf_key != vf) {
     HIPCHK(hipStreamSynchronize(f->stream));
-    if (!b.mg_vf) HIPCHK(hipMalloc((void**)&b.mg_vf, sizeof(double) * ncell));
-    HIPCHK(hipMemcpy(b.mg_vf, vf, sizeof(double) * ncell, hipMemcpyHostToDevice));
+    if (!b.mg_vf) HIPCHK(b.mg_vf.alloc(ncell));
+    HIPCHK(hipMemcpy(b.mg_vf.get(), vf, sizeof(double) * ncell, hipMemcpyHostToDevice));
     b.mg_vf_key = vf;
   }
   if (cf && b.mg_cf_key != cf) {
     HIPCHK(hipStreamSynchronize(f->stream));
-    if (!b.mg_cf) HIPCHK(hipMalloc((void**)&b.mg_cf, sizeof(double) * 7 * ncell));
-    HIPCHK(hipMemcpy(b.mg_cf, cf, sizeof(double) * 7 * ncell, hipMemcpyHostToDevice));
+    if (!b.mg_cf) HIPCHK(b.mg_cf.alloc(7 * ncell));
+    HIPCHK(hipMemcpy(b.mg_cf.get(), cf, sizeof(double) * 7 * ncell, hipMemcpyHostToDevice));
     b.mg_cf_key = cf;
   }
   if (!b.mg_tc) return fail("mg: no fine-to-coarse map for this block yet");
-  m->tc = b.mg_tc;
-  m->start[0] = b.mg_start;
-  m->start[1] = b.mg_start + cni + 1;
+  m->tc = b.mg_tc.get();
+  m->start[0] = b.mg_start.get();
+  m->start[1] = m->start[0] + cni + 1;
   m->start[2] = m->start[1] + cnj + 1;
-  m->vf = b.mg_vf;
-  m->cf = b.mg_cf;
+  m->vf = b.mg_vf.get();
+  m->cf = b.mg_cf.get();
   return 0;
 }
 // the other level's stream has finished what it was given (the two contexts may run on
@@ -2726,8 +2638,7 @@ int agx_mg_restrict(agx_ctx* f, agx_ctx* cz, int blk, int what, const int32_t* t
       HIPCHK(hipMemsetAsync(bc.d.x[e], 0, sizeof(double) * bc.d.nplane, cz->stream));
   } else {
     if (!bf.d.mg_mres) return fail("mg_restrict: the fine level has no matrix residual yet");
-    if (mg_planes(cz, bc, &bc.mg_forcing)) return 1;
-    bc.d.mg_forcing = bc.mg_forcing;
+    if (mg_planes(cz, bc, bc.mg_forcing, &bc.d.mg_forcing)) return 1;
   }
   hipLaunchKernelGGL(k_mg_restrict, cell_grid(bc.d, CELL_BLOCK), CELL_BLOCK, 0, cz->stream, bf.d,
                      bc.d, m, what);
@@ -2749,8 +2660,7 @@ int agx_mg_restrict(agx_ctx* f, agx_ctx* cz, int blk, int what, const int32_t* t
 int agx_mg_matrix_residual(agx_ctx* c, double* mr) {
   if (mg_solver_ok(c)) return 1;
   for (auto& blk : c->blocks) {
-    if (mg_planes(c, blk, &blk.mg_mres)) return 1;
-    blk.d.mg_mres = blk.mg_mres;
+    if (mg_planes(c, blk, blk.mg_mres, &blk.d.mg_mres)) return 1;
     if (mg_x_to_planes(c, blk)) return 1;
   }
   // (the plane form: the diagonal-ordered reductions form the norm only)
@@ -2780,8 +2690,7 @@ int agx_mg_reset_diagonal(agx_ctx* c) {
 
 int agx_mg_save_update(agx_ctx* c) {
   for (auto& blk : c->blocks) {
-    if (mg_planes(c, blk, &blk.mg_xsave)) return 1;
-    blk.d.mg_xsave = blk.mg_xsave;
+    if (mg_planes(c, blk, blk.mg_xsave, &blk.d.mg_xsave)) return 1;
     if (mg_x_to_planes(c, blk)) return 1;
     hipLaunchKernelGGL(k_mg_axpy, dim3((unsigned)((blk.d.nplane + 255) / 256)), dim3(256), 0,
                        c->stream, blk.d, 1);
@@ -2798,17 +2707,17 @@ int agx_mg_prolong(agx_ctx* cz, agx_ctx* f, int blk, const int32_t* tc, const do
   MgMap m;
   if (mg_maps(f, bf, tc, nullptr, cf, bc.d.ni, bc.d.nj, bc.d.nk, &m)) return 1;
   const long nn = (long)(bc.d.ni + 1) * (bc.d.nj + 1) * (bc.d.nk + 1);
-  if (!bc.mg_nodes) HIPCHK(hipMalloc((void**)&bc.mg_nodes, sizeof(double) * AGX_NEQ * nn));
+  if (!bc.mg_nodes) HIPCHK(bc.mg_nodes.alloc((size_t)AGX_NEQ * nn));
   if (mg_x_to_planes(cz, bc) || mg_x_to_planes(f, bf)) return 1;
   hipLaunchKernelGGL(k_mg_axpy, dim3((unsigned)((bc.d.nplane + 255) / 256)), dim3(256), 0,
                      cz->stream, bc.d, 0);
   const dim3 tb = CELL_BLOCK;
   hipLaunchKernelGGL(k_mg_nodes, dim3((bc.d.ni + tb.x) / tb.x, (bc.d.nj + tb.y) / tb.y, bc.d.nk + 1),
-                     tb, 0, cz->stream, bc.d, bc.mg_nodes);
+                     tb, 0, cz->stream, bc.d, bc.mg_nodes.get());
   HIPCHK(hipGetLastError());
   if (mg_order(cz, f)) return 1;
   hipLaunchKernelGGL(k_mg_prolong, cell_grid(bf.d, tb), tb, 0, f->stream, bf.d, m,
-                     (const double*)bc.mg_nodes, bc.d.ni, bc.d.nj, bc.d.nk);
+                     (const double*)bc.mg_nodes.get(), bc.d.ni, bc.d.nj, bc.d.nk);
   mg_x_records(cz, bc);
   mg_x_records(f, bf);
   if (mg_x_from_planes(cz, bc) || mg_x_from_planes(f, bf)) return 1;
@@ -2861,7 +2770,7 @@ int agx_phase_residual(agx_ctx* c, int mm, double cfl) {
       ma.store_consn = store_consn;
       const double rk_alpha[4] = {0.25, 1.0 / 3.0, 0.5, 1.0};   // procBlock.cpp:938
       ma.alpha = rk_alpha[mm & 3];
-      ma.partials = c->partials + off;
+      ma.partials = c->partials.get() + off;
       ma.ablate = getenv("AGX_ABLATE") ? atoi(getenv("AGX_ABLATE")) : 0;
       launch_inv(c, blk.d, cfl, fuse, ma, mp);
       off += mp.nparts;
@@ -2894,14 +2803,11 @@ int agx_phase_residual(agx_ctx* c, int mm, double cfl) {
         rec.ni1 = vb.ni + 1; rec.nj1 = vb.nj + 1;
         rec.nf = (long)rec.ni1 * rec.nj1 * (vb.nk + 1);
         const size_t need = (size_t)3 * RANS_REC * rec.nf;
-        if (need > c->rans_rec_cap) {
-          HIPCHK(hipStreamSynchronize(c->stream));
-          if (c->rans_rec) HIPCHK(hipFree(c->rans_rec));
-          c->rans_rec = nullptr; c->rans_rec_cap = 0;
-          HIPCHK(hipMalloc((void**)&c->rans_rec, sizeof(double) * need));
-          c->rans_rec_cap = need;
+        if (need > c->rans_rec.size()) {
+          HIPCHK(hipStreamSynchronize(c->stream));     // (before the old one is freed)
+          HIPCHK(c->rans_rec.alloc(need));
         }
-        rec.p = c->rans_rec;
+        rec.p = c->rans_rec.get();
         const dim3 tb = CELL_BLOCK;
         auto fgrid = [&](int di, int dj, int dk) {
           return dim3((vb.ni + di + tb.x - 1) / tb.x, (vb.nj + dj + tb.y - 1) / tb.y, vb.nk + dk);
@@ -3009,7 +2915,7 @@ static int implicit_begin(agx_ctx* c, int write_x) {
       hipLaunchKernelGGL(k_zero5, dim3((b.nplane + 255) / 256), dim3(256), 0,
                          c->stream, planes(b.x), b.nplane);
     hipLaunchKernelGGL(k_implicit_begin, cell_grid(b, CELL_BLOCK), CELL_BLOCK, 0,
-                       c->stream, b, c->gas, c->sp, c->err_dev, write_x);
+                       c->stream, b, c->gas, c->sp, c->err_dev.get(), write_x);
     if (b.sw_geo) {
       hipLaunchKernelGGL(k_sweep_records, dim3((unsigned)((b.nplane + 255) / 256)), dim3(256), 0,
                          c->stream, b, c->sp, blk.sweep_geo_built ? 0 : 1);
@@ -3078,7 +2984,7 @@ void matrix_residual_fold(agx_ctx* c, const NormPartial* host, double* mr) {
 
 int agx_phase_matrix_residual(agx_ctx* c, double* mr) {
   const bool defer = c->in_iterate;      // agx_iterate reads it back with the update's norms
-  NormPartial* out = c->norm_out + (defer ? c->blocks.size() + 64 : 0);
+  NormPartial* out = c->norm_out.get() + (defer ? c->blocks.size() + 64 : 0);
   {
     Timer t(c, G_MRESID);
     for (size_t n = 0; n < c->blocks.size(); ++n) {
@@ -3089,17 +2995,17 @@ int agx_phase_matrix_residual(agx_ctx* c, double* mr) {
         const long nwg = mresid_wgs(c, b);
         if (c->mresid_march)
           hipLaunchKernelGGL(k_matrix_resid_d2m, dim3((unsigned)nwg), dim3(256), 0, c->stream, b,
-                             c->gas, c->sp, MRESID_KC, c->partials);
+                             c->gas, c->sp, MRESID_KC, c->partials.get());
         else
           hipLaunchKernelGGL(k_matrix_resid_d2, dim3((unsigned)nwg), dim3(256), 0, c->stream, b,
-                             c->gas, c->sp, c->mresid_split, c->partials);
+                             c->gas, c->sp, c->mresid_split, c->partials.get());
         if (reduce_norms(c, n, nwg, out + n)) return 1;
         continue;
       }
 #endif
       const dim3 grid = cell_grid(b, CELL_BLOCK);
       AGX_BY_MODE(c->sp, k_matrix_resid, grid, CELL_BLOCK, c->stream, b, c->gas, c->sp,
-                  c->partials);
+                  c->partials.get());
       if (reduce_norms(c, n, (long)grid.x * grid.y * grid.z, out + n)) return 1;
     }
   }
@@ -3108,11 +3014,11 @@ int agx_phase_matrix_residual(agx_ctx* c, double* mr) {
     *mr = 0.0;
     return 0;
   }
-  HIPCHK(hipMemcpyAsync(c->norm_host, c->norm_out,
+  HIPCHK(hipMemcpyAsync(c->norm_host.get(), c->norm_out.get(),
                         sizeof(NormPartial) * c->blocks.size(),
                         hipMemcpyDeviceToHost, c->stream));
   HIPCHK(hipStreamSynchronize(c->stream));
-  matrix_residual_fold(c, c->norm_host, mr);
+  matrix_residual_fold(c, c->norm_host.get(), mr);
   return 0;
 }
 
@@ -3128,11 +3034,11 @@ int agx_halo_swap_local(agx_ctx* c, int what) {
   if (c->halo_batch && c->halo_batch_sides > 0) {
     // level by level: every slice of the level, then every insert (halo_batch_plan)
     if (halo_batch_tables(c, what)) return 1;
-    HaloSide* const* tab = c->halo_tab_dev[what][c->halo_set[what]];
+    const auto& tab = c->halo_tab_dev[what][c->halo_set[what]];
     for (const auto& L : c->halo_levels) {
       const dim3 grid((unsigned)((L.nmax + 255) / 256), (unsigned)L.sides);
-      hipLaunchKernelGGL(k_halo_gather_all, grid, dim3(256), 0, c->stream, tab[0] + L.first);
-      hipLaunchKernelGGL(k_halo_scatter_all, grid, dim3(256), 0, c->stream, tab[1] + L.first);
+      hipLaunchKernelGGL(k_halo_gather_all, grid, dim3(256), 0, c->stream, tab[0].get() + L.first);
+      hipLaunchKernelGGL(k_halo_scatter_all, grid, dim3(256), 0, c->stream, tab[1].get() + L.first);
     }
     HIPCHK(hipGetLastError());
     return 0;
@@ -3140,24 +3046,16 @@ int agx_halo_swap_local(agx_ctx* c, int what) {
   for (auto& k : c->conns) {
     const agx_connection& cc = k.c;
     if (!(cc.rank[0] == c->rank && cc.rank[1] == c->rank)) continue;
-    Block& b0 = c->blocks[cc.local_block[0]];
-    Block& b1 = c->blocks[cc.local_block[1]];
     const long n0 = k.side[0].n, n1 = k.side[1].n;
     if (ensure_halo_buf(c, (n0 + n1) * AGX_NEQ)) return 1;
-    double* buf0 = c->halo_buf;                 // what side 0 receives
-    double* buf1 = c->halo_buf + n0 * AGX_NEQ;  // what side 1 receives
     // both slices are taken before either insert (multiArray3d.hpp:810-821)
     const long nmax = std::max(n0, n1);
     if (nmax > 0) {
-      const bool z2 = halo_in_d2(b0, what);
-      HaloSide g0{halo_planes(b1, what), z2 ? k.side[0].src2 : k.side[0].src, n0, buf0};
-      HaloSide g1{halo_planes(b0, what), z2 ? k.side[1].src2 : k.side[1].src, n1, buf1};
-      hipLaunchKernelGGL(k_halo_gather2, dim3((nmax + 255) / 256, 2), dim3(256), 0, c->stream,
-                         g0, g1);
-      HaloSide p0{halo_planes(b0, what), z2 ? k.side[0].dst2 : k.side[0].dst, n0, buf0};
-      HaloSide p1{halo_planes(b1, what), z2 ? k.side[1].dst2 : k.side[1].dst, n1, buf1};
-      hipLaunchKernelGGL(k_halo_scatter2, dim3((nmax + 255) / 256, 2), dim3(256), 0, c->stream,
-                         p0, p1);
+      HaloSide g[2], p[2];      // what side 0 receives, then what side 1 receives
+      halo_sides(c, k, what, c->halo_buf.get(), c->halo_buf.get() + n0 * AGX_NEQ, g, p);
+      const dim3 grid((nmax + 255) / 256, 2);
+      hipLaunchKernelGGL(k_halo_gather2, grid, dim3(256), 0, c->stream, g[0], g[1]);
+      hipLaunchKernelGGL(k_halo_scatter2, grid, dim3(256), 0, c->stream, p[0], p[1]);
     }
   }
   HIPCHK(hipGetLastError());
@@ -3186,7 +3084,7 @@ int agx_halo_pack(agx_ctx* c, int id, int what, double* dev_buf) {
   const long n = k.n_send;
   if (n) hipLaunchKernelGGL(k_halo_gather, dim3((n + 255) / 256), dim3(256), 0,
                             c->stream, halo_planes(b, what),
-                            halo_in_d2(b, what) ? k.send_src2 : k.send_src, n, dev_buf);
+                            k.send_src[halo_in_d2(b, what)].get(), n, dev_buf);
   HIPCHK(hipGetLastError());
   return 0;
 }
@@ -3201,7 +3099,7 @@ int agx_halo_unpack(agx_ctx* c, int id, int what, const double* dev_buf) {
   const long n = k.side[s].n;
   if (n) hipLaunchKernelGGL(k_halo_scatter, dim3((n + 255) / 256), dim3(256), 0,
                             c->stream, halo_planes(b, what),
-                            halo_in_d2(b, what) ? k.side[s].dst2 : k.side[s].dst, n, dev_buf);
+                            k.side[s].map[halo_in_d2(b, what)].dst.get(), n, dev_buf);
   HIPCHK(hipGetLastError());
   return 0;
 }
@@ -3279,10 +3177,10 @@ static int halo_exchange_remote(agx_ctx* c, int what) {
   if (!c->have_ex) return fail("connections to other ranks need an exchange (agx_set_exchange)");
   Timer t(c, G_BC);
   for (auto& r : c->remote)
-    if (agx_halo_pack(c, r.cid, what, r.send)) return 1;
+    if (agx_halo_pack(c, r.cid, what, r.send.get())) return 1;
   if (c->ex.host_buffers) {
     for (auto& r : c->remote)
-      HIPCHK(hipMemcpyAsync(r.hsend, r.send, sizeof(double) * r.count, hipMemcpyDeviceToHost,
+      HIPCHK(hipMemcpyAsync(r.hsend.get(), r.send.get(), sizeof(double) * r.count, hipMemcpyDeviceToHost,
                             c->stream));
     HIPCHK(hipStreamSynchronize(c->stream));
   }
@@ -3290,10 +3188,10 @@ static int halo_exchange_remote(agx_ctx* c, int what) {
     return g_err[0] ? 1 : fail("the exchange's swap operation failed");
   if (c->ex.host_buffers)
     for (auto& r : c->remote)
-      HIPCHK(hipMemcpyAsync(r.recv, r.hrecv, sizeof(double) * r.count, hipMemcpyHostToDevice,
+      HIPCHK(hipMemcpyAsync(r.recv.get(), r.hrecv.get(), sizeof(double) * r.count, hipMemcpyHostToDevice,
                             c->stream));
   for (auto& r : c->remote)
-    if (agx_halo_unpack(c, r.cid, what, r.recv)) return 1;
+    if (agx_halo_unpack(c, r.cid, what, r.recv.get())) return 1;
   return 0;
 }
 
@@ -3368,22 +3266,22 @@ int reduce_over_ranks(agx_ctx* c, double* l2, agx_linf* linf, double* matrix_res
                       const double* l2_in, const agx_linf& linf_in, int status) {
   typedef agx_ctx::NormRecord Rec;
   const int nr = c->ex.nranks;
-  Rec& mine = c->rec_host[0];
+  Rec& mine = c->rec_host.get()[0];
   memset(&mine, 0, sizeof mine);
   for (int e = 0; e < AGX_NEQ; ++e) mine.l2[e] = l2[e] - l2_in[e];   // this call's local sums
   mine.mres = *matrix_resid;
   mine.linf = linf->linf; mine.block = linf->block; mine.i = linf->i; mine.j = linf->j;
   mine.k = linf->k; mine.eqn = linf->eqn;
   mine.status = status;
-  Rec* all = c->rec_host + 1;
+  Rec* all = c->rec_host.get() + 1;
   if (c->ex.host_buffers) {
     if (c->ex.allgather(c->ex.user, &mine, all, (int64_t)sizeof(Rec), c->stream))
       return g_err[0] ? 1 : fail("the exchange's allgather operation failed");
   } else {
-    HIPCHK(hipMemcpyAsync(c->rec_dev, &mine, sizeof(Rec), hipMemcpyHostToDevice, c->stream));
-    if (c->ex.allgather(c->ex.user, c->rec_dev, c->rec_dev + 1, (int64_t)sizeof(Rec), c->stream))
+    HIPCHK(hipMemcpyAsync(c->rec_dev.get(), &mine, sizeof(Rec), hipMemcpyHostToDevice, c->stream));
+    if (c->ex.allgather(c->ex.user, c->rec_dev.get(), c->rec_dev.get() + 1, (int64_t)sizeof(Rec), c->stream))
       return 1;
-    HIPCHK(hipMemcpyAsync(all, c->rec_dev + 1, sizeof(Rec) * nr, hipMemcpyDeviceToHost,
+    HIPCHK(hipMemcpyAsync(all, c->rec_dev.get() + 1, sizeof(Rec) * nr, hipMemcpyDeviceToHost,
                           c->stream));
     HIPCHK(hipStreamSynchronize(c->stream));
   }
@@ -3482,7 +3380,7 @@ int agx_iterate(agx_ctx* c, int mm, double cfl, double* l2, agx_linf* linf,
     AGX_PHASE(agx_phase_matrix_residual(c, matrix_resid));
     AGX_PHASE(agx_phase_implicit_update(c, mm, l2, linf));
     if (!st && c->mres_deferred)      // came back with the update's norms
-      matrix_residual_fold(c, c->norm_host + c->blocks.size(), matrix_resid);
+      matrix_residual_fold(c, c->norm_host.get() + c->blocks.size(), matrix_resid);
     c->mres_deferred = false;
   } else {
     AGX_PHASE(agx_phase_explicit_update(c, mm, l2, linf));

@@ -2263,19 +2263,17 @@ __global__ void k_bc_edges(BlockDev b, GasDev g, int viscous, int* err) {
 // rec[q * SW_DYN + SW_X + e]
 struct Planes5 { double* p[AGX_NEQ]; long stride; double* rec; };
 constexpr int SW_GEO = 16, SW_DYN = 32, SW_RHS = 8, SW_X = 24;
-// both sides of one local connection in one launch (blockIdx.y = side)
+// one side of a connection: the planes it reads or writes, the index map, its n cells and
+// its part of the buffer.  A view: the host owns what it points to.
 struct HaloSide { Planes5 a; const long* map; long n; double* buf; };
-__global__ void k_halo_gather2(HaloSide s0, HaloSide s1) {
-  const HaloSide& s = blockIdx.y == 0 ? s0 : s1;
-  const long t = (long)blockIdx.x * blockDim.x + threadIdx.x;
+// cell t of a side: slice (gather) and insert (scatter)
+__device__ __forceinline__ void halo_gather_side(const HaloSide& s, long t) {
   if (t >= s.n) return;
   const long q = s.map[t];
 #pragma unroll
   for (int e = 0; e < AGX_NEQ; ++e) s.buf[e * s.n + t] = s.a.p[e][q * s.a.stride];
 }
-__global__ void k_halo_scatter2(HaloSide s0, HaloSide s1) {
-  const HaloSide& s = blockIdx.y == 0 ? s0 : s1;
-  const long t = (long)blockIdx.x * blockDim.x + threadIdx.x;
+__device__ __forceinline__ void halo_scatter_side(const HaloSide& s, long t) {
   if (t >= s.n) return;
   const long q = s.map[t];
 #pragma unroll
@@ -2284,50 +2282,33 @@ __global__ void k_halo_scatter2(HaloSide s0, HaloSide s1) {
     s.a.p[e][q * s.a.stride] = v;
     if (s.a.rec) s.a.rec[q * SW_DYN + SW_X + e] = v;
   }
+}
+// both sides of one local connection in one launch (blockIdx.y = side)
+__global__ void k_halo_gather2(HaloSide s0, HaloSide s1) {
+  halo_gather_side(blockIdx.y == 0 ? s0 : s1, (long)blockIdx.x * blockDim.x + threadIdx.x);
+}
+__global__ void k_halo_scatter2(HaloSide s0, HaloSide s1) {
+  halo_scatter_side(blockIdx.y == 0 ? s0 : s1, (long)blockIdx.x * blockDim.x + threadIdx.x);
 }
 // all local connections of a rank in one launch per direction (blockIdx.y: side of the
 // table; the table sits in device memory and is wave-uniform: scalar loads).  A 2 x 2 x 2 cube
 // of blocks has twelve connections and exchanges six times per DPLUR iteration: 72 launch
 // pairs of ~7.5 us each were a tenth of the iteration.
 __global__ void k_halo_gather_all(const HaloSide* __restrict__ tab) {
-  const HaloSide& s = tab[blockIdx.y];
-  const long t = (long)blockIdx.x * blockDim.x + threadIdx.x;
-  if (t >= s.n) return;
-  const long q = s.map[t];
-#pragma unroll
-  for (int e = 0; e < AGX_NEQ; ++e) s.buf[e * s.n + t] = s.a.p[e][q * s.a.stride];
+  halo_gather_side(tab[blockIdx.y], (long)blockIdx.x * blockDim.x + threadIdx.x);
 }
 __global__ void k_halo_scatter_all(const HaloSide* __restrict__ tab) {
-  const HaloSide& s = tab[blockIdx.y];
-  const long t = (long)blockIdx.x * blockDim.x + threadIdx.x;
-  if (t >= s.n) return;
-  const long q = s.map[t];
-#pragma unroll
-  for (int e = 0; e < AGX_NEQ; ++e) {
-    const double v = s.buf[e * s.n + t];
-    s.a.p[e][q * s.a.stride] = v;
-    if (s.a.rec) s.a.rec[q * SW_DYN + SW_X + e] = v;
-  }
+  halo_scatter_side(tab[blockIdx.y], (long)blockIdx.x * blockDim.x + threadIdx.x);
 }
+// one side, to or from a caller's buffer (agx_halo_pack / agx_halo_unpack)
 __global__ void k_halo_gather(Planes5 a, const long* __restrict__ src, long n,
                               double* __restrict__ buf) {
-  const long t = (long)blockIdx.x * blockDim.x + threadIdx.x;
-  if (t >= n) return;
-  const long q = src[t];
-#pragma unroll
-  for (int e = 0; e < AGX_NEQ; ++e) buf[e * n + t] = a.p[e][q * a.stride];
+  halo_gather_side(HaloSide{a, src, n, buf}, (long)blockIdx.x * blockDim.x + threadIdx.x);
 }
 __global__ void k_halo_scatter(Planes5 a, const long* __restrict__ dst, long n,
                                const double* __restrict__ buf) {
-  const long t = (long)blockIdx.x * blockDim.x + threadIdx.x;
-  if (t >= n) return;
-  const long q = dst[t];
-#pragma unroll
-  for (int e = 0; e < AGX_NEQ; ++e) {
-    const double v = buf[e * n + t];
-    a.p[e][q * a.stride] = v;
-    if (a.rec) a.rec[q * SW_DYN + SW_X + e] = v;
-  }
+  halo_scatter_side(HaloSide{a, dst, n, const_cast<double*>(buf)},
+                    (long)blockIdx.x * blockDim.x + threadIdx.x);
 }
 
 // ---------------------------------------------------------------------------

@@ -83,6 +83,18 @@ def read_output(case, path, n_steps, rank=None):
     return hist, states
 
 
+def test_memory_owners_free_exactly_once():
+    """tests/cpp/host_mem.cpp: the owner template of csrc/agx_mem.hpp over a counting malloc
+    backend, built with the address and undefined-behaviour sanitizers -- scopes, repeated and
+    failing allocations, moves, growing vectors, reserve and upload leave no allocation live
+    and free none twice."""
+    subprocess.check_call(["make", "-C", CPP, "host_mem"], stdout=subprocess.DEVNULL)
+    r = subprocess.run([os.path.join(CPP, "host_mem")], stdout=subprocess.PIPE,
+                       stderr=subprocess.STDOUT, timeout=120)
+    assert r.returncode == 0, r.stdout.decode()
+    assert b"host_mem OK" in r.stdout
+
+
 CASES = {
     "rk4_muscl_roe": dict(n=(20, 9, 8), stretch=1.15, skew=0.01, time_integration="rk4",
                           cfl=0.5),
