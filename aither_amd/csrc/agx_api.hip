@@ -15,6 +15,8 @@
 #include <cstdlib>
 #include <cmath>
 #include <vector>
+#include <array>
+#include <map>
 #include <string>
 #include <algorithm>
 
@@ -224,6 +226,12 @@ struct agx_ctx {
   bool halo_tab_valid[5][2] = {};
   int halo_set[5] = {};
   PinnedBuf<HaloSide> halo_tab_host;      // staging, 2 * sides entries
+  // the order in which the tile kernels' workgroups visit their (column, k) steps
+  // (agx_tile_plan.hpp); AGX_TILE_ORDER=step|column sets both.  Each kernel's default is the
+  // order that measured faster at 256^3
+  int tile_order_inv = TILE_ORDER_STEP;      // k_residual_tile
+  int tile_order_visc = TILE_ORDER_STEP;     // k_visc_tile
+  std::map<std::array<int, 6>, TilePlan> tile_plans;   // (made once per shape)
   int mresid_split = 1;      // bands of diagonals per XCD in k_matrix_resid_d2 (AGX_MRESID_SPLIT)
   bool mresid_march = true;  // AGX_MRESID=plane: one plane position per thread (comparison form)
   bool have_time_n = false;  // agx_store_time_n has run (nonreflecting BCs read consVarsN)
@@ -506,7 +514,7 @@ int check_device_error(agx_ctx* c) {
   return 0;
 }
 
-struct MarchPlan { dim3 grid; int kchunk; long nparts; };
+struct MarchPlan { dim3 grid; int kchunk; long nparts; TilePlan tile; };
 int g_march_tj = 6;   // cell rows per workgroup (512 threads)
 // the tile kernel addresses a plane with 32-bit byte offsets (SlabDev::ldb)
 bool tile_ok(const agx_ctx* c, const BlockDev& b) {
@@ -517,9 +525,18 @@ bool all_tile_ok(const agx_ctx* c) {
     if (!tile_ok(c, blk.d)) return false;
   return true;
 }
-MarchPlan march_plan(const agx_ctx* c, const BlockDev& b) {
+// the plan of gx x gy column tiles on P workgroups, made once per shape and charge
+TilePlan tile_plan_of(agx_ctx* c, int gx, int gy, int nk, int P, int charge, int order) {
+  const std::array<int, 6> key = {gx, gy, nk, P, charge, order};
+  auto it = c->tile_plans.find(key);
+  if (it == c->tile_plans.end())
+    it = c->tile_plans.emplace(key, tile_plan_make(gx, gy, nk, P, charge, order)).first;
+  return it->second;
+}
+MarchPlan march_plan(agx_ctx* c, const BlockDev& b) {
   MarchPlan p;
-  const int gx = (b.ni + 63) / 64, gy = (b.nj + g_march_tj - 1) / g_march_tj;
+  const int gx = tile_count(b.ni, TILE_INV_I), gy = tile_count(b.nj, g_march_tj);
+  p.tile = tile_plan_column(gx * gy, b.nk);
   if (tile_ok(c, b)) {
     // persistent workgroups, one per CU (LDS allows no more); small blocks get
     // fewer so that a range is at least ~8 steps long
@@ -529,6 +546,8 @@ MarchPlan march_plan(const agx_ctx* c, const BlockDev& b) {
     p.kchunk = 0;
     p.grid = dim3((unsigned)np);
     p.nparts = np;
+    const int halo = c->cfg.recon == AGX_RECON_CONSTANT ? 1 : (c->cfg.recon == AGX_RECON_MUSCL ? 2 : 3);
+    p.tile = tile_plan_of(c, gx, gy, b.nk, (int)np, tile_charge_inviscid(halo), c->tile_order_inv);
     return p;
   }
   // aim at >= ~2048 workgroups so that all 256 CUs stay busy to the end
@@ -1529,6 +1548,13 @@ int agx_ctx_create(int device, int rank, agx_ctx** out) {
     if (const char* w = getenv("AGX_VISC")) {
       c->visc_gather = !strcmp(w, "gather");
       c->visc_march = !strcmp(w, "march");
+    }
+    if (const char* w = getenv("AGX_TILE_ORDER")) {
+      if (strcmp(w, "step") && strcmp(w, "column")) {
+        delete c;
+        return fail("AGX_TILE_ORDER is '%s': step or column", w);
+      }
+      c->tile_order_inv = c->tile_order_visc = !strcmp(w, "step") ? TILE_ORDER_STEP : TILE_ORDER_COLUMN;
     }
     if (const char* w = getenv("AGX_EAGER_GHOSTS")) c->eager_ghosts = atoi(w) != 0;
     if (const char* w = getenv("AGX_OVERLAP")) c->overlap = atoi(w) != 0;
@@ -2772,6 +2798,7 @@ int agx_phase_residual(agx_ctx* c, int mm, double cfl) {
       ma.alpha = rk_alpha[mm & 3];
       ma.partials = c->partials.get() + off;
       ma.ablate = getenv("AGX_ABLATE") ? atoi(getenv("AGX_ABLATE")) : 0;
+      ma.plan = mp.tile;
       launch_inv(c, blk.d, cfl, fuse, ma, mp);
       off += mp.nparts;
       if (c->sp.implicit && c->sp.block) launch_block_diag(c, blk.d);
@@ -2840,18 +2867,21 @@ int agx_phase_residual(agx_ctx* c, int mm, double cfl) {
         }
 #if AGX_FAST
         // 62 x 6 owned cells per workgroup and k-step (centralFourth: 60 x 6); persistent
-        // workgroups, one per CU (the kernel's LDS windows fill a CU), each marching an equal
-        // share of the (column tile, k) steps
-        const int oi = fourth ? VT_L - 4 : VT_OI;
-        const int gx = (vb.ni + oi - 1) / oi, gy = (vb.nj + VT_OJ - 1) / VT_OJ;
+        // workgroups, one per CU (the kernel's LDS windows fill a CU), each marching its share
+        // of the (column tile, k) steps by the plan (agx_tile_plan.hpp)
+        const int gx = tile_count(vb.ni, fourth ? TILE_VISC_I_F4 : TILE_VISC_I);
+        const int gy = tile_count(vb.nj, TILE_J);
         const long steps = (long)gx * gy * vb.nk;
         const int nwg = (int)std::min<long>(c->num_cu, std::max<long>(1, steps / 8));
+        const TilePlan tp = tile_plan_of(c, gx, gy, vb.nk, nwg,
+                                         fourth ? TILE_CHARGE_VISC_F4 : TILE_CHARGE_VISC,
+                                         c->tile_order_visc);
         if (fourth)
           hipLaunchKernelGGL(k_visc_tile<true>, dim3(nwg), dim3(VT_L, VT_R), 0, c->stream,
-                             make_slab(vb), c->gas, c->sp, cfl, gx, gy);
+                             make_slab(vb), c->gas, c->sp, cfl, gx, tp);
         else
           hipLaunchKernelGGL(k_visc_tile<false>, dim3(nwg), dim3(VT_L, VT_R), 0, c->stream,
-                             make_slab(vb), c->gas, c->sp, cfl, gx, gy);
+                             make_slab(vb), c->gas, c->sp, cfl, gx, tp);
 #endif
       }
     }

@@ -13,6 +13,7 @@
 #pragma once
 #include "agx_device.hpp"
 #include "agx_lusgs.hpp"
+#include "agx_tile_plan.hpp"
 
 namespace agx {
 
@@ -368,7 +369,26 @@ struct MarchArgs {
                            // 16 no spectral radius, 32 idle halo waves,
                            // 64 no tile publish, 128 no prefetch loads
   NormPartial* partials;   // FUSE: one per workgroup
+  TilePlan plan;           // k_residual_tile: the workgroups' ranges (agx_tile_plan.hpp)
 };
+
+// The next segment of a workgroup's range (agx_tile_plan.hpp), held in SGPRs.  The plan's
+// divisions run on the vector unit; what they return is the same in every lane, but left in
+// VGPRs it stays there across the whole march (2 - 3 registers the WENO instances lack).
+__device__ __forceinline__ TileWalk tile_walk_begin(const TilePlan& p) {
+  const int P = gridDim.x;
+  TileWalk w = tile_plan_range(p, tile_range_of((int)blockIdx.x, P), P);
+  w.v = __builtin_amdgcn_readfirstlane(w.v); w.v1 = __builtin_amdgcn_readfirstlane(w.v1);
+  return w;
+}
+__device__ __forceinline__ bool tile_walk_next(const TilePlan& p, TileWalk& w, TileSeg& s) {
+  const bool more = tile_plan_next(p, w, s);
+  w.v = __builtin_amdgcn_readfirstlane(w.v);
+  s.col = __builtin_amdgcn_readfirstlane(s.col);
+  s.k0 = __builtin_amdgcn_readfirstlane(s.k0);
+  s.k1 = __builtin_amdgcn_readfirstlane(s.k1);
+  return __builtin_amdgcn_readfirstlane((int)more) != 0;
+}
 
 // Left/right states at the lower d-face of cell qc, reconstructed variable by
 // variable straight from the SoA planes (only the 2x5 face values stay live).
@@ -708,22 +728,15 @@ k_residual_tile(SlabDev b, GasDev g, SolverDev sp, double cfl, MarchArgs ma) {
     sLin[wv][lane] = 0x7fffffffffffffffLL;
   }
   // Persistent workgroups (one per CU): the (column tile, k) steps of the block
-  // are one linear sequence cut into gridDim.x equal ranges, so every CU
-  // finishes together whatever the block shape; a range that crosses into the
-  // next column re-primes its window there.  Workgroup n runs on XCD n % 8:
-  // ranges are dealt so that each XCD's L2 sees neighbouring columns.
-  const int gx = (b.ni + 63) / 64, gy = (b.nj + TJ - 1) / TJ;
-  const long S = (long)gx * gy * b.nk;
-  const int P = gridDim.x;
-  const int rr = P % 8 == 0 ? (int)(blockIdx.x % 8) * (P / 8) + (int)(blockIdx.x / 8)
-                            : (int)blockIdx.x;
-  long s_pos = S * rr / P;
-  const long s_end = S * (rr + 1) / P;
-  while (s_pos < s_end) {
-  const int col = (int)(s_pos / b.nk);
-  const int k0 = (int)(s_pos - (long)col * b.nk);
-  const int k1 = (int)min((long)b.nk, k0 + (s_end - s_pos));
-  s_pos += k1 - k0;
+  // are one linear sequence cut into gridDim.x ranges of equal cost, so every CU
+  // finishes together whatever the block shape; a segment that starts in another
+  // column or chunk re-primes its window there.  The sequence, its cut and the
+  // dealing of ranges to XCDs are the plan's (agx_tile_plan.hpp, ma.plan).
+  const int gx = tile_count(b.ni, TILE_INV_I);
+  TileWalk walk = tile_walk_begin(ma.plan);
+  TileSeg seg;
+  while (tile_walk_next(ma.plan, walk, seg)) {
+  const int col = seg.col, k0 = seg.k0, k1 = seg.k1;
   const int i0 = (col % gx) * 64, j0 = (col / gx) * TJ;
   const int itop = min(i0 + 64, b.ni), jtop = min(j0 + TJ, b.nj);
   if (wv < TJ) {
@@ -1005,7 +1018,9 @@ k_residual_tile(SlabDev b, GasDev g, SolverDev sp, double cfl, MarchArgs ma) {
 #pragma unroll
           for (int e = 0; e < AGX_NEQ; ++e) {
             sNorm[e][wv][lane] += res[e] * res[e];
-            if (res[e] > vm) { vm = res[e]; vl = lin0 + e; }
+            // (greater, or equal with the smaller index, as every fold: whichever order the
+            // plan visits the cells in, the record is the same)
+            if (res[e] > vm || (res[e] == vm && lin0 + e < vl)) { vm = res[e]; vl = lin0 + e; }
           }
           sNorm[AGX_NEQ][wv][lane] = vm;
           sLin[wv][lane] = vl;

@@ -20,11 +20,14 @@
 // 62 x 6 cells are owned per workgroup.  Per thread and step: ~45 vector-memory
 // instructions, every plane of the block read once per workgroup.
 #pragma once
+#include "agx_tile_plan.hpp"
 
 namespace agx {
 
 constexpr int VT_L = 64, VT_R = 8;           // threads: lanes (i) x rows (j)
 constexpr int VT_OI = VT_L - 2, VT_OJ = VT_R - 2;   // owned cells per workgroup
+static_assert(VT_OI == TILE_VISC_I && VT_L - 4 == TILE_VISC_I_F4 && VT_OJ == TILE_J,
+              "the plan's tile sizes (agx_tile_plan.hpp) are this kernel's");
 // LDS: what a thread publishes for its neighbours, [var][row][lane]
 enum { VS_S0 = 0, VS_SM = 4, VS_SP = 8, VS_AI0 = 12, VS_AJ0 = 15, VS_AJ1 = 18, VS_AK0 = 21,
        VS_AK1 = 24, VS_VOL = 27, VS_WJ = 28, VS_RHO = 29, VS_MU = 30, VS_AI1 = 31, VS_WI = 34,
@@ -188,11 +191,11 @@ __device__ __forceinline__ void vt_face(VShared sh, const GasDev& g, const VRef&
 }
 
 // Persistent: one workgroup per CU; the (column tile, k) steps of the block form one linear
-// sequence cut into gridDim.x equal ranges (a range that crosses into the next column
-// re-primes its window there), so all CUs finish together whatever the block shape --
-// with a grid of (tiles x k-chunks) workgroups at one workgroup per CU the last round ran
-// a fifth full.  Workgroup n runs on XCD n % 8: ranges are dealt so that each XCD's L2
-// sees neighbouring columns.
+// sequence cut into gridDim.x ranges of equal cost (a segment that starts in another column
+// or chunk re-primes its window there), so all CUs finish together whatever the block shape
+// -- with a grid of (tiles x k-chunks) workgroups at one workgroup per CU the last round ran
+// a fifth full.  The sequence, its cut and the dealing of ranges to XCDs are the plan's
+// (agx_tile_plan.hpp): `tp` is made by the host with this kernel's charge.
 //
 // F4 (centralFourth): a face's state reaches two cells to either side.  Along i the window
 // simply owns two lanes less (lanes 2 .. 61; 0, 1 and 63 only supply data); along j rows 1 and 7
@@ -201,22 +204,15 @@ __device__ __forceinline__ void vt_face(VShared sh, const GasDev& g, const VRef&
 // rho, mu and the k-width of plane kk-1 stay in registers.
 template <bool F4>
 __global__ void __launch_bounds__(VT_L * VT_R)
-k_visc_tile(SlabDev b, GasDev g, SolverDev sp, double cfl, int gx, int gy) {
+k_visc_tile(SlabDev b, GasDev g, SolverDev sp, double cfl, int gx, TilePlan tp) {
   __shared__ double sh[VT_R][VT_L][VS_COUNT];
   constexpr int LO = F4 ? 2 : 1;                        // first owning lane
   constexpr int OI = F4 ? VT_L - 4 : VT_OI;             // owned cells along i
   const int l = threadIdx.x, ty = threadIdx.y;
-  const long S = (long)gx * gy * b.nk;
-  const int P = gridDim.x;
-  const int rr = P % 8 == 0 ? (int)(blockIdx.x % 8) * (P / 8) + (int)(blockIdx.x / 8)
-                            : (int)blockIdx.x;
-  long s_pos = S * rr / P;
-  const long s_end = S * (rr + 1) / P;
-  while (s_pos < s_end) {
-  const int col = (int)(s_pos / b.nk);
-  const int k0 = (int)(s_pos - (long)col * b.nk);
-  const int k1 = (int)min((long)b.nk, k0 + (s_end - s_pos));
-  s_pos += k1 - k0;
+  TileWalk walk = tile_walk_begin(tp);
+  TileSeg seg;
+  while (tile_walk_next(tp, walk, seg)) {
+  const int col = seg.col, k0 = seg.k0, k1 = seg.k1;
   const int ci = (col % gx) * OI - LO + l, cj = (col / gx) * VT_OJ - 1 + ty;
   const bool inner = l >= LO && l < LO + OI && ty >= 1 && ty <= VT_OJ;
   const bool own = inner && ci < b.ni && cj < b.nj;

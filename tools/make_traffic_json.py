@@ -23,12 +23,22 @@ PASS_OF = [("k_residual_tile", "R"), ("k_inv_residual", "R"), ("k_block_diag", "
            ("k_dplur", "4"), ("k_matrix_resid", "M"), ("k_update", "U"), ("k_norm_final", "U")]
 
 
+def newest(wl):
+    """The PMC summary of a workload from round `rnd`, or from the last round before it that
+    measured the workload (a round re-measures only what it changed)."""
+    for n in range(int(rnd[1:]), 0, -1):
+        path = f"profiles/r{n:02d}_{wl}_pmc_traffic.json"
+        if os.path.exists(path):
+            return path
+    return f"profiles/{rnd}_{wl}_pmc_traffic.json"
+
+
 def bytes_of(v):
     return v.get("FETCH_SIZE", 0.0) * 1024 * 2 + v.get("WRITE_SIZE", 0.0) * 1024
 
 
 out = {}
-path = f"profiles/{rnd}_rk4_pmc_traffic.json"
+path = newest("rk4")
 if os.path.exists(path):
     pm = json.load(open(path))
     tiles = {k: v for k, v in pm.items() if "k_residual_tile" in k}
@@ -42,7 +52,7 @@ if os.path.exists(path):
         "algorithmic_bytes": 296 * 256 ** 3, "method": METHOD, "source": path}
 RANS_BYTES = 8 * ((7 + 19 + 7 + 3 + 29) + 2 * (7 * 7 + 19 + 29 + 7) + (7 * 7 + 19 + 29) + 3 * 7)
 for wl, cells in (("lusgs", 256 ** 3), ("dplur8", 8 * 128 ** 3), ("rans4", 4 * 128 * 128 * 64)):
-    path = f"profiles/{rnd}_{wl}_pmc_traffic.json"
+    path = newest(wl)
     if not os.path.exists(path):
         continue
     pm = json.load(open(path))
