@@ -2292,7 +2292,11 @@ int agx_field_download(agx_ctx* c, int id, int field, double* out) {
   if (flush_consn(c)) return 1;
   if (id < 0 || id >= (int)c->blocks.size()) return fail("bad block id %d", id);
   Block& b = c->blocks[id];
-  if (field == AGX_FIELD_UPDATE && b.d.d2.base && d2_x_copy(c, b, 0)) return 1;
+  // (the D2 arrays hold x with the writer's tag in its two lowest mantissa bits: while the
+  // planes are current -- an upload or a multigrid transfer wrote them last -- they are the
+  // untagged x itself, zero ghost cells of a restriction included)
+  if (field == AGX_FIELD_UPDATE && b.d.d2.base && !b.x_planes_current && d2_x_copy(c, b, 0))
+    return 1;
   if (field >= AGX_FIELD_VEL_GRAD && field <= AGX_FIELD_PRESS_GRAD) {
     // cell-centre gradients: formed on demand into a temporary (an output path)
     const long ncell = (long)b.d.ni * b.d.nj * b.d.nk;
@@ -2519,7 +2523,9 @@ int agx_nearest_wall_distance(agx_ctx* c, int64_t ncell, const double* cen, int6
 }
 
 int agx_field_upload(agx_ctx* c, int id, int field, const double* in) {
-  x_changed(c);
+  // (an upload of x writes this block's planes and, on the D2 path, copies them to its D2
+  // arrays below: the planes of this block are current afterwards, those of the other blocks
+  // are what they were)
   c->ghosts_prefilled = false;
   c->state_is_time_n = false;
   if (flush_consn(c)) return 1;
@@ -2550,8 +2556,8 @@ int mg_solver_ok(agx_ctx* c) {
 }
 // On the diagonal-ordered LU-SGS path x lives in the D2 arrays; the multigrid kernels work on
 // the planes: current planes before they read, the D2 arrays (tagged) after they wrote.
-// (x_planes_current: nothing wrote the D2 x since the last copy -- sweeps, exchanges, the
-// prepare kernel and uploads clear it, x_changed)
+// (x_planes_current: nothing wrote the D2 x since the last copy -- sweeps, exchanges and the
+// prepare kernel clear it, x_changed; an upload of x copies the block's planes itself)
 int mg_x_to_planes(agx_ctx* c, Block& b) {
   return b.d.d2.base && !b.x_planes_current ? d2_x_copy(c, b, 0) : 0;
 }

@@ -482,6 +482,16 @@ class MultigridSolver:
         api.check(api.halo_exchange(s.ctx, abi.HALO_STATE), "halo_exchange")
         api.check(api.phase_bc_edges(s.ctx), "phase_bc_edges")
         api.check(api.phase_residual(s.ctx, mm, cfl), "phase_residual")
+        # gridLevel::CalcResidual ends with SwapEddyViscAndGradients and, for rans,
+        # SwapTurbVars (gridLevel.cpp:386-392); Restriction calls it on the coarse level
+        # (:559-563), so every level makes these swaps, as PhasedSolver.iterate does
+        cfg = s.cfg
+        block = cfg.matrix_solver in (abi.SOLVER["blusgs"], abi.SOLVER["bdplur"])
+        if block and cfg.is_viscous:
+            api.check(api.halo_exchange(s.ctx, abi.HALO_VELGRAD_A), "halo_exchange")
+            api.check(api.halo_exchange(s.ctx, abi.HALO_VELGRAD_B), "halo_exchange")
+        if cfg.n_eq == 7:
+            api.check(api.halo_exchange(s.ctx, abi.HALO_TURB), "halo_exchange")
 
     # -- linearSolver::Relax (linearSolver.cpp:430-470, :509-536) ---------------
     def relax(self, lev, sweeps):

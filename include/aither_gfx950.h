@@ -475,7 +475,16 @@ int agx_nearest_wall_distance(agx_ctx *ctx, int64_t ncell, const double *cell_ce
  * diagonal-ordered production path and in its hyperplane form); the turbulence equations of
  * the 7-equation library are restricted, forced and prolonged like the flow equations, as
  * the reference's transfers on varArray do.  `to_coarse` [nk][nj][ni][3] (int32, host):
- * the coarse cell (i, j, k) of every physical cell of the fine block. */
+ * the coarse cell (i, j, k) of every physical cell of the fine block.
+ * The device copies of `to_coarse`, `vol_fac` and `coeffs` are keyed on the HOST POINTER, per
+ * fine block: an array is uploaded when its pointer differs from the one of the previous
+ * call.  The arrays must therefore stay alive and unchanged for as long as the fine context
+ * lives (gridLevel keeps them as members); freeing one and passing another at the same
+ * address, or changing one in place, leaves the device with the old contents.
+ * The caller's cycle makes the swaps that end gridLevel::CalcResidual after the
+ * agx_phase_residual of EVERY level (gridLevel.cpp:386-392; Restriction :559-563 calls
+ * CalcResidual on the coarse level): AGX_HALO_VELGRAD_A and _B for a viscous block-matrix
+ * solver, AGX_HALO_TURB for seven equations -- the conditions of agx_iterate. */
 enum { AGX_MG_STATE = 0, AGX_MG_UPDATE = 1, AGX_MG_FORCING = 2 };
 /* BlockRestriction (procBlock.hpp:636-690) of
  *   AGX_MG_STATE    the primitive state, volume weighted (procBlock::Restriction :6847);

@@ -231,6 +231,8 @@ class multigrid {
   int mgCycleIndex_ = 1;                          // V: 1, W: 2
   int matrixSweeps_ = 1;
   bool lusgs_ = false;
+  bool swapGradients_ = false;                    // block-matrix solver, viscous
+  bool swapTurbVars_ = false;                     // rans
 
   static void Check(int rc, const char *what) { hotPath::Check(rc, what); }
   AGX_CAT(AGX_SYMBOL_PREFIX, ctx) *Ctx(int ll) const { return solution_[ll]->ctx_; }
@@ -241,12 +243,22 @@ class multigrid {
     Check(AGX_SYM(halo_exchange)(Ctx(ll), AGX_HALO_STATE), "multigrid (halo_exchange)");
     Check(AGX_SYM(phase_bc_edges)(Ctx(ll)), "multigrid (phase_bc_edges)");
     Check(AGX_SYM(phase_residual)(Ctx(ll), mm, cfl), "multigrid (phase_residual)");
+    // CalcResidual ends with SwapEddyViscAndGradients and, for rans, SwapTurbVars
+    // (gridLevel.cpp:386-392), on every level: Restriction calls it on the coarse one (:559-563)
+    if (swapGradients_) {
+      Check(AGX_SYM(halo_exchange)(Ctx(ll), AGX_HALO_VELGRAD_A), "multigrid (SwapEddyViscAndGradients)");
+      Check(AGX_SYM(halo_exchange)(Ctx(ll), AGX_HALO_VELGRAD_B), "multigrid (SwapEddyViscAndGradients)");
+    }
+    if (swapTurbVars_) Check(AGX_SYM(halo_exchange)(Ctx(ll), AGX_HALO_TURB), "multigrid (SwapTurbVars)");
   }
 
  public:
   multigrid(int cycleIndex, const agx_config &cfg)
       : mgCycleIndex_(cycleIndex), matrixSweeps_(cfg.matrix_sweeps),
-        lusgs_(cfg.matrix_solver == AGX_SOLVER_LUSGS || cfg.matrix_solver == AGX_SOLVER_BLUSGS) {}
+        lusgs_(cfg.matrix_solver == AGX_SOLVER_LUSGS || cfg.matrix_solver == AGX_SOLVER_BLUSGS),
+        swapGradients_((cfg.matrix_solver == AGX_SOLVER_BLUSGS ||
+                        cfg.matrix_solver == AGX_SOLVER_BDPLUR) && cfg.is_viscous),
+        swapTurbVars_(cfg.n_eq == 7) {}
   int NumGridLevels() const { return static_cast<int>(solution_.size()); }
   hotPath &Level(int ll) { return *solution_[ll]; }
   // levels are added finest first

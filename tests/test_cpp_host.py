@@ -62,7 +62,7 @@ def read_output(case, path, n_steps, rank=None):
     """rank: read <path>.<rank>, which holds only that rank's blocks"""
     if rank is not None:
         path = f"{path}.{rank}"
-    n_eq, nonlin = 5, case.deck.nonlinear_iterations
+    n_eq, nonlin = case.n_eq, case.deck.nonlinear_iterations
     raw = open(path, "rb").read()
     rec = n_eq * 8 + 16 + 20
     hist, off = [], 0
@@ -229,13 +229,36 @@ def _run_mg(driver, cycle_index, tf, of, files):
     subprocess.check_call([os.path.join(CPP, driver), str(cycle_index), tf, of] + files, timeout=300)
 
 
-def test_cpp_multigrid_oracle_matches_python_driver(oracle, tmp_path):
+MG_BOX = dict(n=(12, 10, 8), nblocks=2, axis="i", levels=3, cycle="W",
+              time_integration="implicitEuler")
+MG_CASES = {
+    "euler_dplur": MG_KW,
+    # the swaps of gridLevel::CalcResidual on every level (gridLevel.cpp:386-392): the velocity
+    # gradients of a viscous block-matrix solver, eddy viscosity, f1 and f2 of the rans set
+    "ns_blusgs": dict(stretch=1.1, bcs={3: ("viscousWall", 2)}, equation_set="navierStokes",
+                      matrix_solver="blusgs", matrix_sweeps=2, cfl=20.0, **MG_BOX),
+    "rans_blusgs": dict(stretch=1.15, equation_set="rans", turbulence_model="sst2003",
+                        bcs={3: ("viscousWall", 2), 1: ("characteristic", 1),
+                             2: ("characteristic", 1), 4: ("characteristic", 1),
+                             5: ("characteristic", 1), 6: ("characteristic", 1)},
+                        matrix_solver="blusgs", matrix_sweeps=2, cfl=10.0, **MG_BOX),
+}
+
+
+def _mg_agx_driver(cases):
+    return "host_multigrid_agx_rans" if cases[0].n_eq == 7 else "host_multigrid_agx"
+
+
+@pytest.mark.parametrize("name", sorted(MG_CASES))
+def test_cpp_multigrid_oracle_matches_python_driver(oracle, tmp_path, name):
     """mgSolution::CycleAtLevel written twice -- aither_gfx950::multigrid (C++, the reference's
     language) and aither_amd.solver.MultigridSolver (Python) -- over the same library (the
-    oracle): three levels, W cycle, two blocks with a connection; bit for bit."""
+    oracle): three levels, W cycle, two blocks with a connection; Euler DPLUR, viscous BLU-SGS
+    with a wall and k-omega SST BLU-SGS (the two drivers make the same gradient and turbulence
+    swaps on every level); bit for bit."""
     from aither_amd.solver import MultigridSolver
     build_drivers()
-    cases, transfers = synthetic.multigrid_levels(**MG_KW)
+    cases, transfers = synthetic.multigrid_levels(**MG_CASES[name])
     tf, files = write_multigrid_files(cases, transfers, tmp_path, 3)
     of = str(tmp_path / "ora.bin")
     _run_mg("host_multigrid_ora", 2, tf, of, files)
@@ -253,13 +276,14 @@ def test_cpp_multigrid_oracle_matches_python_driver(oracle, tmp_path):
 
 
 @pytest.mark.gpu
-def test_cpp_multigrid_gpu_vs_oracle(tmp_path):
-    """The C++ multigrid driver over libaither_gfx950.so against the same driver over the
-    oracle."""
+@pytest.mark.parametrize("name", sorted(MG_CASES))
+def test_cpp_multigrid_gpu_vs_oracle(tmp_path, name):
+    """The C++ multigrid driver over libaither_gfx950.so (libaither_gfx950_rans.so for the
+    seven equations) against the same driver over the oracle."""
     build_drivers()
-    cases, transfers = synthetic.multigrid_levels(**MG_KW)
+    cases, transfers = synthetic.multigrid_levels(**MG_CASES[name])
     tf, files = write_multigrid_files(cases, transfers, tmp_path, 3)
-    _run_mg("host_multigrid_agx", 2, tf, str(tmp_path / "agx.bin"), files)
+    _run_mg(_mg_agx_driver(cases), 2, tf, str(tmp_path / "agx.bin"), files)
     _run_mg("host_multigrid_ora", 2, tf, str(tmp_path / "ora.bin"), files)
     hg, sg = read_output(cases[0], str(tmp_path / "agx.bin"), 3)
     ho, so = read_output(cases[0], str(tmp_path / "ora.bin"), 3)
