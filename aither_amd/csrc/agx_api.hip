@@ -74,6 +74,9 @@ struct Block {
   DevBuf<double> sweep_rec;   // plane-by-plane sweeps: geo | dyn | rhs records (k_sweep_records)
   bool sweep_geo_built = false; // the (static) geometry records exist
   bool x_planes_current = false; // D2 path: the planes of x equal the D2 arrays (multigrid calls)
+  // D2 path: agx_phase_implicit_begin left x_ = 0 unwritten (the first half sweep does not read
+  // it); until that sweep has run a download of x returns the zeros the reference holds
+  bool x_is_zero = false;
   // multigrid: forcing | matrix residual | saved update planes (each allocated on first
   // use); the transfer maps of this block as the FINE side (device copies, keyed by the
   // host pointers they were uploaded from); node values of this block as the coarse side
@@ -240,6 +243,9 @@ struct agx_ctx {
   // behind the norm read-back the host waits for, so that the GPU does not idle
   // while the host turns the iteration around
   bool in_iterate = false, ghosts_prefilled = false;
+  // the caller's own agx_phase_bc_faces has run and the agx_phase_residual that reads its
+  // ghost cells has not: the output paths that refill the ghost cells are refused
+  bool ghost_fill_open = false;
   // inside agx_iterate the matrix residual is not read back by a host synchronisation of
   // its own (the update would wait for the host): it rides with the update's norms
   bool mres_deferred = false;
@@ -1077,11 +1083,16 @@ int reduce_norms(agx_ctx* c, size_t blk_index, long nparts, NormPartial* out = n
   return 0;
 }
 
+// the inviscid ghost fill as the library's own callers make it: agx_phase_bc_faces is the
+// caller's, and opens the interval in which ghosts_for_output refuses (ghost_fill_open)
+int bc_faces(agx_ctx* c) { Timer t(c, G_BC); return bc_pass(c, true, 0); }
+int bc_edges(agx_ctx* c) { Timer t(c, G_BC); return bc_pass(c, false, 0); }
+
 // gridLevel::GetBoundaryConditions gridLevel.cpp:287-319 for the blocks of this rank
 int fill_ghosts(agx_ctx* c) {
-  if (agx_phase_bc_faces(c)) return 1;
+  if (bc_faces(c)) return 1;
   if (agx_halo_exchange(c, AGX_HALO_STATE)) return 1;
-  return agx_phase_bc_edges(c);
+  return bc_edges(c);
 }
 int update_pass(agx_ctx* c, int mode, int mm, double* l2, agx_linf* linf) {
   c->state_is_time_n = false;
@@ -2274,11 +2285,19 @@ static int d2_x_copy(agx_ctx* c, Block& b, int to_d2) {
 // (already queued behind the last update unless something touched the state since), then
 // the viscous-wall fill (gridLevel.cpp:287-319, procBlock.cpp:6131-6136).  Ghost cells of
 // connections to other ranks stay as last exchanged (an output step is not a collective).
-static int ghosts_for_output(agx_ctx* c) {
+// The viscous-wall fill stays in the ghost cells, so between the caller's agx_phase_bc_faces
+// and the agx_phase_residual that follows it -- whose inviscid fluxes would read it -- the
+// call is refused (include/aither_gfx950.h "reads between phases").
+static int ghosts_for_output(agx_ctx* c, const char* who) {
+  if (c->ghost_fill_open)
+    return fail("%s: gradients, node and wall variables refill the ghost cells, which are "
+                "being filled for the coming residual (agx_phase_bc_faces was called, "
+                "agx_phase_residual not yet); legal from agx_phase_residual to the next "
+                "agx_phase_bc_faces and between agx_iterate calls", who);
   if (!c->ghosts_prefilled) {
-    if (agx_phase_bc_faces(c)) return 1;
+    if (bc_faces(c)) return 1;
     if (agx_halo_swap_local(c, AGX_HALO_STATE)) return 1;
-    if (agx_phase_bc_edges(c)) return 1;
+    if (bc_edges(c)) return 1;
   }
   if (c->cfg.is_viscous) {
     if (bc_pass(c, true, 2)) return 1;     // (2: the stored wall-law data stay the last residual's)
@@ -2295,13 +2314,25 @@ int agx_field_download(agx_ctx* c, int id, int field, double* out) {
   // (the D2 arrays hold x with the writer's tag in its two lowest mantissa bits: while the
   // planes are current -- an upload or a multigrid transfer wrote them last -- they are the
   // untagged x itself, zero ghost cells of a restriction included)
+  if (field == AGX_FIELD_UPDATE && b.x_is_zero) {
+    const int g = b.d.ng;
+    memset(out, 0, sizeof(double) * AGX_NEQ * (size_t)(b.d.ni + 2 * g) * (b.d.nj + 2 * g) *
+                       (b.d.nk + 2 * g));
+    return 0;
+  }
   if (field == AGX_FIELD_UPDATE && b.d.d2.base && !b.x_planes_current && d2_x_copy(c, b, 0))
     return 1;
+  // (k_lusgs_prepare forms the diagonal inside the D2 arrays, as 1 / a beside x: the plane
+  // d.a keeps the spectral radii the residual summed, without the time term)
+  if (field == AGX_FIELD_DIAGONAL && b.d.d2.base)
+    return fail("agx_field_download: the diagonal-ordered LU-SGS path keeps the scalar diagonal "
+                "a_ only as 1 / a inside its sweep arrays, not as a field (AGX_LUSGS=plane, the "
+                "hyperplane form, keeps it)");
   if (field >= AGX_FIELD_VEL_GRAD && field <= AGX_FIELD_PRESS_GRAD) {
     // cell-centre gradients: formed on demand into a temporary (an output path)
     const long ncell = (long)b.d.ni * b.d.nj * b.d.nk;
     double* tmp = nullptr;
-    if (ghosts_for_output(c)) return 1;
+    if (ghosts_for_output(c, "agx_field_download")) return 1;
     if (stage_buffer(c, (size_t)3 * NGF * ncell, &tmp)) return 1;
     hipLaunchKernelGGL(k_cell_grads, cell_grid(b.d, CELL_BLOCK), CELL_BLOCK, 0, c->stream, b.d,
                        c->gas, tmp);
@@ -2369,7 +2400,7 @@ int wall_pack(agx_ctx* c, int id, int nvar, const int32_t* vars, double* out) {
   const long total = b.wall_faces;
   double* tmp = nullptr;
   if (stage_buffer(c, (size_t)nvar * total, &tmp)) return 1;
-  if (ghosts_for_output(c)) return 1;
+  if (ghosts_for_output(c, "agx_output_pack")) return 1;
   const int fourth = c->cfg.viscous_recon == AGX_VISC_RECON_CENTRAL_4TH ? 1 : 0;
   hipLaunchKernelGGL(k_wall_pack, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, c->stream,
                      b.d, c->gas, out_spec(c, b, nvar, vars), b.wall_tab_dev.get(),
@@ -2404,7 +2435,7 @@ int point_pack(agx_ctx* c, int id, bool node, int nvar, const int32_t* vars, dou
   if (stage_buffer(c, gdoubles + (size_t)nvar * npoint, &tmp)) return 1;
   // every nodal variable reads ghost cells, of the cell variables the gradients do: those the
   // next residual would see
-  if ((node || need_grads) && ghosts_for_output(c)) return 1;
+  if ((node || need_grads) && ghosts_for_output(c, "agx_output_pack")) return 1;
   const dim3 grid((b.d.ni + n1 + CELL_BLOCK.x - 1) / CELL_BLOCK.x,
                   (b.d.nj + n1 + CELL_BLOCK.y - 1) / CELL_BLOCK.y, b.d.nk + n1);
   if (need_grads)
@@ -2538,6 +2569,7 @@ int agx_field_upload(agx_ctx* c, int id, int field, const double* in) {
   if (field_info(b, field, &p, &nc, &gh)) return fail("field %d cannot be uploaded", field);
   const int g = gh ? b.d.ng : 0;
   if (upload_aos(c, b, in, p, nc, b.d.ni + 2 * g, b.d.nj + 2 * g, b.d.nk + 2 * g, g)) return 1;
+  if (field == AGX_FIELD_UPDATE) b.x_is_zero = false;
   if (field == AGX_FIELD_UPDATE && b.d.d2.base) return d2_x_copy(c, b, 1);
   return 0;
 }
@@ -2779,12 +2811,17 @@ int agx_store_time_n(agx_ctx* c, int also_nm1) {
 }
 
 // ---- phases ---------------------------------------------------------------
-int agx_phase_bc_faces(agx_ctx* c) { Timer t(c, G_BC); return bc_pass(c, true, 0); }
-int agx_phase_bc_edges(agx_ctx* c) { Timer t(c, G_BC); return bc_pass(c, false, 0); }
+int agx_phase_bc_faces(agx_ctx* c) {
+  if (bc_faces(c)) return 1;
+  c->ghost_fill_open = true;      // (until the residual has read these ghost cells)
+  return 0;
+}
+int agx_phase_bc_edges(agx_ctx* c) { return bc_edges(c); }
 
 int agx_phase_residual(agx_ctx* c, int mm, double cfl) {
   if (c->cfg.dt_nondim <= 0.0 && cfl <= 0.0)
     return fail("Neither dt or cfl was specified!");   // procBlock.cpp:813-816
+  c->ghost_fill_open = false;
   c->sp.diag_add = c->mg_coarse ? 1 : 0;
   const bool fuse = can_fuse(c);
   const int store_consn = !c->use_gather && all_tile_ok(c) && c->consn_pending && mm == 0;
@@ -2943,7 +2980,9 @@ static int implicit_begin(agx_ctx* c, int write_x) {
       // multigrid level, write_x = 0: x is the restricted one)
       bool conn = false;
       for (int q = 0; q < 6; ++q) conn = conn || b.side_conn[q] != 0;
-      d2_prepare(c, blk, write_x && (c->sp.requires_init || conn) ? 1 : 0, 0);
+      const int wx = write_x && (c->sp.requires_init || conn) ? 1 : 0;
+      d2_prepare(c, blk, wx, 0);
+      blk.x_is_zero = write_x && !wx;
       continue;
     }
 #endif
@@ -2964,6 +3003,7 @@ static int implicit_begin(agx_ctx* c, int write_x) {
 
 int agx_phase_relax_forward(agx_ctx* c, int sweep) {
   x_changed(c);
+  for (auto& blk : c->blocks) blk.x_is_zero = false;
   Timer t(c, G_SWEEP);
   const int full = sweep > 0 || c->sp.requires_init;
   bool swept = false;

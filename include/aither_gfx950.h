@@ -76,7 +76,9 @@ enum { AGX_FIELD_STATE = 0,      /* state_      nEq, with ghosts           */
        AGX_FIELD_SPEC_RADIUS = 3,/* specRadius_ 1,   no ghosts (flow part) */
        AGX_FIELD_CONS_N = 4,     /* consVarsN_  nEq, no ghosts             */
        AGX_FIELD_UPDATE = 5,     /* linearSolver x_ nEq, with ghosts       */
-       AGX_FIELD_DIAGONAL = 6,   /* linearSolver a_ (scalar) 1, no ghosts  */
+       AGX_FIELD_DIAGONAL = 6,   /* linearSolver a_ (scalar) 1, no ghosts;
+                                  * refused by name on the diagonal-ordered LU-SGS
+                                  * path, which keeps a_ only inside its sweep arrays */
        AGX_FIELD_TEMPERATURE = 7,/* temperature_ 1,  with ghosts           */
        AGX_FIELD_VISCOSITY = 8,  /* viscosity_  1,   with ghosts           */
        AGX_FIELD_CONS_NM1 = 9,   /* consVarsNm1_ nEq, no ghosts            */
@@ -374,7 +376,17 @@ int agx_setup_finalize(agx_ctx *ctx);
 /* ---- state movement ---------------------------------------------------- */
 /* replaces gridLevel ctor state init / ReadRestart (gridLevel.cpp:55,63-65) */
 int agx_state_upload(agx_ctx *ctx, int block_id, const double *state_aos);
-/* replaces the pack in GetFinestGridLevel (procBlock.cpp:4491-4660) */
+/* replaces the pack in GetFinestGridLevel (procBlock.cpp:4491-4660).
+ * Reads between phases: a download, agx_output_pack and agx_restart_pack may be made at any
+ * point between two calls of the library -- between the phases of an iteration, between the
+ * agx_mg_* calls of a cycle, between agx_iterate calls -- and leave the run bit-identical.
+ * One group is the exception, because it refills the ghost cells of the state (inviscid fill,
+ * then the viscous-wall fill, which stays): the gradient fields (AGX_FIELD_VEL_GRAD ..
+ * AGX_FIELD_PRESS_GRAD), and of agx_output_pack the gradient variables, every node variable
+ * and every wall variable.  From the caller's agx_phase_bc_faces up to the
+ * agx_phase_residual that follows it the ghost cells are being filled for that residual, and
+ * these calls are REFUSED with a message; they are legal from agx_phase_residual to the next
+ * agx_phase_bc_faces, and between agx_iterate calls (agx_iterate's own fill does not count). */
 int agx_field_download(agx_ctx *ctx, int block_id, int field, double *out_aos);
 int agx_field_upload(agx_ctx *ctx, int block_id, int field, const double *in_aos);
 
@@ -434,7 +446,9 @@ int agx_phase_implicit_update(agx_ctx *ctx, int mm, double *l2, agx_linf *linf);
  * Refused: variables of two ranges in one call, an id in no range, a block without a
  * viscousWall surface, an inviscid context, wall-law surfaces before the first residual (the
  * three: wall variables), the four node variables named above, nvar beyond the number of ids
- * of its range (repeated ids are allowed in all three). */
+ * of its range (repeated ids are allowed in all three); gradient, node and wall variables
+ * between agx_phase_bc_faces and the agx_phase_residual that follows it ("reads between
+ * phases" at agx_field_download). */
 int agx_output_pack(agx_ctx *ctx, int block, int nvar, const int32_t *vars, double *out);
 /* WriteRestart (output.cpp:651-752), the payload of one block: cell by cell (i fastest)
  * n_eq + 1 dimensional values -- density, velocity, pressure, [tke, sdr,] mass fraction of

@@ -110,6 +110,7 @@ struct ora_ctx {
   double mres_sumsq; /* ... and of the squared residual itself */
   agx_exchange ex;   /* multi-rank transport (host buffers) */
   int have_ex;
+  int ghost_fill_open; /* the caller's own ora_phase_bc_faces .. the next ora_phase_residual */
 };
 
 /* ------------------------------------------------------------------------ */
@@ -3009,13 +3010,22 @@ static double *field_ptr(blk_t *b, int field, long *n) {
  * the ghost cells the NEXT residual would see -- the inviscid fill of the state as it is
  * now, then the viscous-wall fill (gridLevel.cpp:287-319, procBlock.cpp:6131-6136); ghost
  * cells of connections to other ranks stay as last exchanged. */
-int ora_phase_bc_faces(ora_ctx *c);
-int ora_phase_bc_edges(ora_ctx *c);
+static int bc_faces(ora_ctx *c);
+static int bc_edges(ora_ctx *c);
 int ora_halo_swap_local(ora_ctx *c, int what);
-static int ghosts_for_output(ora_ctx *c) {
-  if (ora_phase_bc_faces(c)) return 1;
+/* The viscous-wall fill stays in the ghost cells.  Between a caller's own ora_phase_bc_faces
+ * and the ora_phase_residual that follows it the ghost cells are being filled for that
+ * residual, whose inviscid fluxes would read the viscous fill: refused there, see
+ * include/aither_gfx950.h "reads between phases". */
+static int ghosts_for_output(ora_ctx *c, const char *who) {
+  if (c->ghost_fill_open)
+    return fail("%s: gradients, node and wall variables refill the ghost cells, which are "
+                "being filled for the coming residual (agx_phase_bc_faces was called, "
+                "agx_phase_residual not yet); legal from agx_phase_residual to the next "
+                "agx_phase_bc_faces and between agx_iterate calls", who);
+  if (bc_faces(c)) return 1;
   if (ora_halo_swap_local(c, AGX_HALO_STATE)) return 1;
-  if (ora_phase_bc_edges(c)) return 1;
+  if (bc_edges(c)) return 1;
   if (c->cfg.is_viscous)
     for (int n = 0; n < c->nblk; ++n) {
       if (assign_ghost_faces(c, &c->blk[n], 1)) return 1;
@@ -3027,7 +3037,7 @@ int ora_field_download(ora_ctx *c, int id, int field, double *out) {
   if (id < 0 || id >= c->nblk) return fail("bad block id");
   if (field >= AGX_FIELD_VEL_GRAD && field <= AGX_FIELD_PRESS_GRAD) {
     blk_t *b = &c->blk[id];
-    if (ghosts_for_output(c)) return 1;
+    if (ghosts_for_output(c, "agx_field_download")) return 1;
     double *all = (double *)malloc(sizeof(double) * 18 * b->ncell);
     cell_gradients(c, b, all);
     const int off = field == AGX_FIELD_VEL_GRAD ? 0 : 9 + 3 * (field - AGX_FIELD_TEMP_GRAD);
@@ -3056,7 +3066,7 @@ int ora_output_pack(ora_ctx *c, int id, int nvar, const int32_t *vars, double *o
     if (vars[v] == AGX_OUT_VISCOSITY && !c->cfg.is_viscous)
       return fail("viscosity_ is only kept for viscous runs (procBlock.cpp:6171)");
     if (vars[v] >= AGX_OUT_VELGRAD && vars[v] < AGX_OUT_RESID && !gr) {
-      if (ghosts_for_output(c)) return 1;
+      if (ghosts_for_output(c, "agx_output_pack")) return 1;
       gr = (double *)malloc(sizeof(double) * 3 * nf * b->ncell);
       cell_gradients_n(c, b, nf, gr);
     }
@@ -3461,18 +3471,27 @@ int ora_store_time_n(ora_ctx *c, int also_nm1) {
   return 0;
 }
 
-int ora_phase_bc_faces(ora_ctx *c) {
+static int bc_faces(ora_ctx *c) {
   for (int n = 0; n < c->nblk; ++n)
     if (assign_ghost_faces(c, &c->blk[n], 0)) return 1;
   return 0;
 }
-int ora_phase_bc_edges(ora_ctx *c) {
+static int bc_edges(ora_ctx *c) {
   for (int n = 0; n < c->nblk; ++n)
     if (assign_ghost_edges(c, &c->blk[n], 0)) return 1;
   return 0;
 }
+/* the public entries: a caller's own ghost fill is open until its residual has read it
+ * (ghosts_for_output); ora_iterate's fill and the output paths' use bc_faces / bc_edges */
+int ora_phase_bc_faces(ora_ctx *c) {
+  if (bc_faces(c)) return 1;
+  c->ghost_fill_open = 1;
+  return 0;
+}
+int ora_phase_bc_edges(ora_ctx *c) { return bc_edges(c); }
 int ora_phase_residual(ora_ctx *c, int mm, double cfl) {
   (void)mm;
+  c->ghost_fill_open = 0;
   for (int n = 0; n < c->nblk; ++n) {
     if (calc_residual(c, &c->blk[n])) return 1;
   }
@@ -3654,9 +3673,9 @@ int ora_iterate(ora_ctx *c, int mm, double cfl, double *l2, agx_linf *linf,
     for (int n = 0; n < c->nconn; ++n)
       if (my_side(c, &c->conn[n]) >= 0)
         return fail("iterate: connections to other ranks need an exchange or the phase API");
-  if (ora_phase_bc_faces(c)) return 1;
+  if (bc_faces(c)) return 1;
   if (ora_halo_exchange(c, AGX_HALO_STATE)) return 1;
-  if (ora_phase_bc_edges(c)) return 1;
+  if (bc_edges(c)) return 1;
   if (ora_phase_residual(c, mm, cfl)) return 1;
   *matrix_resid = 0.0;
   if (c->cfg.time_integration >= AGX_TIME_IMPLICIT_EULER) {

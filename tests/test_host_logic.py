@@ -423,3 +423,95 @@ def test_oracle_runs_the_thin_block_cases(oracle):
             assert st[..., 0].min() > 0.5 and st[..., 4].min() > 0.3, (n, deck)
             assert np.abs(st - ini).max() > 0.0, (n, deck)
             s.close()
+
+
+def test_probe_hooks_name_entries_of_the_abi(oracle):
+    """Every entry the probing proxy hooks (tests/probe.py HOOKED) is an entry of abi.Api --
+    a renamed entry would silently lose its positions -- and the hooks cover the header's
+    whole phase list and every agx_mg_* entry."""
+    import probe
+    for name in probe.HOOKED:
+        assert name in abi.SYMBOLS and callable(getattr(oracle, name)), name
+    assert len(set(probe.HOOKED)) == len(probe.HOOKED)
+    assert {n for n in abi.SYMBOLS if n.startswith(("phase_", "mg_"))} <= set(probe.HOOKED)
+    for entry, kind in probe.REFUSED_AT:
+        assert entry.split("[")[0] in probe.HOOKED and kind in probe.KINDS
+
+
+def test_probe_decks_select_their_piece():
+    """tests/test_probe_gpu.py: every deck has the property that selects the piece of deferred
+    state it is there for -- the dispatch conditions of agx_api.hip (can_fuse, use_d2,
+    plane_sweep_all_applicable, the solver kinds) restated on its table."""
+    from test_production_paths_gpu import can_fuse, on_d2_path
+    import test_probe_gpu as t
+    import tp_cases
+    kw = t.deck_kw
+    stacked = lambda name: t.DECKS[name][1] == "stacked"
+    for name in ("euler_rk4", "euler_rk4_stacked_i", "euler_explicit_weno"):
+        assert can_fuse(kw(name)) and "bcs" not in kw(name), name      # (slip walls: no nr surface)
+    assert kw("euler_rk4")["time_integration"] == "rk4"
+    assert kw("euler_explicit_weno")["time_integration"] == "explicitEuler"
+    assert stacked("euler_rk4_stacked_i")
+    for name in ("ns_lusgs2", "ns_lusgs2_stacked_k", "ns_lusgs2_bdf2", "ns_lusgs2_bdf2_stacked_k"):
+        assert on_d2_path(kw(name)) and kw(name)["matrix_sweeps"] == 2, name
+        assert stacked(name) == name.endswith("_k")                     # CONN form
+    for name in ("ns_lusgs2_bdf2", "ns_lusgs2_bdf2_stacked_k"):
+        assert kw(name)["time_integration"] == "bdf2" and kw(name)["nonlinear_iterations"] == 2
+    # plane_sweep_all_applicable: LU-SGS off the D2 path, two blocks, ni + nj + nk - 2 >= 8
+    roe = kw("euler_lusgs_roe_stacked_i")
+    assert roe["matrix_solver"] == "lusgs" and not on_d2_path(roe) and not can_fuse(roe)
+    assert stacked("euler_lusgs_roe_stacked_i") and sum(t.N) - 2 >= 8
+    # DPLUR: an odd number of sweeps leaves x and xold in exchanged roles
+    dpl = kw("ns_dplur3_stacked_j")
+    assert dpl["matrix_solver"] == "dplur" and dpl["matrix_sweeps"] % 2 == 1
+    assert stacked("ns_dplur3_stacked_j") and t.TIMED == "ns_dplur3_stacked_j"
+    # the velocity-gradient halo: block-matrix, viscous, a connection
+    for name, solver in (("ns_bdplur_stacked_i", "bdplur"), ("ns_blusgs_c4_stacked_k", "blusgs")):
+        assert kw(name)["matrix_solver"] == solver and stacked(name)
+        assert kw(name)["equation_set"] == "navierStokes"
+    assert kw("ns_blusgs_c4_stacked_k")["viscous_face_reconstruction"] == "centralFourth"
+    for name, solver in (("rans_lusgs_stacked_i", "lusgs"), ("rans_blusgs_stacked_i", "blusgs")):
+        assert kw(name)["equation_set"] == "rans" and kw(name)["matrix_solver"] == solver
+        assert stacked(name) and kw(name)["bcs"][3][0] == "viscousWall"
+        assert kw(name)["n"] == tp_cases.RANS_BASE["n"]
+    law = t.maker("rans_wall_law")()
+    (wall,) = [s for s in law.blocks[0].surfaces if s.bc_type == "viscousWall"]
+    assert wall.tag == t.WALL_LAW_TAG and kw("rans_wall_law")["wall_treatment"] == "wallLaw"
+    stag = t.maker("stagnation_nonreflecting")()
+    assert {s.bc_type for s in stag.blocks[0].surfaces} >= {"stagnationInlet", "pressureOutlet"}
+    assert ("stagnation_nonreflecting", "solver") in t.RUNS
+    for name in t.MULTIGRID:
+        cases, trs = t.maker(name)()
+        assert len(cases) == 2 and cases[0].deck.multigrid_cycle == "V"
+    assert on_d2_path(kw("mg_euler_lusgs")) and kw("mg_rans_blusgs")["matrix_solver"] == "blusgs"
+    for name, (lib, form, _) in t.DECKS.items():
+        if lib[1] == tp_cases.TP:
+            made = t.maker(name)()
+            case = made[0][0] if name in t.MULTIGRID else made
+            assert case.gas.thermodynamic_model == tp_cases.TP and \
+                tp_cases.vibrational_share(case) >= tp_cases.MIN_VIB_SHARE, name
+    # every deck under both drivers, the multigrid ones under the cycle driver
+    assert len(t.RUNS) == 2 * (len(t.DECKS) - len(t.MULTIGRID)) + len(t.MULTIGRID)
+
+
+def test_probe_census(oracle):
+    """Like test_every_branch_is_covered_by_the_cases: every entry of the header's phase list,
+    store_time_n, iterate, the local halo swap, and every agx_mg_* entry the cycle driver calls
+    is reached by a deck of EVERY library in tests/test_probe_gpu.py (the positions are the
+    driver's: recorded on the oracle, which runs the same drivers), and there every reached
+    position is probed by all three kinds (test_reads_between_phases holds len(seen) to
+    len(labels) for each kind)."""
+    import gc
+    import probe
+    import test_probe_gpu as t
+    reached = {}
+    for name, driver in t.RUNS:
+        labels = probe.run(oracle, t.maker(name), driver, steps=1)[1].labels
+        gc.collect()
+        reached.setdefault(t.DECKS[name][0], set()).update(lb.split("[")[0] for lb in labels)
+    called = set(probe.PHASES) | set(probe.MG) | {"store_time_n", "iterate", "halo_swap_local"}
+    assert set(reached) == {t.CP5, t.CP7, t.TP5, t.TP7}
+    for lib, got in reached.items():
+        # (the 7-equation libraries and the hot decks have no explicit scheme)
+        assert called - got <= (set() if lib == t.CP5 else {"phase_explicit_update"}), \
+            (lib, called - got)
