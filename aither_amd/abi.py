@@ -54,6 +54,17 @@ WALL_OUT = {"yplus": 64, "shearStress": 65, "viscosityRatio": 66, "heatFlux": 67
 # variables of the nodal function file (AGX_NODE_BASE + AGX_OUT_*): the names of OUT
 NODE_BASE = 128
 NODE_OUT = {_n: NODE_BASE + _v for _n, _v in OUT.items()}
+# integrated wall loads (AGX_LOAD_*): one value per load surface (viscousWall, slipWall)
+LOAD_BASE = 256
+LOAD_OUT = {"area": LOAD_BASE}
+for _n, _base in (("area", 1), ("pressureForce", 4), ("viscousForce", 7)):
+    for _q, _c in enumerate("xyz"):
+        LOAD_OUT[f"{_n}_{_c}"] = LOAD_BASE + _base + _q
+LOAD_OUT["heatLoad"] = LOAD_BASE + 10
+for _n, _base in (("pressureMoment", 11), ("viscousMoment", 14)):
+    for _q, _c in enumerate("xyz"):
+        LOAD_OUT[f"{_n}_{_c}"] = LOAD_BASE + _base + _q
+LOAD_MOMENTS = tuple(_n for _n in LOAD_OUT if "Moment" in _n)
 
 c_dp = C.POINTER(C.c_double)
 

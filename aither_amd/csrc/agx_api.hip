@@ -113,6 +113,13 @@ struct Block {
   std::vector<WallSurfDev> wall_tab;
   DevBuf<WallSurfDev> wall_tab_dev;
   long wall_faces = 0;
+  // load surfaces (viscousWall and slipWall) in the order given: what k_wall_loads walks,
+  // their faces and chunks, the chunk records of a call, and -- node-built blocks, from
+  // agx_setup_finalize on -- the centres of their faces (k_load_centres)
+  std::vector<LoadSurfDev> load_tab;
+  DevBuf<LoadSurfDev> load_tab_dev;
+  long load_faces = 0, load_chunks = 0;
+  DevBuf<double> load_partial, load_fcen;
 };
 
 struct ConnSide {          // what side s receives / sends
@@ -1515,6 +1522,15 @@ int geo_complete(agx_ctx* c) {
     }
   HIPCHK(hipGetLastError());
 #endif
+  // 6. the moments of the integrated wall loads keep the centres of the load-surface faces
+  for (auto& b : c->blocks) {
+    if (b.load_faces == 0) continue;
+    HIPCHK(b.load_fcen.alloc((size_t)3 * b.load_faces));
+    hipLaunchKernelGGL(k_load_centres, geo_grid(b.load_faces), dim3(256), 0, c->stream, b.d,
+                       b.fcen.get(), b.load_tab_dev.get(), (int)b.load_tab.size(), b.load_faces,
+                       b.load_fcen.get());
+  }
+  HIPCHK(hipGetLastError());
   HIPCHK(hipStreamSynchronize(c->stream));
   for (auto& b : c->blocks) {
     b.fcen.reset();
@@ -1957,6 +1973,36 @@ int agx_block_set_bcs(agx_ctx* c, int id, int n, const agx_bc_surface* s) {
     b.wall_tab.push_back(w);
   }
   HIPCHK(b.wall_tab_dev.upload(b.wall_tab));
+  // the table of the integrated wall loads (agx_output_pack with AGX_LOAD_*): viscousWall
+  // and slipWall surfaces, each cut into chunks of LOAD_CHUNK faces of its own
+  b.load_tab_dev.reset();
+  b.load_partial.reset();
+  b.load_fcen.reset();
+  b.load_tab.clear();
+  b.load_faces = b.load_chunks = 0;
+  for (int q = 0; q < n; ++q) {
+    if (s[q].bc_type != AGX_BC_VISCOUSWALL && s[q].bc_type != AGX_BC_SLIPWALL) continue;
+    LoadSurfDev w;
+    const int lo[3] = {s[q].imin, s[q].jmin, s[q].kmin}, hi[3] = {s[q].imax, s[q].jmax, s[q].kmax};
+    const int nn[3] = {b.d.ni, b.d.nj, b.d.nk};
+    w.side = surface_type(s[q]);
+    w.visc = s[q].bc_type == AGX_BC_VISCOUSWALL ? 1 : 0;
+    const int d3 = (w.side - 1) / 2;
+    for (int d = 0; d < 3; ++d) {
+      w.lo[d] = lo[d];
+      w.n[d] = d == d3 ? 1 : hi[d] - lo[d];
+      if (lo[d] < 0 || hi[d] > nn[d] || w.n[d] < 1 || (d == d3 && lo[d] != 0 && lo[d] != nn[d]))
+        return fail("wall surface %d does not lie on a side of block %d", q, id);
+    }
+    const long faces = (long)w.n[0] * w.n[1] * w.n[2];
+    w.off = b.load_faces;
+    w.chunk0 = b.load_chunks;
+    b.load_faces += faces;
+    b.load_chunks += (faces + LOAD_CHUNK - 1) / LOAD_CHUNK;
+    b.load_tab.push_back(w);
+  }
+  HIPCHK(b.load_tab_dev.upload(b.load_tab));
+  if (b.load_chunks > 0) HIPCHK(b.load_partial.alloc((size_t)b.load_chunks * LOAD_NQ));
   return 0;
 }
 
@@ -2407,6 +2453,43 @@ int wall_pack(agx_ctx* c, int id, int nvar, const int32_t* vars, double* out) {
                      (int)b.wall_tab.size(), total, fourth, tmp);
   return copy_out(c, out, tmp, (size_t)nvar * total);
 }
+// The integrated wall loads of one block's load surfaces (the ids are load ids, nvar is in
+// their range): k_wall_loads' chunk records, then k_wall_loads_sum
+int wall_loads(agx_ctx* c, int id, int nvar, const int32_t* vars, double* out) {
+  Block& b = c->blocks[id];
+  if (b.load_tab.empty())
+    return fail("agx_output_pack: block %d has no viscousWall or slipWall surface", id);
+  if (!c->finalized) return fail("agx_setup_finalize has not been called");
+  const bool viscous = c->cfg.is_viscous != 0;
+  if (viscous && b.d.wallv && !c->have_wall_data)
+    return fail("agx_output_pack: the wall-law surfaces hold no wall data before the first "
+                "residual");
+  if (!b.load_fcen)
+    for (int v = 0; v < nvar; ++v)
+      if (vars[v] >= AGX_LOAD_PRESSURE_MOMENT_X) {
+        if (!b.node_built)
+          return fail("agx_output_pack: load variable %d is a moment, and block %d was built "
+                      "from arrays: agx_block_geom carries no face centres (a block built from "
+                      "agx_block_geom.nodes keeps those of its wall faces)", vars[v], id);
+        return fail("agx_output_pack: load variable %d is a moment, and the face centres of "
+                    "block %d went with an agx_block_set_bcs after agx_setup_finalize",
+                    vars[v], id);
+      }
+  const int nsurf = (int)b.load_tab.size();
+  double* tmp = nullptr;
+  if (stage_buffer(c, (size_t)nvar * nsurf, &tmp)) return 1;
+  // a viscous context evaluates its viscousWall faces with the ghost cells the next residual
+  // would see; an inviscid one reads physical cells only
+  if (viscous && ghosts_for_output(c, "agx_output_pack")) return 1;
+  const int fourth = c->cfg.viscous_recon == AGX_VISC_RECON_CENTRAL_4TH ? 1 : 0;
+  hipLaunchKernelGGL(k_wall_loads, dim3((unsigned)b.load_chunks), dim3(LOAD_CHUNK), 0, c->stream,
+                     b.d, c->gas, b.load_tab_dev.get(), nsurf, b.load_faces, viscous ? 1 : 0,
+                     fourth, b.load_fcen.get(), b.load_partial.get());
+  hipLaunchKernelGGL(k_wall_loads_sum, dim3((unsigned)((nvar * nsurf + 63) / 64)), dim3(64), 0,
+                     c->stream, out_spec(c, b, nvar, vars), b.load_tab_dev.get(), nsurf,
+                     b.load_chunks, 1.0 / c->gas.scaling, b.load_partial.get(), tmp);
+  return copy_out(c, out, tmp, (size_t)nvar * nsurf);
+}
 // WriteFunFile's payload of one block, or (node) WriteNodeFun's: one value per physical cell
 // or per node; vars: cell ids
 int point_pack(agx_ctx* c, int id, bool node, int nvar, const int32_t* vars, double* out) {
@@ -2452,16 +2535,32 @@ int agx_output_pack(agx_ctx* c, int id, int nvar, const int32_t* vars, double* o
   if (flush_consn(c)) return 1;
   if (id < 0 || id >= (int)c->blocks.size()) return fail("bad block id %d", id);
   if (nvar < 1 || nvar > AGX_OUT_COUNT) return fail("agx_output_pack: nvar %d out of range", nvar);
-  // cell variables, wall variables (WriteWallFun) or node variables (WriteNodeFun), each range
-  // with its own bound on nvar
-  int n_wall = 0, n_node = 0;
+  // cell variables, wall variables (WriteWallFun), node variables (WriteNodeFun) or integrated
+  // wall loads, each range with its own bound on nvar
+  int n_wall = 0, n_node = 0, n_load = 0;
   for (int v = 0; v < nvar; ++v) {
     const bool cell = vars[v] >= 0 && vars[v] < AGX_OUT_COUNT;
     const bool wall = vars[v] >= AGX_WALL_YPLUS && vars[v] < AGX_WALL_END;
     const bool node = vars[v] >= AGX_NODE_BASE && vars[v] < AGX_NODE_END;
-    if (!cell && !wall && !node) return fail("unknown output variable %d", vars[v]);
+    const bool load = vars[v] >= AGX_LOAD_BASE && vars[v] < AGX_LOAD_END;
+    if (!cell && !wall && !node && !load) return fail("unknown output variable %d", vars[v]);
     n_wall += wall;
     n_node += node;
+    n_load += load;
+  }
+  if (n_load > 0) {
+    if (n_node > 0)
+      return fail("agx_output_pack: node and load variables in one call (a call holds ids of "
+                  "one range)");
+    if (n_wall > 0)
+      return fail("agx_output_pack: wall and load variables in one call (a call holds ids of "
+                  "one range)");
+    if (n_load != nvar)
+      return fail("agx_output_pack: cell and load variables in one call (a call holds ids of "
+                  "one range)");
+    if (nvar > AGX_LOAD_END - AGX_LOAD_BASE)
+      return fail("agx_output_pack: nvar %d out of range", nvar);
+    return wall_loads(c, id, nvar, vars, out);
   }
   if (n_node > 0) {
     if (n_wall > 0)

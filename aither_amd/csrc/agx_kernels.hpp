@@ -3594,21 +3594,17 @@ struct WallSurfDev {
   int side;            // surface type 1..6
   long off;            // first face of the surface in a variable's row
 };
-__global__ void __launch_bounds__(256)
-k_wall_pack(BlockDev b, GasDev g, OutSpec sp, const WallSurfDev* __restrict__ tab, int nsurf,
-            long total, int fourth, double* __restrict__ out) {
-  const long t = (long)blockIdx.x * blockDim.x + threadIdx.x;
-  if (t >= total) return;
-  int sn = 0;
-  while (sn + 1 < nsurf && t >= tab[sn + 1].off) ++sn;
-  const WallSurfDev ws = tab[sn];
-  const long r = t - ws.off;
-  const int fi = ws.lo[0] + (int)(r % ws.n[0]);
-  const int fj = ws.lo[1] + (int)((r / ws.n[0]) % ws.n[1]);
-  const int fk = ws.lo[2] + (int)(r / ((long)ws.n[0] * ws.n[1]));
-  const int d = (ws.side - 1) / 2;
-  const long qU = b.idx(fi, fj, fk), qL = qU - b.stride(d);
-  WallVars w;
+// The face pressure of filled wallVars: PressureRT (wallData.cpp:140-144), nondimensional
+__device__ __forceinline__ double wall_face_pressure(const GasDev& g, const WallVars& w) {
+  return w.density * g.R * w.temperature;
+}
+// The wallVars of one viscousWall face (the per-face evaluation k_wall_pack and k_wall_loads
+// share): the stored wall data of a wall-law face, or the low-Re evaluation described above.
+// d: the wall's direction, side: its surface type; qU: the face's index in the planes (the
+// cell above it), qL: the cell below.
+__device__ __forceinline__ void wall_face_vars(const BlockDev& b, const GasDev& g, int d,
+                                               int side, int fi, int fj, int fk, long qU,
+                                               long qL, int fourth, WallVars& w) {
   const WallVars* stored = nullptr;
 #if AGX_NEQ == 7
   const agx_bc_surface* bs;
@@ -3647,9 +3643,30 @@ k_wall_pack(BlockDev b, GasDev g, OutSpec sp, const WallSurfDev* __restrict__ ta
     w.temperature = sf[4] / (sf[0] * g.R);
     w.friction_velocity = sqrt(sqrt(dot3(tau, tau)) / w.density);
     // y+ from the wall distance of the wall-adjacent cell, procBlock.cpp:1372-1375
-    const double y = ws.side % 2 == 1 ? b.wdist[qU] : b.wdist[qL];
+    const double y = side % 2 == 1 ? b.wdist[qU] : b.wdist[qL];
     w.yplus = y * w.friction_velocity * w.density / (w.viscosity + w.turb_eddy_visc);
   }
+}
+__global__ void __launch_bounds__(256)
+k_wall_pack(BlockDev b, GasDev g, OutSpec sp, const WallSurfDev* __restrict__ tab, int nsurf,
+            long total, int fourth, double* __restrict__ out) {
+  const long t = (long)blockIdx.x * blockDim.x + threadIdx.x;
+  if (t >= total) return;
+  int sn = 0;
+  while (sn + 1 < nsurf && t >= tab[sn + 1].off) ++sn;
+  const WallSurfDev ws = tab[sn];
+  const long r = t - ws.off;
+  const int fi = ws.lo[0] + (int)(r % ws.n[0]);
+  const int fj = ws.lo[1] + (int)((r / ws.n[0]) % ws.n[1]);
+  const int fk = ws.lo[2] + (int)(r / ((long)ws.n[0] * ws.n[1]));
+  const int d = (ws.side - 1) / 2;
+  const long qU = b.idx(fi, fj, fk), qL = qU - b.stride(d);
+  // (read from a copy of the kernel's own: a * a + b * b + c * c leaves the contraction into
+  // fma to the compiler, and with the copy it forms |tau|^2 of shearStress the way it did
+  // before the evaluation moved into wall_face_vars -- the payload keeps its bits)
+  WallVars wt;
+  wall_face_vars(b, g, d, ws.side, fi, fj, fk, qU, qL, fourth, wt);
+  const WallVars w = wt;
   // the factors of output.cpp:519-553
   const double rR = sp.rho_ref, aR = sp.a_ref, lR = sp.l_ref, tR = sp.t_ref, muR = sp.mu_ref;
   const double tau_sc = (1.0 / g.scaling) * muR * aR / lR;
@@ -3662,7 +3679,7 @@ k_wall_pack(BlockDev b, GasDev g, OutSpec sp, const WallSurfDev* __restrict__ ta
       case AGX_WALL_HEAT_FLUX: val = w.heat_flux * (muR * tR / lR); break;
       case AGX_WALL_FRICTION_VELOCITY: val = w.friction_velocity * aR; break;
       case AGX_WALL_DENSITY: val = w.density * rR; break;
-      case AGX_WALL_PRESSURE: val = w.density * g.R * w.temperature * (rR * aR * aR); break;
+      case AGX_WALL_PRESSURE: val = wall_face_pressure(g, w) * (rR * aR * aR); break;
       case AGX_WALL_TEMPERATURE: val = w.temperature * tR; break;
       case AGX_WALL_VISCOSITY: val = w.viscosity * (muR * (1.0 / g.scaling)); break;
       case AGX_WALL_TKE: val = w.tke * (aR * aR); break;
@@ -3673,6 +3690,148 @@ k_wall_pack(BlockDev b, GasDev g, OutSpec sp, const WallSurfDev* __restrict__ ta
     }
     out[(long)v * total + t] = val;
   }
+}
+// Integrated wall loads (agx_output_pack with AGX_LOAD_*; no counterpart in the reference):
+// area, area vector, pressure and viscous force, heat load and the two moments about the
+// origin of every load surface (viscousWall and slipWall) of a block.  m = sigma n is the
+// wall's unit normal into the fluid: n the stored area vector of the face, sigma = +1 on
+// lower sides, -1 on upper sides.  A viscousWall face of a viscous context takes pressure,
+// shear vector and heat flux from wall_face_vars, i.e. what k_wall_pack hands out; every
+// other face the pressure of its wall-adjacent physical cell and no shear, no heat flux.
+//
+// Two stages, no floating-point atomics, a shape that depends on the surfaces alone: the
+// faces of a surface are cut into chunks of 256 (a chunk never spans two surfaces, the last
+// chunk of a surface is padded with zero terms); a workgroup sums its chunk -- inside a wave
+// by shuffles over the distances 32, 16 .. 1, the four waves through LDS in wave order -- and
+// stores one record of LOAD_NQ sums; k_wall_loads_sum adds the records of a surface in
+// ascending chunk order and applies the dimensional factors.  All LOAD_NQ sums are formed
+// on every call, so a subset of ids returns the bits of the full call.
+enum { LOAD_NQ = AGX_LOAD_END - AGX_LOAD_BASE, LOAD_CHUNK = 256 };
+struct LoadSurfDev {
+  int lo[3], n[3];     // first face / cell index and count per direction (1 across the wall)
+  int side;            // surface type 1..6
+  int visc;            // a viscousWall surface (0: slipWall)
+  long off;            // first face of the surface among the block's load-surface faces
+  long chunk0;         // its first chunk
+};
+__device__ __forceinline__ void load_face_index(const LoadSurfDev& ws, long r, int& fi, int& fj,
+                                                int& fk) {
+  fi = ws.lo[0] + (int)(r % ws.n[0]);
+  fj = ws.lo[1] + (int)((r / ws.n[0]) % ws.n[1]);
+  fk = ws.lo[2] + (int)(r / ((long)ws.n[0] * ws.n[1]));
+}
+// agx_setup_finalize, node-built blocks: the centres of the load-surface faces, component c
+// of face t at out[c * total + t], kept for the moments once the face-centre planes are gone
+__global__ void __launch_bounds__(256)
+k_load_centres(BlockDev b, const double* __restrict__ fcen, const LoadSurfDev* __restrict__ tab,
+               int nsurf, long total, double* __restrict__ out) {
+  const long t = (long)blockIdx.x * blockDim.x + threadIdx.x;
+  if (t >= total) return;
+  int sn = 0;
+  while (sn + 1 < nsurf && t >= tab[sn + 1].off) ++sn;
+  const LoadSurfDev ws = tab[sn];
+  int fi, fj, fk;
+  load_face_index(ws, t - ws.off, fi, fj, fk);
+  const int d = (ws.side - 1) / 2;
+  const long q = b.idx(fi, fj, fk);
+  for (int c = 0; c < 3; ++c) out[(long)c * total + t] = fcen[(long)(3 * d + c) * b.nplane + q];
+}
+// viscous: a viscous context; fc: k_load_centres' output or null (the moments come out 0 and
+// the host refuses their ids); partial: [chunk][LOAD_NQ], nondimensional
+__global__ void __launch_bounds__(LOAD_CHUNK)
+k_wall_loads(BlockDev b, GasDev g, const LoadSurfDev* __restrict__ tab, int nsurf, long total,
+             int viscous, int fourth, const double* __restrict__ fc,
+             double* __restrict__ partial) {
+  __shared__ double red[LOAD_CHUNK / 64][LOAD_NQ];
+  const long ch = blockIdx.x;
+  int sn = 0;
+  while (sn + 1 < nsurf && ch >= tab[sn + 1].chunk0) ++sn;
+  const LoadSurfDev ws = tab[sn];
+  const long r = (ch - ws.chunk0) * LOAD_CHUNK + threadIdx.x;
+  double s[LOAD_NQ];
+#pragma unroll
+  for (int v = 0; v < LOAD_NQ; ++v) s[v] = 0.0;
+  if (r < (long)ws.n[0] * ws.n[1] * ws.n[2]) {
+    int fi, fj, fk;
+    load_face_index(ws, r, fi, fj, fk);
+    const int d = (ws.side - 1) / 2;
+    const long qU = b.idx(fi, fj, fk), qL = qU - b.stride(d);
+    double pw, tau[3] = {0.0, 0.0, 0.0}, qn = 0.0;
+    if (viscous && ws.visc) {
+      WallVars w;
+      wall_face_vars(b, g, d, ws.side, fi, fj, fk, qU, qL, fourth, w);
+      pw = wall_face_pressure(g, w);
+      for (int c = 0; c < 3; ++c) tau[c] = w.shear[c];
+      qn = w.heat_flux;
+    } else {
+      // (the ghost rule keeps the ghost pressure equal to it, ghostStates.cpp:109-121)
+      pw = b.state[4][ws.side % 2 == 1 ? qU : qL];
+    }
+    double n[4];
+    load_area(b, d, qU, n);
+    const double sg = ws.side % 2 == 1 ? 1.0 : -1.0, a = n[3];
+    s[AGX_LOAD_AREA - AGX_LOAD_BASE] = a;
+    s[AGX_LOAD_HEAT - AGX_LOAD_BASE] = sg * qn * a;
+#pragma unroll
+    for (int c = 0; c < 3; ++c) {
+      const double ma = sg * n[c] * a;
+      s[AGX_LOAD_AREA_X - AGX_LOAD_BASE + c] = ma;
+      s[AGX_LOAD_PRESSURE_FORCE_X - AGX_LOAD_BASE + c] = -(pw * ma);
+      s[AGX_LOAD_VISCOUS_FORCE_X - AGX_LOAD_BASE + c] = sg * tau[c] * a;
+    }
+    if (fc) {
+      const long t = ws.off + r;
+      const double rf[3] = {fc[t], fc[total + t], fc[2 * total + t]};
+      const double* fp = s + (AGX_LOAD_PRESSURE_FORCE_X - AGX_LOAD_BASE);
+      const double* fv = s + (AGX_LOAD_VISCOUS_FORCE_X - AGX_LOAD_BASE);
+#pragma unroll
+      for (int c = 0; c < 3; ++c) {
+        const int c1 = (c + 1) % 3, c2 = (c + 2) % 3;
+        s[AGX_LOAD_PRESSURE_MOMENT_X - AGX_LOAD_BASE + c] = rf[c1] * fp[c2] - rf[c2] * fp[c1];
+        s[AGX_LOAD_VISCOUS_MOMENT_X - AGX_LOAD_BASE + c] = rf[c1] * fv[c2] - rf[c2] * fv[c1];
+      }
+    }
+  }
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+#pragma unroll
+  for (int v = 0; v < LOAD_NQ; ++v) {
+    double x = s[v];
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) x += __shfl_down(x, o, 64);
+    if (lane == 0) red[wave][v] = x;
+  }
+  __syncthreads();
+  if (threadIdx.x < LOAD_NQ) {
+    double x = red[0][threadIdx.x];
+    for (int wv = 1; wv < LOAD_CHUNK / 64; ++wv) x += red[wv][threadIdx.x];
+    partial[ch * LOAD_NQ + threadIdx.x] = x;
+  }
+}
+// One thread per (variable of the call, surface): the surface's chunk records in ascending
+// order, then the factor: areas l_ref^2, pressure rho_ref a_ref^2, shear and heat flux those
+// of k_wall_pack, face centres l_ref.  out[v * nsurf + s]
+__global__ void __launch_bounds__(64)
+k_wall_loads_sum(OutSpec sp, const LoadSurfDev* __restrict__ tab, int nsurf, long nchunk,
+                 double inv_scaling, const double* __restrict__ partial,
+                 double* __restrict__ out) {
+  const int t = blockIdx.x * blockDim.x + threadIdx.x;
+  if (t >= sp.nvar * nsurf) return;
+  const int v = t / nsurf, sn = t % nsurf;
+  const int q = sp.var[v] - AGX_LOAD_BASE;
+  const long c0 = tab[sn].chunk0, c1 = sn + 1 < nsurf ? tab[sn + 1].chunk0 : nchunk;
+  double x = 0.0;
+  for (long ch = c0; ch < c1; ++ch) x += partial[ch * LOAD_NQ + q];
+  const double lR = sp.l_ref, a2 = lR * lR;
+  const double p_sc = sp.rho_ref * sp.a_ref * sp.a_ref;
+  const double tau_sc = inv_scaling * sp.mu_ref * sp.a_ref / lR;
+  double f;
+  if (q < AGX_LOAD_PRESSURE_FORCE_X - AGX_LOAD_BASE) f = a2;
+  else if (q < AGX_LOAD_VISCOUS_FORCE_X - AGX_LOAD_BASE) f = p_sc * a2;
+  else if (q < AGX_LOAD_HEAT - AGX_LOAD_BASE) f = tau_sc * a2;
+  else if (q == AGX_LOAD_HEAT - AGX_LOAD_BASE) f = (sp.mu_ref * sp.t_ref / lR) * a2;
+  else if (q < AGX_LOAD_VISCOUS_MOMENT_X - AGX_LOAD_BASE) f = p_sc * a2 * lR;
+  else f = tau_sc * a2 * lR;
+  out[t] = x * f;
 }
 // ---------------------------------------------------------------------------
 // WriteNodeFun (output.cpp:452-469): the nodal function file, procBlock::CellToNode

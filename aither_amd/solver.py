@@ -269,6 +269,72 @@ class Solver:
             res[name] = rows
         return res
 
+    def load_surfaces(self, gb):
+        """The load surfaces of block gb -- viscousWall and slipWall -- in the order of the
+        load payload (the order the library got them in): like wall_surfaces, with each
+        surface's bc_type."""
+        out = []
+        for s in self.case.blocks[gb].surfaces:
+            if s.bc_type not in ("viscousWall", "slipWall"):
+                continue
+            side = s.surface_type()
+            d = (side - 1) // 2
+            n = [s.imax - s.imin, s.jmax - s.jmin, s.kmax - s.kmin]
+            n[d] = 1
+            out.append(dict(side=side, tag=s.tag, bc_type=s.bc_type,
+                            range=(s.imin, s.imax, s.jmin, s.jmax, s.kmin, s.kmax),
+                            shape=(n[2], n[1], n[0])))
+        return out
+
+    def load_names(self, gb):
+        """The load variables block gb can give: all of abi.LOAD_OUT for a block built from its
+        nodes, without the moments for one built from host arrays (no face centres)."""
+        node_built = isinstance(self.case.blocks[gb].geom, _geo.NodeGeometry)
+        return [n for n in abi.LOAD_OUT if node_built or n not in abi.LOAD_MOMENTS]
+
+    def wall_loads(self, gb, names=None, about=None):
+        """The integrated loads of block gb's load surfaces (abi.LOAD_OUT), summed by the
+        library: {name: ndarray[nsurf]}, dimensional, on the wall (the normal points into the
+        fluid).  names: default load_names(gb).  about: a reference point (x, y, z) in metres;
+        the moments come back about it, M - about x F (the forces are fetched if the call
+        does not name them)."""
+        names = list(self.load_names(gb) if names is None else names)
+        ask = list(names)
+        if about is not None:
+            for kind in ("pressure", "viscous"):
+                if any(n.startswith(kind + "Moment") for n in names):
+                    ask += [f"{kind}Force_{c}" for c in "xyz" if f"{kind}Force_{c}" not in ask]
+        nsurf = len(self.load_surfaces(gb))
+        ids = (C.c_int32 * len(ask))(*[abi.LOAD_OUT[n] for n in ask])
+        out = np.empty((len(ask), max(nsurf, 1)))
+        self.api.check(self.api.output_pack(self.ctx, self.block_ids[gb], len(ask), ids,
+                                            out.ctypes.data_as(abi.c_dp)), "output_pack")
+        got = {n: out[q, :nsurf].copy() for q, n in enumerate(ask)}
+        if about is not None:
+            r = [float(x) for x in about]
+            for kind in ("pressure", "viscous"):
+                f = [got.get(f"{kind}Force_{c}") for c in "xyz"]
+                for c, name in enumerate(f"{kind}Moment_{x}" for x in "xyz"):
+                    if name in names:
+                        c1, c2 = (c + 1) % 3, (c + 2) % 3
+                        got[name] = got[name] - (r[c1] * f[c2] - r[c2] * f[c1])
+        return {n: got[n] for n in names}
+
+    def total_loads(self, tags=None, about=None):
+        """The loads of this rank's blocks summed over their load surfaces, in the fixed order
+        (block, surface): {name: float}.  tags: only surfaces whose BC tag is listed.  The
+        names are those every block with a load surface can give."""
+        blocks = [gb for gb in sorted(self.block_ids) if self.load_surfaces(gb)]
+        names = [n for n in abi.LOAD_OUT if all(n in self.load_names(gb) for gb in blocks)]
+        total = {n: 0.0 for n in names}
+        for gb in blocks:
+            got = self.wall_loads(gb, names, about=about)
+            for q, s in enumerate(self.load_surfaces(gb)):
+                if tags is None or s["tag"] in tags:
+                    for n in names:
+                        total[n] += float(got[n][q])
+        return total
+
     def restart_pack(self, gb, which=0):
         """WriteRestart's payload of block gb: [nk, nj, ni, n_eq + 1], dimensional."""
         g = self.case.blocks[gb].geom
@@ -472,6 +538,15 @@ class MultigridSolver:
 
     def download(self, field, gb, level=0):
         return self.levels[level].download(field, gb)
+
+    def load_surfaces(self, gb, level=0):
+        return self.levels[level].load_surfaces(gb)
+
+    def wall_loads(self, gb, names=None, about=None, level=0):
+        return self.levels[level].wall_loads(gb, names, about)
+
+    def total_loads(self, tags=None, about=None, level=0):
+        return self.levels[level].total_loads(tags, about)
 
     def _p(self, a, ctype):
         return a.ctypes.data_as(C.POINTER(ctype))

@@ -197,6 +197,49 @@ enum { AGX_WALL_YPLUS = 64, AGX_WALL_SHEAR_STRESS, AGX_WALL_VISCOSITY_RATIO, AGX
  * cells (the reference converts the recombined block). */
 enum { AGX_NODE_BASE = 128, AGX_NODE_END = AGX_NODE_BASE + AGX_OUT_COUNT };
 
+/* integrated wall loads: a fourth range of agx_output_pack, with no counterpart in the
+ * reference (output.cpp writes per-face wall data only).  One value per LOAD SURFACE of the
+ * block -- its viscousWall and slipWall surfaces in the order agx_block_set_bcs got them --
+ * dimensional (SI): out[v * nsurf + s].  Sums over the faces of the surface, with |A| the
+ * face's area, n its stored unit area vector (direction of increasing index), r_f its centre:
+ *   area                  sum |A|
+ *   area_x/y/z            sum m |A|
+ *   pressureForce_x/y/z   - sum p m |A|
+ *   viscousForce_x/y/z    sum (tau . m) |A|
+ *   heatLoad              sum (k + kt) grad T . m |A|: heat flowing from the fluid into the wall
+ *   pressureMoment_x/y/z  sum r_f x (- p m |A|), about the origin
+ *   viscousMoment_x/y/z   sum r_f x ((tau . m) |A|), about the origin
+ * Orientation: m = sigma n is the wall's unit normal pointing INTO THE FLUID, sigma = +1 on
+ * lower sides (surface types 1, 3, 5), -1 on upper sides (2, 4, 6); the sums are the loads
+ * the fluid puts on the wall.  A box of gas at rest pushes its i-min wall towards -x;
+ * u = a y with a > 0 over a j-min wall drags that wall towards +x; gas hotter than a j-min
+ * wall gives it a positive heat load.
+ * Face values.  viscousWall faces of a viscous context: exactly what AGX_WALL_PRESSURE,
+ * AGX_WALL_SHEAR_X/Y/Z and AGX_WALL_HEAT_FLUX hand out for the face (same evaluation, same
+ * timing: low-Re faces from the state now and the ghost cells the next residual would see,
+ * wall-law faces the stored wall data), areas times l_ref^2, face centres times l_ref.
+ * slipWall faces, and every load surface of an inviscid context: p of the wall-adjacent
+ * physical cell (the ghost rule keeps the ghost pressure equal to it,
+ * ghostStates.cpp:109-121), no shear, no heat flux.
+ * Moments need face centres, which the device holds for node-built blocks only
+ * (agx_block_geom.nodes: the centres of the load-surface faces are kept from
+ * agx_setup_finalize on); a block built from arrays refuses the six moment ids by name and
+ * approximates nothing.  Another reference point is the caller's M - r_ref x F.
+ * Timing and legality.  A viscous context: a ghost-refilling read like the wall variables
+ * ("reads between phases" at agx_field_download).  An inviscid context: physical cells only,
+ * legal at every position.  Not a collective: a rank gets the loads of its own blocks.
+ * No floating-point atomics and a summation shape fixed by the surfaces alone (chunks of 256
+ * faces, added in ascending order): two calls, and any subset, order or repetition of ids,
+ * return the same bits. */
+enum { AGX_LOAD_BASE = 256, AGX_LOAD_AREA = AGX_LOAD_BASE,
+       AGX_LOAD_AREA_X, AGX_LOAD_AREA_Y, AGX_LOAD_AREA_Z,
+       AGX_LOAD_PRESSURE_FORCE_X, AGX_LOAD_PRESSURE_FORCE_Y, AGX_LOAD_PRESSURE_FORCE_Z,
+       AGX_LOAD_VISCOUS_FORCE_X, AGX_LOAD_VISCOUS_FORCE_Y, AGX_LOAD_VISCOUS_FORCE_Z,
+       AGX_LOAD_HEAT,
+       AGX_LOAD_PRESSURE_MOMENT_X, AGX_LOAD_PRESSURE_MOMENT_Y, AGX_LOAD_PRESSURE_MOMENT_Z,
+       AGX_LOAD_VISCOUS_MOMENT_X, AGX_LOAD_VISCOUS_MOMENT_Y, AGX_LOAD_VISCOUS_MOMENT_Z,
+       AGX_LOAD_END };
+
 /* what a halo exchange carries (gridLevel.cpp:299-313, utility.cpp:400-423) */
 enum { AGX_HALO_STATE = 0, AGX_HALO_UPDATE = 1,
        /* velocityGrad_ of the cells across connection surfaces, swapped after the
@@ -383,7 +426,8 @@ int agx_state_upload(agx_ctx *ctx, int block_id, const double *state_aos);
  * One group is the exception, because it refills the ghost cells of the state (inviscid fill,
  * then the viscous-wall fill, which stays): the gradient fields (AGX_FIELD_VEL_GRAD ..
  * AGX_FIELD_PRESS_GRAD), and of agx_output_pack the gradient variables, every node variable
- * and every wall variable.  From the caller's agx_phase_bc_faces up to the
+ * and every wall variable, and on a viscous context every load variable (AGX_LOAD_*; an
+ * inviscid context reads physical cells only there).  From the caller's agx_phase_bc_faces up to the
  * agx_phase_residual that follows it the ghost cells are being filled for that residual, and
  * these calls are REFUSED with a message; they are legal from agx_phase_residual to the next
  * agx_phase_bc_faces, and between agx_iterate calls (agx_iterate's own fill does not count). */
@@ -443,12 +487,19 @@ int agx_phase_implicit_update(agx_ctx *ctx, int mm, double *l2, agx_linf *linf);
  * payload of the nodal function file of one block instead -- variable by variable in the
  * caller's order, within a variable the (nk+1)(nj+1)(ni+1) nodes, i fastest (the loop nest of
  * output.cpp:231-233 over the node block): out[v * nnodes + node].
+ * Integrated wall loads (no counterpart in output.cpp): with load variables (AGX_LOAD_*) one
+ * value per load surface of the block instead -- its viscousWall and slipWall surfaces in the
+ * order agx_block_set_bcs got them -- variable by variable in the caller's order:
+ * out[v * nsurf + surface], see the enum.
  * Refused: variables of two ranges in one call, an id in no range, a block without a
  * viscousWall surface, an inviscid context, wall-law surfaces before the first residual (the
  * three: wall variables), the four node variables named above, nvar beyond the number of ids
- * of its range (repeated ids are allowed in all three); gradient, node and wall variables
+ * of its range (repeated ids are allowed in all four); gradient, node and wall variables
  * between agx_phase_bc_faces and the agx_phase_residual that follows it ("reads between
- * phases" at agx_field_download). */
+ * phases" at agx_field_download).  Load variables: a block without a viscousWall or slipWall
+ * surface, a call before agx_setup_finalize, wall-law surfaces before the first residual, the
+ * six moment ids on a block built from arrays, and -- a viscous context only -- the interval
+ * between agx_phase_bc_faces and agx_phase_residual. */
 int agx_output_pack(agx_ctx *ctx, int block, int nvar, const int32_t *vars, double *out);
 /* WriteRestart (output.cpp:651-752), the payload of one block: cell by cell (i fastest)
  * n_eq + 1 dimensional values -- density, velocity, pressure, [tke, sdr,] mass fraction of

@@ -164,6 +164,17 @@ class hotPath {
     Check(AGX_SYM(output_pack)(ctx_, block, static_cast<int>(vars.size()), vars.data(), out),
           "hotPath::WallPack");
   }
+  // No counterpart in output.cpp: the integrated loads of the block's load surfaces -- its
+  // viscousWall and slipWall surfaces in the order SetBCs got them -- summed on the device:
+  // the listed variables (AGX_LOAD_*: area, area vector, pressure and viscous force, heat
+  // load, pressure and viscous moment about the origin), variable by variable, one value per
+  // surface, dimensional; `out` holds vars.size() * (load surfaces) values.  The normal points
+  // into the fluid, so these are the loads ON the wall (see the header); the moment ids need a
+  // block built from its nodes.  A moment about r_ref is M - r_ref x F of the same call
+  void SurfaceLoads(int block, const std::vector<int32_t> &vars, double *out) const {
+    Check(AGX_SYM(output_pack)(ctx_, block, static_cast<int>(vars.size()), vars.data(), out),
+          "hotPath::SurfaceLoads");
+  }
   // WriteNodeFun (output.cpp:452-469): the block's payload of the nodal function file -- the
   // listed variables by their cell ids (AGX_OUT_*; AGX_NODE_BASE is added here), converted to
   // the (nk+1)(nj+1)(ni+1) nodes on the device (procBlock::CellToNode), variable by variable,
