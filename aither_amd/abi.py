@@ -12,7 +12,7 @@ FLUX = {"roe": 0, "ausm": 1}
 TIME = {"explicitEuler": 0, "rk4": 1, "implicitEuler": 2,
         "crankNicholson": 3, "bdf2": 4}
 SOLVER = {"lusgs": 0, "dplur": 1, "blusgs": 2, "bdplur": 3}
-EQN = {"euler": 0, "navierStokes": 1, "rans": 2}
+EQN = {"euler": 0, "navierStokes": 1, "rans": 2, "largeEddySimulation": 3}
 JACOBIAN = {"rusanov": 0, "approximateRoe": 1}
 VISC_RECON = {"central": 0, "centralFourth": 1}
 TURB = {"none": 0, "sst2003": 1, "kOmegaWilcox2006": 2, "sstdes": 3, "wale": 4}

@@ -121,10 +121,14 @@ class InputDeck:
                                          "bdf2")
 
     def is_viscous(self):
-        return self.equation_set in ("navierStokes", "rans")
+        return self.equation_set in ("navierStokes", "rans", "largeEddySimulation")
 
     def is_rans(self):
         return self.equation_set == "rans"
+
+    def is_turbulent(self):
+        # input::IsTurbulent: rans or largeEddySimulation (input.cpp:694-709)
+        return self.equation_set in ("rans", "largeEddySimulation")
 
     def is_multilevel_in_time(self):
         return self.time_integration == "bdf2"
@@ -190,8 +194,19 @@ class InputDeck:
         bad = []
         if len(self.fluids) != 1:
             bad.append("multi-species")
-        if self.equation_set not in ("euler", "navierStokes", "rans"):
+        if self.equation_set not in ("euler", "navierStokes", "rans", "largeEddySimulation"):
             bad.append(f"equationSet {self.equation_set}")
+        # input::CheckTurbulenceModel, input.cpp:965-979
+        les = self.equation_set == "largeEddySimulation"
+        if les and self.turbulence_model == "none":
+            bad.append("equationSet largeEddySimulation without a turbulenceModel "
+                       "(input.cpp:965-969)")
+        elif les and self.turbulence_model != "wale":
+            bad.append(f"equationSet largeEddySimulation with turbulenceModel "
+                       f"{self.turbulence_model}: it accepts wale only (input.cpp:979-982)")
+        if not les and self.turbulence_model == "wale":
+            bad.append(f"turbulenceModel wale with equationSet {self.equation_set}: it is the "
+                       "model of largeEddySimulation (input.cpp:970-978)")
         if self.equation_set == "rans" and self.turbulence_model not in ("sst2003", "sstdes",
                                                                          "kOmegaWilcox2006"):
             bad.append(f"turbulenceModel {self.turbulence_model}")

@@ -1675,14 +1675,29 @@ int agx_config_set(agx_ctx* c, const agx_config* cfg) {
   if (cfg->inv_flux_jacobian == AGX_JACOBIAN_APPROX_ROE)
     return fail("rans: approximateRoe is not built");
 #else
-  if (cfg->equation_set != AGX_EQN_EULER && cfg->equation_set != AGX_EQN_NAVIER_STOKES)
-    return fail("equation_set %d: this library covers euler and navierStokes "
-                "(rans: libaither_gfx950_rans.so)", cfg->equation_set);
-  if ((cfg->equation_set == AGX_EQN_NAVIER_STOKES) != (cfg->is_viscous != 0))
+  const bool les = cfg->equation_set == AGX_EQN_LES;
+  if (cfg->equation_set != AGX_EQN_EULER && cfg->equation_set != AGX_EQN_NAVIER_STOKES && !les)
+    return fail("equation_set %d: this library covers euler, navierStokes and "
+                "largeEddySimulation (rans: libaither_gfx950_rans.so)", cfg->equation_set);
+  if ((cfg->equation_set == AGX_EQN_NAVIER_STOKES || les) != (cfg->is_viscous != 0))
     return fail("equation_set %d contradicts is_viscous %d", cfg->equation_set, cfg->is_viscous);
-  if (cfg->turbulence_model != AGX_TURB_NONE)
-    return fail("turbulence_model %d is not built (laminar / inviscid only)",
-                cfg->turbulence_model);
+  // input::CheckTurbulenceModel input.cpp:965-979
+  if (les && cfg->turbulence_model != AGX_TURB_WALE)
+    return fail("equation_set largeEddySimulation with turbulence_model %d: it accepts wale "
+                "only, and needs it (input.cpp:965-969, :979-982)", cfg->turbulence_model);
+  if (!les && cfg->turbulence_model == AGX_TURB_WALE)
+    return fail("turbulence_model wale with equation_set %d: wale is the model of "
+                "largeEddySimulation and of no other equation set (input.cpp:970-978)",
+                cfg->equation_set);
+  if (cfg->turbulence_model != AGX_TURB_NONE && !les)
+    return fail("turbulence_model %d is not built (laminar / inviscid, or wale with "
+                "largeEddySimulation)", cfg->turbulence_model);
+  if (les && cfg->time_integration >= AGX_TIME_IMPLICIT_EULER)
+    return fail("largeEddySimulation with an implicit time_integration (%d: implicitEuler, "
+                "crankNicholson, bdf2) is not built: the scalar and block off-diagonals and "
+                "diagonals with an eddy viscosity in a 5-equation run have no independent "
+                "reference while the oracle does not carry the model; explicitEuler and rk4 "
+                "are built", cfg->time_integration);
 #endif
   if (cfg->inv_flux_jacobian != AGX_JACOBIAN_RUSANOV &&
       cfg->inv_flux_jacobian != AGX_JACOBIAN_APPROX_ROE)
@@ -1730,6 +1745,7 @@ int agx_config_set(agx_ctx* c, const agx_config* cfg) {
   sp.block = (cfg->matrix_solver == AGX_SOLVER_BLUSGS || cfg->matrix_solver == AGX_SOLVER_BDPLUR) ? 1 : 0;
   sp.time_integration = cfg->time_integration;
   sp.roe_jacobian = cfg->inv_flux_jacobian == AGX_JACOBIAN_APPROX_ROE;
+  sp.les = cfg->equation_set == AGX_EQN_LES ? 1 : 0;
   c->have_cfg = true;
   return 0;
 }
@@ -1765,8 +1781,11 @@ int agx_block_create(agx_ctx* c, const agx_block_geom* g, int* block_id) {
   d.sxy = d.sx * (d.nj + 2 * d.ng + 1);
   d.nplane = d.sxy * (d.nk + 2 * d.ng + 1);
   // one slab for all planes of the block (see SlabDev in agx_kernels.hpp)
-  HIPCHK(b.slab.alloc((size_t)d.nplane * PL_COUNT));
-  HIPCHK(hipMemsetAsync(b.slab.get(), 0, sizeof(double) * d.nplane * PL_COUNT, c->stream));
+  // (largeEddySimulation: one plane more, eddyViscosity_ of the cells; every other run keeps
+  // its footprint)
+  const int nplanes = PL_COUNT + (c->sp.les ? 1 : 0);
+  HIPCHK(b.slab.alloc((size_t)d.nplane * nplanes));
+  HIPCHK(hipMemsetAsync(b.slab.get(), 0, sizeof(double) * d.nplane * nplanes, c->stream));
   auto pl = [&](int id) { return b.slab.get() + (long)id * d.nplane; };
   d.vol = pl(PL_VOL); d.specrad = pl(PL_SPECRAD); d.dt = pl(PL_DT);
   d.a = pl(PL_A); d.ainv = pl(PL_AINV); d.wdist = pl(PL_WDIST);
@@ -1786,6 +1805,8 @@ int agx_block_create(agx_ctx* c, const agx_block_geom* g, int* block_id) {
   d.specrad_t = pl(PL_SPECRAD_T); d.a_t = pl(PL_A_T); d.ainv_t = pl(PL_AINV_T);
   d.viscp = pl(PL_VISC);
   for (int q = 0; q < 3; ++q) d.turb3[q] = pl(PL_TURB3 + q);
+#else
+  if (c->sp.les) d.turb3[0] = pl(PL_EDDY_LES);
 #endif
   if (c->sp.implicit && is_block_solver(c)) {
     // a_, aInv_ (25 planes each) and velocityGrad_ (9) of the block-matrix solvers
@@ -2447,7 +2468,9 @@ int wall_pack(agx_ctx* c, int id, int nvar, const int32_t* vars, double* out) {
   double* tmp = nullptr;
   if (stage_buffer(c, (size_t)nvar * total, &tmp)) return 1;
   if (ghosts_for_output(c, "agx_output_pack")) return 1;
-  const int fourth = c->cfg.viscous_recon == AGX_VISC_RECON_CENTRAL_4TH ? 1 : 0;
+  // (bit 1: a largeEddySimulation run, wall_face_vars)
+  const int fourth = (c->cfg.viscous_recon == AGX_VISC_RECON_CENTRAL_4TH ? 1 : 0) |
+                     (c->sp.les ? 2 : 0);
   hipLaunchKernelGGL(k_wall_pack, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, c->stream,
                      b.d, c->gas, out_spec(c, b, nvar, vars), b.wall_tab_dev.get(),
                      (int)b.wall_tab.size(), total, fourth, tmp);
@@ -2481,7 +2504,8 @@ int wall_loads(agx_ctx* c, int id, int nvar, const int32_t* vars, double* out) {
   // a viscous context evaluates its viscousWall faces with the ghost cells the next residual
   // would see; an inviscid one reads physical cells only
   if (viscous && ghosts_for_output(c, "agx_output_pack")) return 1;
-  const int fourth = c->cfg.viscous_recon == AGX_VISC_RECON_CENTRAL_4TH ? 1 : 0;
+  const int fourth = (c->cfg.viscous_recon == AGX_VISC_RECON_CENTRAL_4TH ? 1 : 0) |
+                     (c->sp.les ? 2 : 0);
   hipLaunchKernelGGL(k_wall_loads, dim3((unsigned)b.load_chunks), dim3(LOAD_CHUNK), 0, c->stream,
                      b.d, c->gas, b.load_tab_dev.get(), nsurf, b.load_faces, viscous ? 1 : 0,
                      fourth, b.load_fcen.get(), b.load_partial.get());
@@ -2500,15 +2524,14 @@ int point_pack(agx_ctx* c, int id, bool node, int nvar, const int32_t* vars, dou
     const int var = vars[v];
     if (var == AGX_OUT_VISCOSITY && !c->sp.viscous)
       return fail("viscosity_ is only kept for viscous runs (procBlock.cpp:6171)");
-#if AGX_NEQ == 7
-    if (node && (var == AGX_OUT_VISCOSITY_RATIO || var == AGX_OUT_TURB_VISCOSITY ||
-                 var == AGX_OUT_F1 || var == AGX_OUT_F2))
+    if ((AGX_NEQ == 7 || c->sp.les) && node &&
+        (var == AGX_OUT_VISCOSITY_RATIO || var == AGX_OUT_TURB_VISCOSITY ||
+         var == AGX_OUT_F1 || var == AGX_OUT_F2))
       return fail("agx_output_pack: node variable %d (viscosityRatio, turbulentViscosity, f1, f2) "
                   "is not formed at nodes: the reference averages eddyViscosity_, f1_, f2_ with "
                   "their ghost cells, which hold what the residual's accumulation at boundary "
                   "faces and the corner initial values left; the library keeps them in physical "
                   "cells and connection ghost cells only", AGX_NODE_BASE + var);
-#endif
     need_grads = need_grads || (var >= AGX_OUT_VELGRAD && var < AGX_OUT_RESID);
   }
   const int n1 = node ? 1 : 0;      // one node more than cells along each direction
@@ -2991,11 +3014,13 @@ int agx_phase_residual(agx_ctx* c, int mm, double cfl) {
     {
       const bool fourth = c->cfg.viscous_recon == AGX_VISC_RECON_CENTRAL_4TH;
       const bool wide_plane = (double)blk.d.nplane * 8.0 >= 4294967296.0;
-      if (!AGX_FAST || c->visc_gather || (fourth && (c->visc_march || wide_plane))) {
+      if (!AGX_FAST || c->visc_gather || ((fourth || c->sp.les) && (c->visc_march || wide_plane))) {
         // (one thread per cell, the stencil straight from the planes: AGX_VISC=gather, and
-        // centralFourth where the tile kernel's 32-bit plane offsets do not reach)
-        hipLaunchKernelGGL(k_visc_residual, cell_grid(blk.d, CELL_BLOCK), CELL_BLOCK,
-                           0, c->stream, blk.d, c->gas, c->sp, cfl, fourth ? 1 : 0);
+        // centralFourth or largeEddySimulation -- k_visc_march has no WALE arm -- where the
+        // tile kernel's 32-bit plane offsets do not reach)
+        hipLaunchKernelGGL(c->sp.les ? k_visc_residual_les : k_visc_residual,
+                           cell_grid(blk.d, CELL_BLOCK), CELL_BLOCK, 0, c->stream, blk.d, c->gas,
+                           c->sp, cfl, fourth ? 1 : 0);
       } else {
         const BlockDev& vb = blk.d;
         if (c->visc_march || wide_plane) {
@@ -3018,7 +3043,15 @@ int agx_phase_residual(agx_ctx* c, int mm, double cfl) {
         const TilePlan tp = tile_plan_of(c, gx, gy, vb.nk, nwg,
                                          fourth ? TILE_CHARGE_VISC_F4 : TILE_CHARGE_VISC,
                                          c->tile_order_visc);
-        if (fourth)
+        // (largeEddySimulation: the instantiations with the WALE arm, which also write the
+        // run's eddy-viscosity plane)
+        if (c->sp.les && fourth)
+          hipLaunchKernelGGL((k_visc_tile<true, true>), dim3(nwg), dim3(VT_L, VT_R), 0, c->stream,
+                             make_slab(vb), c->gas, c->sp, cfl, gx, tp);
+        else if (c->sp.les)
+          hipLaunchKernelGGL((k_visc_tile<false, true>), dim3(nwg), dim3(VT_L, VT_R), 0, c->stream,
+                             make_slab(vb), c->gas, c->sp, cfl, gx, tp);
+        else if (fourth)
           hipLaunchKernelGGL(k_visc_tile<true>, dim3(nwg), dim3(VT_L, VT_R), 0, c->stream,
                              make_slab(vb), c->gas, c->sp, cfl, gx, tp);
         else

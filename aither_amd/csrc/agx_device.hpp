@@ -647,6 +647,36 @@ __device__ __forceinline__ double turb_diff_visc(const GasDev& g, const double* 
   return (AGX_NEQ > 5 && g.wilcox) ? s[0] * s[AGX_NEQ - 2] / s[AGX_NEQ - 1] : mut;
 }
 
+// turbWale::EddyVisc turbulence.cpp:967-996 (largeEddySimulation): the eddy viscosity of a
+// face from its Green-Gauss velocity gradient grad[r][c] = d u_c / d x_r (columns 0..2; the
+// value is the same for G and its transpose) and length = half the sum of the two cells'
+// widths across the face (procBlock.cpp:1357-1365).  No density, no InvNondimScaling: CalcFlux
+// multiplies it by NondimScaling like any viscosity.  The powers a^1.5, b^2.5, a^1.25 as
+// products and square roots (plain sqrt: a = 0 in pure shear).
+template <int NC>
+__device__ __forceinline__ double wale_eddy_visc(const double (*grad)[NC], double length) {
+  double g2[3][3];
+#pragma unroll
+  for (int r = 0; r < 3; ++r)
+#pragma unroll
+    for (int c = 0; c < 3; ++c)
+      g2[r][c] = grad[r][0] * grad[0][c] + grad[r][1] * grad[1][c] + grad[r][2] * grad[2][c];
+  const double third_tr = (1.0 / 3.0) * (g2[0][0] + g2[1][1] + g2[2][2]);
+  double a = 0.0, b = 0.0;
+#pragma unroll
+  for (int r = 0; r < 3; ++r)
+#pragma unroll
+    for (int c = 0; c < 3; ++c) {
+      const double sd = 0.5 * (g2[r][c] + g2[c][r]) - (r == c ? third_tr : 0.0);
+      const double s = 0.5 * (grad[r][c] + grad[c][r]);
+      a = fma(sd, sd, a);
+      b = fma(s, s, b);
+    }
+  const double ra = sqrt(a);
+  const double cl = 0.544 * length;          // Cw, turbulence.hpp:664
+  return (cl * cl) * (a * ra) / (b * b * sqrt(b) + a * sqrt(ra) + AGX_EPS);
+}
+
 // RusanovScalarOffDiagonal fluxJacobian.cpp:122-162 with FaceSpectralRadius
 // spectralRadius.hpp:182-203 and ConvectiveFluxUpdate inviscidFlux.hpp:544-562
 // diag != nullptr selects RoeOffDiagonal (fluxJacobian.cpp:240-291, inviscid): the

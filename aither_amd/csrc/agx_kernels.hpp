@@ -108,7 +108,10 @@ enum {
   PL_SPECRAD_T = PL_WDIST + 1, PL_A_T, PL_AINV_T, PL_VISC, PL_TURB3 /* mut, f1, f2 */,
   PL_COUNT = PL_TURB3 + 3
 #else
-  PL_COUNT = PL_WDIST + 1
+  PL_COUNT = PL_WDIST + 1,
+  // largeEddySimulation runs only: eddyViscosity_ of the cells, one plane past the slab that
+  // every other run allocates
+  PL_EDDY_LES = PL_COUNT
 #endif
 };
 // the LDS-tiled / diagonal-ordered production kernels are written for the
@@ -160,7 +163,12 @@ struct SolverDev {   // scalar run-time parameters of agx_config
   // consVarsN need not be read
   int un_is_u;
   int block;           // input::IsBlockMatrix (blusgs / bdplur)
+  // equationSet largeEddySimulation, turbulenceModel wale (5-equation libraries): the viscous
+  // kernels take their WALE arm.  (The struct's size and the other members' places are what
+  // they were: the flag lies in its tail padding.)
+  int les;
 };
+static_assert(sizeof(SolverDev) == 96, "SolverDev::les lies in the tail padding");
 
 __device__ __forceinline__ void load5(double* const* p, long q, double* s) {
 #pragma unroll
@@ -1319,19 +1327,28 @@ __device__ __forceinline__ void visc_face_terms(const BlockDev& b, const GasDev&
 // what the wall-surface output (k_wall_pack) keeps of a face besides its flux: TauNormal
 // (utility.cpp:426-437), the conductive heat flux k grad T . n (viscousFlux.cpp:170-178), the
 // face state and its laminar viscosity
-struct ViscWallOut { double tau[3], qn, sf[AGX_NEQ], muf; };
+struct ViscWallOut { double tau[3], qn, sf[AGX_NEQ], muf, mut; };
 // viscous flux * |A| through the lower d-face of cell index qU (cells qL|qU); WALL: also what
-// k_wall_pack keeps (an instantiation of its own: the residual kernels' is what it was)
-template <bool WALL = false>
+// k_wall_pack keeps (an instantiation of its own: the residual kernels' is what it was).
+// LES (largeEddySimulation, instantiations of their own again): the WALE eddy viscosity of the
+// face (EddyViscAndBlending procBlock.cpp:1357-1365, every face that is not a wall-law face)
+// joins mu in tau and, as mut cp(T_face) / Prt, the conductivity (viscousFlux.cpp:77-116);
+// *mut_out: the unscaled value, as eddyViscosity_ accumulates it
+template <bool WALL = false, bool LES = false>
 __device__ __forceinline__ void visc_face(const BlockDev& b, const GasDev& g,
                                           int d, long qU, double* f, bool fourth = false,
-                                          ViscWallOut* wo = nullptr) {
+                                          ViscWallOut* wo = nullptr, double* mut_out = nullptr) {
   double grad[3][4];          // [derivative direction][u, v, w, T]
   double sf[AGX_NEQ], muf;
   visc_face_terms(b, g, d, qU, fourth, grad, sf, muf);
   double n[4];
   load_area(b, d, qU, n);
-  const double mu = g.scaling * muf;
+  double mu = g.scaling * muf;
+  double mut = 0.0;
+  if constexpr (LES) {
+    mut = wale_eddy_visc(grad, 0.5 * (b.wid[d][qU - b.stride(d)] + b.wid[d][qU]));
+    mu += g.scaling * mut;
+  }
   const double lambda = -(2.0 / 3.0) * mu;
   const double trace = grad[0][0] + grad[1][1] + grad[2][2];
   double tau[3];
@@ -1342,7 +1359,11 @@ __device__ __forceinline__ void visc_face(const BlockDev& b, const GasDev& g,
                       (grad[r][2] + grad[2][r]) * n[2];
     tau[r] = lambda * trace * n[r] + mu * mm;
   }
-  const double kk = conductivity(g, temperature(g, sf)) * g.scaling;
+  double kk = conductivity(g, temperature(g, sf)) * g.scaling;
+  if constexpr (LES) {
+    kk += g.scaling * mut * cp_of(g, temperature(g, sf)) / g.turb_prandtl;
+    if (mut_out) *mut_out = mut;
+  }
   const double tg = grad[0][3] * n[0] + grad[1][3] * n[1] + grad[2][3] * n[2];
   f[0] = 0.0;
   f[1] = tau[0] * n[3];
@@ -1354,6 +1375,7 @@ __device__ __forceinline__ void visc_face(const BlockDev& b, const GasDev& g,
     wo->qn = kk * tg;
     for (int e = 0; e < AGX_NEQ; ++e) wo->sf[e] = sf[e];
     wo->muf = muf;
+    wo->mut = mut;
   }
 }
 
@@ -1440,6 +1462,61 @@ k_visc_residual(BlockDev b, GasDev g, SolverDev sp, double cfl, int fourth) {
   if (sp.implicit) b.a[q] = diag;
   b.dt[q] = sp.dt_fixed > 0.0 ? sp.dt_fixed : cfl * (vol / fmax(sr, 0.0));
 }
+
+#if AGX_NEQ == 5
+// k_visc_residual with the WALE arm of visc_face (largeEddySimulation; a kernel of its own,
+// launched for SolverDev::les -- k_visc_residual is the code it was): the mut
+// of the cell's LOWER face of each direction -- the face at which CalcViscFluxI/J/K call
+// ViscCellSpectralRadius for the cell, procBlock.cpp:1427-1455 -- enters the spectral radius
+// as mut / Prt (spectralRadius.hpp:94-123), and one sixth of the six faces' mut is the
+// cell's eddyViscosity_ (:1401-1402, :1436-1437), stored unscaled in the run's extra plane
+__device__ __forceinline__ void visc_residual_cell_les(const BlockDev& b, const GasDev& g,
+                                                   const SolverDev& sp, double cfl, int fourth,
+                                                   long q) {
+  double res[AGX_NEQ];
+  load5(b.resid, q, res);
+  double sr = b.specrad[q];
+  double diag = sp.implicit ? b.a[q] : 0.0;
+  double sc[AGX_NEQ];
+  load5(b.state, q, sc);
+  const double tc = temperature(g, sc);
+  const double muc = viscosity(g, tc);
+  const double vol = b.vol[q];
+  double mut_cell = 0.0;
+#pragma unroll
+  for (int d = 0; d < 3; ++d) {
+    const long s = b.stride(d);
+    double f[AGX_NEQ], mut_lo = 0.0, mut_up = 0.0;
+    visc_face<false, true>(b, g, d, q, f, fourth != 0, nullptr, &mut_lo);
+#pragma unroll
+    for (int e = 0; e < AGX_NEQ; ++e) res[e] += f[e];
+    visc_face<false, true>(b, g, d, q + s, f, fourth != 0, nullptr, &mut_up);
+#pragma unroll
+    for (int e = 0; e < AGX_NEQ; ++e) res[e] -= f[e];
+    // ViscCellSpectralRadius spectralRadius.hpp:94-124
+    const double fmag = 0.5 * (b.fa[d][3][q] + b.fa[d][3][q + s]);
+    const double vterm = g.scaling * (muc * inv_prandtl_of(g, tc) + mut_lo / g.turb_prandtl);
+    mut_cell += (1.0 / 6.0) * mut_lo;
+    mut_cell += (1.0 / 6.0) * mut_up;
+    const double vsr = visc_max_term(g, sc[0], tc) * vterm * fmag * fmag / vol;
+    sr += vsr * sp.visc_cfl_coeff;
+    diag += 2.0 * vsr;
+  }
+  store5(b.resid, q, res);
+  b.specrad[q] = sr;
+  if (sp.implicit) b.a[q] = diag;
+  b.dt[q] = sp.dt_fixed > 0.0 ? sp.dt_fixed : cfl * (vol / fmax(sr, 0.0));
+  b.turb3[0][q] = mut_cell;
+}
+__global__ void __launch_bounds__(256)
+k_visc_residual_les(BlockDev b, GasDev g, SolverDev sp, double cfl, int fourth) {
+  const int i = blockIdx.x * blockDim.x + threadIdx.x;
+  const int j = blockIdx.y * blockDim.y + threadIdx.y;
+  const int k = blockIdx.z;
+  if (i >= b.ni || j >= b.nj) return;
+  visc_residual_cell_les(b, g, sp, cfl, fourth, b.idx(i, j, k));
+}
+#endif
 
 #if AGX_NEQ == 7
 // ---------------------------------------------------------------------------
@@ -3529,6 +3606,12 @@ __device__ __forceinline__ double out_value(int var, const OutPoint& pt, const O
     case AGX_OUT_GLOBAL_POSITION: return (double)sp.global_pos;
     case AGX_OUT_VISCOSITY: return pt.mu * muR;
     case AGX_OUT_WALL_DISTANCE: return src.plane(b.wdist, true) * lR;
+#if AGX_NEQ == 5
+    // largeEddySimulation: eddyViscosity_ of the last residual (zero before the first, and
+    // in every other run: no plane), output.cpp:284-291
+    case AGX_OUT_VISCOSITY_RATIO: return src.turb(0) / pt.mu;
+    case AGX_OUT_TURB_VISCOSITY: return src.turb(0) * muR;
+#endif
 #if AGX_NEQ == 7
     case AGX_OUT_VISCOSITY_RATIO: return src.turb(0) / pt.mu;
     case AGX_OUT_TURB_VISCOSITY: return src.turb(0) * muR;
@@ -3558,6 +3641,8 @@ struct CellSource {
   __device__ double grad(int gidx) const { return grow[gidx]; }
 #if AGX_NEQ == 7
   __device__ double turb(int n) const { return b.turb3[n][q]; }
+#else
+  __device__ double turb(int n) const { return b.turb3[n] ? b.turb3[n][q] : 0.0; }
 #endif
 };
 // One thread per physical cell, variable by variable into out[v * ncell + cell] (each store of
@@ -3628,7 +3713,14 @@ __device__ __forceinline__ void wall_face_vars(const BlockDev& b, const GasDev& 
 #else
     double flux[AGX_NEQ];
     ViscWallOut wo;
-    visc_face<true>(b, g, d, qU, flux, fourth != 0, &wo);
+    // (fourth: bit 0 centralFourth, bit 1 a largeEddySimulation run -- the WALE eddy
+    // viscosity at the low-Re wall face, procBlock.cpp:1357-1376)
+    if (fourth & 2) {
+      visc_face<true, true>(b, g, d, qU, flux, (fourth & 1) != 0, &wo);
+      mut = wo.mut;
+    } else {
+      visc_face<true>(b, g, d, qU, flux, fourth != 0, &wo);
+    }
     for (int e = 0; e < AGX_NEQ; ++e) sf[e] = wo.sf[e];
     for (int c = 0; c < 3; ++c) tau[c] = wo.tau[c];
     muf = wo.muf; qn = wo.qn;
@@ -3924,10 +4016,9 @@ struct NodeSource {
     return a * (nb == 3 ? (ghosts ? 0.25 : 1.0) : nb == 2 ? (ghosts ? 1.0 / 6.0 : 0.5) : 0.125);
   }
   __device__ double grad(int gidx) const { return grow[gidx]; }
-#if AGX_NEQ == 7
   // viscosityRatio, turbulentViscosity, f1, f2 are refused at nodes by agx_output_pack
+  // (rans, and largeEddySimulation; any other run has none and hands out zero)
   __device__ double turb(int) const { return 0.0; }
-#endif
 };
 __global__ void __launch_bounds__(256)
 k_node_pack(BlockDev b, GasDev g, OutSpec sp, const double* __restrict__ grads,

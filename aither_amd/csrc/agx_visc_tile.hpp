@@ -92,7 +92,13 @@ __device__ __forceinline__ void vt_edge(VShared sh, double (*grad)[4], const dou
 struct VtNoWide {
   __device__ __forceinline__ void operator()(double*, double*, double&, double&) const {}
 };
-template <bool F4, class Wide>
+// LES (largeEddySimulation, instantiations of their own; the others are the code they were):
+// the WALE eddy viscosity of the face from the gradient in hand (wale_eddy_visc, agx_device.hpp)
+// joins mu before lambda and tau and, as mut cp / Prt, the conductivity; it is handed out
+// unscaled in f[4].  The VS_MU slots carry the j-faces' mut to the row below in these
+// instantiations (see k_visc_tile), so a neighbour's viscosity is formed from its temperature
+// here -- the expression that filled the slot, the same bits.
+template <bool F4, bool LES, class Wide>
 __device__ __forceinline__ void vt_face(VShared sh, const GasDev& g, const VRef& rL,
                                         const VRef& rU, const VRef& rhoL, const VRef& rhoU,
                                         double rhoU_reg, double muU_reg, bool u_in_reg,
@@ -134,15 +140,25 @@ __device__ __forceinline__ void vt_face(VShared sh, const GasDev& g, const VRef&
 #pragma unroll
     for (int c = 0; c < 4; ++c) grad[r][c] *= inv_vol;
   const double rL_ = sh[rhoL.row][rhoL.lane][rhoL.var];
-  const double mL_ = sh[rhoL.row][rhoL.lane][rhoL.var + 1];          // VS_MU = VS_RHO + 1
   const double rU_ = u_in_reg ? rhoU_reg : sh[rhoU.row][rhoU.lane][rhoU.var];
-  const double mU_ = u_in_reg ? muU_reg : sh[rhoU.row][rhoU.lane][rhoU.var + 1];
+  double mL_, mU_;
+  if constexpr (LES) {
+    mL_ = rL_ > 0.0 ? viscosity(g, vL[3]) : 0.0;
+    mU_ = u_in_reg ? muU_reg : (rU_ > 0.0 ? viscosity(g, vU[3]) : 0.0);
+  } else {
+    mL_ = sh[rhoL.row][rhoL.lane][rhoL.var + 1];          // VS_MU = VS_RHO + 1
+    mU_ = u_in_reg ? muU_reg : sh[rhoU.row][rhoU.lane][rhoU.var + 1];
+  }
   double vf[3], tf, mu;
   if constexpr (F4) {
     // Newton form on the divided differences of the four cell values (visc_face_state,
     // agx_kernels.hpp); the reference reconstructs (rho, u, v, w, p) and mu
     double c0[6], c3[6], w0 = 1.0, w3 = 1.0;
     wide(c0, c3, w0, w3);
+    if constexpr (LES) {
+      c0[5] = c0[4] > 0.0 ? viscosity(g, c0[3]) : 0.0;
+      c3[5] = c3[4] > 0.0 ? viscosity(g, c3[3]) : 0.0;
+    }
     const double w1 = wL, w2 = wU;
     const double r01 = fast_rcp(w0 + w1), r12 = fast_rcp(w1 + w2), r23 = fast_rcp(w2 + w3);
     const double t012 = fast_rcp(w0 + w1 + w2), t123 = fast_rcp(w1 + w2 + w3);
@@ -172,6 +188,11 @@ __device__ __forceinline__ void vt_face(VShared sh, const GasDev& g, const VRef&
     tf = (cD * rU_ * vU[3] + cU * rL_ * vL[3]) * fast_rcp(rf);
     mu = g.scaling * (cD * mU_ + cU * mL_);
   }
+  if constexpr (LES) {
+    // EddyViscAndBlending procBlock.cpp:1357-1365: length = half the two cells' widths
+    f[4] = wale_eddy_visc(grad, 0.5 * (wL + wU));
+    mu += g.scaling * f[4];
+  }
   const double lambda = -(2.0 / 3.0) * mu;
   const double trace = grad[0][0] + grad[1][1] + grad[2][2];
   // tau . A  (viscousFlux.cpp:58-135 with the area vector instead of n |A|)
@@ -182,7 +203,9 @@ __device__ __forceinline__ void vt_face(VShared sh, const GasDev& g, const VRef&
                       (grad[r][2] + grad[2][r]) * aF[2];
     tau[r] = lambda * trace * aF[r] + mu * mm;
   }
-  const double kk = conductivity(g, tf) * g.scaling;
+  double kk = conductivity(g, tf) * g.scaling;
+  // TurbConductivity: mut cp / Prt (viscousFlux.cpp:112-113; calorically perfect here)
+  if constexpr (LES) kk += g.scaling * f[4] * g.cp / g.turb_prandtl;
   const double tg = grad[0][3] * aF[0] + grad[1][3] * aF[1] + grad[2][3] * aF[2];
   f[0] = tau[0];
   f[1] = tau[1];
@@ -202,10 +225,25 @@ __device__ __forceinline__ void vt_face(VShared sh, const GasDev& g, const VRef&
 // -- one wave each -- fetch the cell beyond the window (row -1 / row 8) into registers with the
 // plane they prefetch; along k the own column's plane kk+2 is requested one step earlier and
 // rho, mu and the k-width of plane kk-1 stay in registers.
-template <bool F4>
+//
+// LES (largeEddySimulation): every face hands out its WALE eddy viscosity beside the four flux
+// components (f[4]).  The cell update takes the mut of the cell's LOWER i-, j- and k-face into
+// the spectral radius (the faces at which CalcViscFluxI/J/K call ViscCellSpectralRadius for the
+// cell, procBlock.cpp:1427-1455: its own fi, fj and the rotating fk_lo) and one sixth of all six
+// into the eddy-viscosity plane (eddyViscosity_, :1401-1402, :1436-1437; unscaled).  The upper
+// i-face's comes by the shuffle that carries fi, the upper k-face's is the thread's own, the
+// upper j-face's is another wave's: it travels through that thread's VS_MU slot, written beside
+// VS_FJ after the j-face and read after the barrier that ends the faces.  The slot is free in
+// these instantiations because nobody reads a viscosity from LDS in them: vt_face forms a
+// neighbour's from its temperature (some ten flops per operand, no barrier, no LDS growth:
+// the window stays 8 x 64 x 39 doubles), and the own column's rotates in a register (MU0r).
+// Overhang threads and the `pre` pass contribute nothing: their fi / fj stay zero, and the
+// `pre` pass forms exactly the lower k-face a re-primed segment needs, mut included.
+template <bool F4, bool LES = false>
 __global__ void __launch_bounds__(VT_L * VT_R)
 k_visc_tile(SlabDev b, GasDev g, SolverDev sp, double cfl, int gx, TilePlan tp) {
   __shared__ double sh[VT_R][VT_L][VS_COUNT];
+  constexpr int NF = LES ? 5 : 4;                       // flux components (+ mut) per face
   constexpr int LO = F4 ? 2 : 1;                        // first owning lane
   constexpr int OI = F4 ? VT_L - 4 : VT_OI;             // owned cells along i
   const int l = threadIdx.x, ty = threadIdx.y;
@@ -285,6 +323,15 @@ k_visc_tile(SlabDev b, GasDev g, SolverDev sp, double cfl, int gx, TilePlan tp) 
   // beyond the window's rows (u, v, w, T, rho, mu, j-width; rows 1 and 7)
   double S2[4] = {0, 0, 0, 0}, R2 = 0, MU2 = 0, WK2 = 0, RM = 0, MUM = 0, WKM = 0;
   double EJ[7] = {0, 0, 0, 0, 0, 0, 0};
+  double MU0r = 0;      // LES only: viscosity of plane kk of the own column (VS_MU carries mut)
+  // who fetches the area vector of the face at i+1 / j+1 from memory (VT_LDSAREA).  LES: also
+  // the thread of the block's last i- / j-face: without centralFourth the lane / row after it is
+  // clamped onto its own column, whose slot holds the face at ni / nj again -- the face at
+  // ni + 1 / nj + 1 only where the ghost geometry repeats the boundary cell's, not across a
+  // block connection on a stretched grid.  (The other instantiations are the code they were
+  // and take the clamped slot there.)
+  const bool mem_i = !VT_LDSAREA || l == VT_L - 1 || (LES && !F4 && ci == b.ni);
+  const bool mem_j = !VT_LDSAREA || ty == VT_R - 1 || (LES && !F4 && cj == b.nj);
   const bool ej_row = F4 && (ty == 1 || ty == VT_R - 1);
   // (row 1: j-2, row 7: j+1 -- wanted only where the row's own face is, cj <= nj)
   const unsigned qej = (unsigned)(b.idx(ic, ty == 1 ? jc - 2 : min(jc + 1, b.nj + 1), 0) * 8);
@@ -294,7 +341,9 @@ k_visc_tile(SlabDev b, GasDev g, SolverDev sp, double cfl, int gx, TilePlan tp) 
     ld_state(kk, t4, r, m);
     PUT4(VS_S0, t4);
     if (!F4) PUT4(VS_SM, t4);
-    sh[ty][l][VS_RHO] = r; sh[ty][l][VS_MU] = m;
+    sh[ty][l][VS_RHO] = r;
+    if constexpr (LES) { MU0r = m; sh[ty][l][VS_MU] = 0.0; }
+    else sh[ty][l][VS_MU] = m;
     ld_state(kk + 1, t4, R1, MU1);
     PUT4(VS_SP, t4);
     if (F4) {
@@ -311,13 +360,13 @@ k_visc_tile(SlabDev b, GasDev g, SolverDev sp, double cfl, int gx, TilePlan tp) 
     ld_avec(2, qk, t3); PUT3(VS_AK0, t3);
     ld_avec(2, qk + sk, t3); PUT3(VS_AK1, t3);
     ld_avec(2, qc + (unsigned)min(kk + 2, kfmax) * sk, AK2);
-    if (!VT_LDSAREA || l == VT_L - 1) ld_avec(0, qk + 8, AIp);
-    if (!VT_LDSAREA || ty == VT_R - 1) ld_avec(1, qk + sj, AJp);
+    if (mem_i) ld_avec(0, qk + 8, AIp);
+    if (mem_j) ld_avec(1, qk + sj, AJp);
     sh[ty][l][VS_VOL] = b.ldb(PL_VOL, qk); V1 = b.ldb(PL_VOL, qk + sk);
     WK0 = b.ldb(PL_WID + 2, qk); WK1 = b.ldb(PL_WID + 2, qk + sk);
     sh[ty][l][VS_WI] = b.ldb(PL_WID + 0, qk); sh[ty][l][VS_WJ] = b.ldb(PL_WID + 1, qk);
   }
-  double fk_lo[4] = {0, 0, 0, 0};
+  double fk_lo[NF] = {0, 0, 0, 0};
   const int tu = min(ty + 1, VT_R - 1), td = max(ty - 1, 0);
   const int lr = min(l + 1, VT_L - 1), ll = max(l - 1, 0);
   for (; kk < k1; ++kk) {
@@ -325,14 +374,14 @@ k_visc_tile(SlabDev b, GasDev g, SolverDev sp, double cfl, int gx, TilePlan tp) 
     __syncthreads();                           // the windows of all columns are in place
     // neighbours are read where they are used (i: lanes l -+ 1 of the own row, j:
     // rows ty -+ 1); clamped indices only ever serve threads whose face is not needed
-    double fi[4] = {0, 0, 0, 0}, fj[4] = {0, 0, 0, 0}, fk_up[4] = {0, 0, 0, 0};
+    double fi[NF] = {0, 0, 0, 0}, fj[NF] = {0, 0, 0, 0}, fk_up[NF] = {0, 0, 0, 0};
     const VRef me0{VS_S0, ty, l}, meP{VS_SP, ty, l}, meM{VS_SM, ty, l};
     const VRef meR{VS_RHO, ty, l};
     // ---- lower i-face: cells (i-1,j) | (i,j) ----
     if (do_i && !pre) {
       double aF[3], aFm[3];
       vt_ld3(sh, VRef{VS_AI0, ty, l}, aF); vt_ld3(sh, VRef{VS_AI0, ty, ll}, aFm);
-      if (VT_LDSAREA && l < VT_L - 1) vt_ld3(sh, VRef{VS_AI0, ty, lr}, AIp);
+      if (!mem_i) vt_ld3(sh, VRef{VS_AI0, ty, lr}, AIp);
       const VtEdge ju{{VS_S0, tu, l}, {VS_S0, tu, ll}, {VS_AJ0, tu, l}, {VS_AJ0, tu, ll}};
       const VtEdge jl{{VS_S0, td, l}, {VS_S0, td, ll}, {VS_AJ0, ty, l}, {VS_AJ0, ty, ll}};
       const VtEdge ku{meP, {VS_SP, ty, ll}, {VS_AK1, ty, l}, {VS_AK1, ty, ll}};
@@ -343,7 +392,7 @@ k_visc_tile(SlabDev b, GasDev g, SolverDev sp, double cfl, int gx, TilePlan tp) 
         c0[4] = sh[ty][l0][VS_RHO]; c0[5] = sh[ty][l0][VS_MU]; w0 = sh[ty][l0][VS_WI];
         c3[4] = sh[ty][lr][VS_RHO]; c3[5] = sh[ty][lr][VS_MU]; w3 = sh[ty][lr][VS_WI];
       };
-      vt_face<F4>(sh, g, VRef{VS_S0, ty, ll}, me0, VRef{VS_RHO, ty, ll}, meR, 0.0, 0.0, false,
+      vt_face<F4, LES>(sh, g, VRef{VS_S0, ty, ll}, me0, VRef{VS_RHO, ty, ll}, meR, 0.0, 0.0, false,
                   nullptr, aF, aFm, AIp, ju, jl, ku, kl, sh[ty][ll][VS_VOL], sh[ty][l][VS_VOL],
                   sh[ty][ll][VS_WI], sh[ty][l][VS_WI], fi, wide);
     }
@@ -352,12 +401,14 @@ k_visc_tile(SlabDev b, GasDev g, SolverDev sp, double cfl, int gx, TilePlan tp) 
     double racc[4];
 #pragma unroll
     for (int c = 0; c < 4; ++c) racc[c] = fi[c] - __shfl_down(fi[c], 1, 64);
+    double mut_iup = 0.0;
+    if constexpr (LES) mut_iup = __shfl_down(fi[4], 1, 64);
     __builtin_amdgcn_sched_barrier(0);
     // ---- lower j-face: cells (i,j-1) | (i,j) ----
     if (do_j && !pre) {
       double aF[3], aFm[3];
       vt_ld3(sh, VRef{VS_AJ0, ty, l}, aF); vt_ld3(sh, VRef{VS_AJ0, td, l}, aFm);
-      if (VT_LDSAREA && ty < VT_R - 1) vt_ld3(sh, VRef{VS_AJ0, tu, l}, AJp);
+      if (!mem_j) vt_ld3(sh, VRef{VS_AJ0, tu, l}, AJp);
       const VtEdge iu{{VS_S0, ty, lr}, {VS_S0, td, lr}, {VS_AI0, ty, lr}, {VS_AI0, td, lr}};
       const VtEdge il{{VS_S0, ty, ll}, {VS_S0, td, ll}, {VS_AI0, ty, l}, {VS_AI0, td, l}};
       const VtEdge ku{meP, {VS_SP, td, l}, {VS_AK1, ty, l}, {VS_AK1, td, l}};
@@ -381,15 +432,19 @@ k_visc_tile(SlabDev b, GasDev g, SolverDev sp, double cfl, int gx, TilePlan tp) 
           c3[4] = sh[tu][l][VS_RHO]; c3[5] = sh[tu][l][VS_MU]; w3 = sh[tu][l][VS_WJ];
         }
       };
-      vt_face<F4>(sh, g, VRef{VS_S0, td, l}, me0, VRef{VS_RHO, td, l}, meR, 0.0, 0.0, false,
+      vt_face<F4, LES>(sh, g, VRef{VS_S0, td, l}, me0, VRef{VS_RHO, td, l}, meR, 0.0, 0.0, false,
                   nullptr, aF, aFm, AJp, iu, il, ku, kl, sh[td][l][VS_VOL], sh[ty][l][VS_VOL],
                   sh[td][l][VS_WJ], sh[ty][l][VS_WJ], fj, wide);
     }
 #pragma unroll
     for (int c = 0; c < 4; ++c) { sh[ty][l][VS_FJ + c] = fj[c]; racc[c] += fj[c]; }
+    if constexpr (LES) sh[ty][l][VS_MU] = fj[4];
     __builtin_amdgcn_sched_barrier(0);
     // ---- upper k-face: cells (i,j,k) | (i,j,k+1) ----
-    const double R0 = sh[ty][l][VS_RHO], MU0 = sh[ty][l][VS_MU], V0 = sh[ty][l][VS_VOL];
+    const double R0 = sh[ty][l][VS_RHO], V0 = sh[ty][l][VS_VOL];
+    double MU0;
+    if constexpr (LES) MU0 = MU0r;
+    else MU0 = sh[ty][l][VS_MU];
     if (own) {
       double aF[3], aFm[3], SPr[4];
       vt_ld3(sh, VRef{VS_AK1, ty, l}, aF); vt_ld3(sh, VRef{VS_AK0, ty, l}, aFm);
@@ -405,7 +460,7 @@ k_visc_tile(SlabDev b, GasDev g, SolverDev sp, double cfl, int gx, TilePlan tp) 
         for (int c = 0; c < 4; ++c) c3[c] = S2[c];
         c3[4] = R2; c3[5] = MU2; w3 = WK2;
       };
-      vt_face<F4>(sh, g, me0, meP, meR, meR, R1, MU1, true, SPr, aF, aFm, AK2, iu, il, ju, jl, V0,
+      vt_face<F4, LES>(sh, g, me0, meP, meR, meR, R1, MU1, true, SPr, aF, aFm, AK2, iu, il, ju, jl, V0,
                   V1, WK0, WK1, fk_up, wide);
     }
     __builtin_amdgcn_sched_barrier(0);
@@ -422,8 +477,8 @@ k_visc_tile(SlabDev b, GasDev g, SolverDev sp, double cfl, int gx, TilePlan tp) 
     rq_avec(0, qn2, rAI);
     rq_avec(1, qn2, rAJ);
     rq_avec(2, qc + (unsigned)min(kk + 3, kfmax) * sk, rAK);
-    if (!VT_LDSAREA || l == VT_L - 1) rq_avec(0, qn + 8, rAIp);
-    if (!VT_LDSAREA || ty == VT_R - 1) rq_avec(1, qn + sj, rAJp);
+    if (mem_i) rq_avec(0, qn + 8, rAIp);
+    if (mem_j) rq_avec(1, qn + sj, rAJp);
     const double nV = b.ldb(PL_VOL, qn2);
     const double nWK = b.ldb(PL_WID + 2, F4 ? qc + (unsigned)min(kk + 3, kcmax) * sk : qn2);
     double nEJ[6] = {0, 0, 0, 0, 0, 0}, nEw = 0;
@@ -456,11 +511,31 @@ k_visc_tile(SlabDev b, GasDev g, SolverDev sp, double cfl, int gx, TilePlan tp) 
       const double fm[3] = {0.5 * (fast_sqrt(dot3(ai0, ai0)) + fast_sqrt(dot3(AIp, AIp))),
                             0.5 * (fast_sqrt(dot3(aj0, aj0)) + fast_sqrt(dot3(AJp, AJp))),
                             0.5 * (fast_sqrt(dot3(ak0, ak0)) + fast_sqrt(dot3(ak1, ak1)))};
+      if constexpr (LES) {
+        const double mut_lo[3] = {fi[4], fj[4], fk_lo[4]};
+        const double vmax = visc_max_term(g, R0);
+#pragma unroll
+        for (int d = 0; d < 3; ++d) {
+          const double vterm = g.scaling * (MU0 * g.inv_prandtl + mut_lo[d] / g.turb_prandtl);
+          const double vsr = vmax * vterm * fm[d] * fm[d] * ivol;
+          sr += vsr * sp.visc_cfl_coeff;
+          diag += 2.0 * vsr;
+        }
+        const double sixth = 1.0 / 6.0;
+        double ev = sixth * fi[4];
+        ev += sixth * mut_iup;
+        ev += sixth * fj[4];
+        ev += sixth * sh[ty + 1][l][VS_MU];
+        ev += sixth * fk_lo[4];
+        ev += sixth * fk_up[4];
+        b.stb(PL_EDDY_LES, q, ev);
+      } else {
 #pragma unroll
       for (int d = 0; d < 3; ++d) {
         const double vsr = vfac * fm[d] * fm[d] * ivol;
         sr += vsr * sp.visc_cfl_coeff;
         diag += 2.0 * vsr;
+      }
       }
 #pragma unroll
       for (int e = 1; e < AGX_NEQ; ++e) b.stb(PL_RESID + e, q, res[e]);   // mass: no viscous flux
@@ -479,9 +554,12 @@ k_visc_tile(SlabDev b, GasDev g, SolverDev sp, double cfl, int gx, TilePlan tp) 
       LD4(VS_SP, ty, l, t4); PUT4(VS_S0, t4);
       if (F4) {
         PUT4(VS_SP, S2);
-        RM = sh[ty][l][VS_RHO]; MUM = sh[ty][l][VS_MU];
+        RM = sh[ty][l][VS_RHO];
         sh[ty][l][VS_RHO] = R1; R1 = R2; R2 = nR;
-        sh[ty][l][VS_MU] = MU1; MU1 = MU2; MU2 = nMU;
+        // (LES: the slot holds this step's mut for the row below, which may still be reading)
+        if constexpr (LES) { MUM = MU0r; MU0r = MU1; }
+        else { MUM = sh[ty][l][VS_MU]; sh[ty][l][VS_MU] = MU1; }
+        MU1 = MU2; MU2 = nMU;
 #pragma unroll
         for (int c = 0; c < 4; ++c) S2[c] = nS[c];
         if (ej_row) {
@@ -495,7 +573,9 @@ k_visc_tile(SlabDev b, GasDev g, SolverDev sp, double cfl, int gx, TilePlan tp) 
       } else {
         PUT4(VS_SP, nS);
         sh[ty][l][VS_RHO] = R1; R1 = nR;
-        sh[ty][l][VS_MU] = MU1; MU1 = nMU;
+        if constexpr (LES) MU0r = MU1;
+        else sh[ty][l][VS_MU] = MU1;
+        MU1 = nMU;
       }
       LD3(VS_AI1, ty, l, t3); PUT3(VS_AI0, t3); PUT3(VS_AI1, nAI);
       LD3(VS_AJ1, ty, l, t3); PUT3(VS_AJ0, t3); PUT3(VS_AJ1, nAJ);
@@ -505,7 +585,7 @@ k_visc_tile(SlabDev b, GasDev g, SolverDev sp, double cfl, int gx, TilePlan tp) 
       if (F4) { WKM = WK0; WK0 = WK1; WK1 = WK2; WK2 = nWK; }
       else { WK0 = WK1; WK1 = nWK; }
 #pragma unroll
-      for (int c = 0; c < 4; ++c) fk_lo[c] = fk_up[c];
+      for (int c = 0; c < NF; ++c) fk_lo[c] = fk_up[c];
 #pragma unroll
       for (int c = 0; c < 3; ++c) { AK2[c] = nAK[c]; AIp[c] = nAIp[c]; AJp[c] = nAJp[c]; }
     }

@@ -52,14 +52,25 @@ enum { AGX_TIME_EXPLICIT_EULER = 0, AGX_TIME_RK4 = 1,
 enum { AGX_SOLVER_LUSGS = 0, AGX_SOLVER_DPLUR = 1,
        AGX_SOLVER_BLUSGS = 2, AGX_SOLVER_BDPLUR = 3 }; /* input.cpp:843-858 */
 enum { AGX_EQN_EULER = 0, AGX_EQN_NAVIER_STOKES = 1,
-       AGX_EQN_RANS = 2 };                    /* input::equationSet_, input.cpp:1033-1060 */
+       AGX_EQN_RANS = 2,
+       AGX_EQN_LES = 3 /* largeEddySimulation (input.cpp:653-663, :694-709, :751): five
+                          equations, IsTurbulent() true, IsRANS() false; turbulence_model wale
+                          and nothing else (:965-979).  The 5-equation libraries, explicit time
+                          integration (implicit LES is refused by name) */
+     };                                       /* input::equationSet_, input.cpp:1033-1060 */
 enum { AGX_JACOBIAN_RUSANOV = 0,
        AGX_JACOBIAN_APPROX_ROE = 1 };         /* input::InvFluxJac, fluxJacobian.cpp:196-238 */
 enum { AGX_VISC_RECON_CENTRAL = 0,
        AGX_VISC_RECON_CENTRAL_4TH = 1 };      /* reconstruction.hpp:315-379 */
 enum { AGX_TURB_NONE = 0, AGX_TURB_SST2003 = 1, AGX_TURB_KW_WILCOX2006 = 2,
        AGX_TURB_SST_DES = 3,
-       AGX_TURB_WALE = 4 /* named for completeness: agx_config_set REFUSES it (not built) */
+       AGX_TURB_WALE = 4 /* with AGX_EQN_LES only (input.cpp:965-979).  turbWale::EddyVisc
+                            turbulence.cpp:967-996, Cw = 0.544, evaluated at every face that is
+                            not a wall-law face (EddyViscAndBlending turbulence.hpp:685-695,
+                            procBlock.cpp:1357-1365); enters tau and the conductivity
+                            (viscousFlux.cpp:58-211, Prt = 0.9 turbulence.hpp:70), y+ at low-Re
+                            walls (procBlock.cpp:1372-1376), the viscous spectral radius
+                            (spectralRadius.hpp:94-123) and eddyViscosity_ (:1401-1402) */
      };                                       /* turbulence.hpp */
 
 /* boundary condition types, ghostStates.cpp:62-689 */
