@@ -77,6 +77,15 @@ struct Block {
   // D2 path: agx_phase_implicit_begin left x_ = 0 unwritten (the first half sweep does not read
   // it); until that sweep has run a download of x returns the zeros the reference holds
   bool x_is_zero = false;
+  // D2 path: PA_S and vf() of the physical cells hold the state planes' values (k_update_d2
+  // wrote both last), so the next prepare takes its lean form.  Only the D2 branch of
+  // update_pass sets it; whatever else may write the state planes of physical cells clears it
+  // (state_written, upload_aos).  A cleared flag costs a full prepare, never a result.
+  bool d2_state_current = false;
+  // D2 path: k_lusgs_prepare folded the norms of the residual planes as they are now into
+  // its slot of norm_out, so the update neither reads the residual nor folds.  Prepare sets
+  // it; agx_phase_residual and uploads clear it (resid_written, upload_aos).
+  bool resid_norms_current = false;
   // multigrid: forcing | matrix residual | saved update planes (each allocated on first
   // use); the transfer maps of this block as the FINE side (device copies, keyed by the
   // host pointers they were uploaded from); node values of this block as the coarse side
@@ -244,6 +253,12 @@ struct agx_ctx {
   std::map<std::array<int, 6>, TilePlan> tile_plans;   // (made once per shape)
   int mresid_split = 1;      // bands of diagonals per XCD in k_matrix_resid_d2 (AGX_MRESID_SPLIT)
   bool mresid_march = true;  // AGX_MRESID=plane: one plane position per thread (comparison form)
+  // AGX_D2_STATE=update (default): k_update_d2 writes the D2 state of the next iteration and
+  // prepare skips the physical cells | prepare: prepare re-lays the state every iteration
+  bool d2_state_update = true;
+  // AGX_RESID_NORMS=prepare (default): k_lusgs_prepare folds the residual norms and the
+  // update does not read the residual | update: k_update_d2 reads it for the norms
+  bool resid_norms_prepare = true;
   bool have_time_n = false;  // agx_store_time_n has run (nonreflecting BCs read consVarsN)
   bool have_wall_data = false;   // a residual's viscous ghost fill has stored the wall-law data
   // agx_iterate fills the ghost cells for the NEXT call right after the update,
@@ -374,6 +389,10 @@ int upload_aos(agx_ctx* c, Block& b, const double* host, double* const* dst,
                int ncomp, int ci, int cj, int ck, int gsrc) {
   const long n = (long)ci * cj * ck;
   double* tmp = nullptr;
+  // (whichever planes of the block this writes: its D2 state and its folded norms are taken
+  // for stale)
+  b.d2_state_current = false;
+  b.resid_norms_current = false;
   if (stage_buffer(c, (size_t)n * ncomp, &tmp)) return 1;
   HIPCHK(hipMemcpyAsync(tmp, host, sizeof(double) * n * ncomp,
                         hipMemcpyHostToDevice, c->stream));
@@ -476,6 +495,15 @@ int halo_in_d2(const Block& b, int what) { return what == AGX_HALO_UPDATE && b.d
 // something is about to write x where it lives (the D2 arrays on the diagonal-ordered path)
 void x_changed(agx_ctx* c) {
   for (auto& blk : c->blocks) blk.x_planes_current = false;
+}
+// something other than k_update_d2 is about to write the state planes of physical cells /
+// something is about to write the residual planes (Block::d2_state_current,
+// Block::resid_norms_current)
+void state_written(agx_ctx* c) {
+  for (auto& blk : c->blocks) blk.d2_state_current = false;
+}
+void resid_written(agx_ctx* c) {
+  for (auto& blk : c->blocks) blk.resid_norms_current = false;
 }
 Planes5 halo_planes(Block& b, int what) {
   Planes5 r;
@@ -1104,10 +1132,14 @@ int fill_ghosts(agx_ctx* c) {
 int update_pass(agx_ctx* c, int mode, int mm, double* l2, agx_linf* linf) {
   c->state_is_time_n = false;
   const double alpha[4] = {0.25, 1.0 / 3.0, 0.5, 1.0};   // procBlock.cpp:938
+  const size_t nb = c->blocks.size();
+  // blocks whose norms sit in prepare's slots of norm_out, [2 nb + 64, 3 nb + 64)
+  std::vector<size_t> from_prepare;
   if (mode != 2 && c->fused_pending) {
     // the marching kernel already advanced the state into the second buffer
     // and left one norm partial per workgroup: fold them and swap buffers
     Timer t(c, G_UPDATE);
+    state_written(c);
     long off = 0;
     for (size_t n = 0; n < c->blocks.size(); ++n) {
       BlockDev& b = c->blocks[n].d;
@@ -1123,17 +1155,35 @@ int update_pass(agx_ctx* c, int mode, int mm, double* l2, agx_linf* linf) {
   } else {
     Timer t(c, G_UPDATE);
     for (size_t n = 0; n < c->blocks.size(); ++n) {
-      const BlockDev& b = c->blocks[n].d;
+      Block& blk = c->blocks[n];
+      const BlockDev& b = blk.d;
       const int last = mm == c->cfg.nonlinear_iterations - 1;
 #if AGX_FAST
       if (mode == 2 && b.d2.base) {
         const dim3 tg((b.ni + TT - 1) / TT, (b.nj + TT - 1) / TT, b.nk);
-        hipLaunchKernelGGL(k_update_d2, tg, dim3(256), 0, c->stream, b, c->gas, c->sp, last,
-                           c->partials.get());
-        if (reduce_norms(c, n, (long)tg.x * tg.y * tg.z)) return 1;
+        // the D2 state of the next prepare from here (AGX_D2_STATE); the norms from
+        // k_lusgs_prepare where it folded those of this residual (AGX_RESID_NORMS)
+        const bool ws = c->d2_state_update, pn = blk.resid_norms_current;
+#define AGX_UPD_D2(W, N)                                                                  \
+  hipLaunchKernelGGL((k_update_d2<W, N>), tg, dim3(256), 0, c->stream, b, c->gas, c->sp, \
+                     last, c->partials.get())
+        if (ws && pn) AGX_UPD_D2(1, 0);
+        else if (ws) AGX_UPD_D2(1, 1);
+        else if (pn) AGX_UPD_D2(0, 0);
+        else AGX_UPD_D2(0, 1);
+#undef AGX_UPD_D2
+        blk.d2_state_current = ws;
+        if (pn) {
+          // (one use: a second update on the same residual reads it itself)
+          blk.resid_norms_current = false;
+          from_prepare.push_back(n);
+        } else if (reduce_norms(c, n, (long)tg.x * tg.y * tg.z)) {
+          return 1;
+        }
         continue;
       }
 #endif
+      blk.d2_state_current = false;
       const dim3 grid = cell_grid(b, CELL_BLOCK);
       hipLaunchKernelGGL(k_update, grid, CELL_BLOCK, 0, c->stream, b, c->gas,
                          c->sp, mode, mode == 1 ? alpha[mm & 3] : 1.0, last,
@@ -1141,7 +1191,15 @@ int update_pass(agx_ctx* c, int mode, int mm, double* l2, agx_linf* linf) {
       if (reduce_norms(c, n, (long)grid.x * grid.y * grid.z)) return 1;
     }
   }
-  HIPCHK(hipMemcpyAsync(c->norm_host.get(), c->norm_out.get(),
+  // the same layout either way: every block's norms from prepare's slots, or from the
+  // update's (a mix -- an upload into one block between the two -- is gathered there first)
+  const NormPartial* norm_src = c->norm_out.get();
+  if (from_prepare.size() == nb && nb > 0) norm_src += 2 * nb + 64;
+  else
+    for (size_t n : from_prepare)
+      HIPCHK(hipMemcpyAsync(c->norm_out.get() + n, c->norm_out.get() + 2 * nb + 64 + n,
+                            sizeof(NormPartial), hipMemcpyDeviceToDevice, c->stream));
+  HIPCHK(hipMemcpyAsync(c->norm_host.get(), norm_src,
                         sizeof(NormPartial) * c->blocks.size(),
                         hipMemcpyDeviceToHost, c->stream));
   if (c->mres_deferred)
@@ -1594,6 +1652,20 @@ int agx_ctx_create(int device, int rank, agx_ctx** out) {
     if (const char* w = getenv("AGX_SWEEP_RECORDS")) c->sweep_records = atoi(w) != 0;
     if (const char* w = getenv("AGX_MRESID_SPLIT")) c->mresid_split = std::min(64, std::max(1, atoi(w)));
     if (const char* w = getenv("AGX_MRESID")) c->mresid_march = strcmp(w, "plane") != 0;
+    if (const char* w = getenv("AGX_D2_STATE")) {
+      if (strcmp(w, "update") && strcmp(w, "prepare")) {
+        delete c;
+        return fail("AGX_D2_STATE is '%s': update or prepare", w);
+      }
+      c->d2_state_update = !strcmp(w, "update");
+    }
+    if (const char* w = getenv("AGX_RESID_NORMS")) {
+      if (strcmp(w, "prepare") && strcmp(w, "update")) {
+        delete c;
+        return fail("AGX_RESID_NORMS is '%s': prepare or update", w);
+      }
+      c->resid_norms_prepare = !strcmp(w, "prepare");
+    }
     if (const char* w = getenv("AGX_HALO_BATCH")) {   // 0: a launch pair per connection; require:
       c->halo_batch = strcmp(w, "0") != 0;            // finalize fails where no batch forms
       c->halo_batch_required = !strcmp(w, "require");
@@ -2212,8 +2284,14 @@ int agx_setup_finalize(agx_ctx* c) {
     const dim3 g = cell_grid(blk.d, CELL_BLOCK);
     max_parts = std::max(max_parts, (long)g.x * g.y * g.z);
     march_parts += march_plan(c, blk.d).nparts;
-    if (blk.d.d2.base)    // k_matrix_resid_d2: one partial per 256 plane positions
+    if (blk.d.d2.base) {  // k_matrix_resid_d2: one partial per 256 plane positions
       max_parts = std::max(max_parts, mresid_wgs(c, blk.d));
+#if AGX_FAST
+      // k_lusgs_prepare: one per tile of the padded box
+      max_parts = std::max(max_parts, (long)((blk.d.d2.Pi + TT - 1) / TT) *
+                                          ((blk.d.d2.Pj + TT - 1) / TT) * (blk.d.nk + 2 * blk.d.ng));
+#endif
+    }
   }
   max_parts = std::max(max_parts, march_parts);
   for (auto& k : c->conns) {
@@ -2276,8 +2354,10 @@ int agx_setup_finalize(agx_ctx* c) {
   HIPCHK(c->partials.alloc((size_t)max_parts));
   const size_t nb = std::max<size_t>(c->blocks.size(), 1);
   // [0, nb): norms of the update; [nb, nb + 64): scratch of the two-level fold;
-  // [nb + 64, 2 nb + 64): the matrix residual (read back with the update's norms)
-  HIPCHK(c->norm_out.alloc(2 * nb + 64));
+  // [nb + 64, 2 nb + 64): the matrix residual (read back with the update's norms);
+  // [2 nb + 64, 3 nb + 64): the residual norms k_lusgs_prepare folds (the matrix residual of
+  // the phase API lands in [0, nb) between prepare and update)
+  HIPCHK(c->norm_out.alloc(3 * nb + 64));
   HIPCHK(c->norm_host.alloc(2 * nb));
   c->finalized = true;
   return 0;
@@ -2701,7 +2781,7 @@ static int implicit_begin(agx_ctx* c, int write_x);
 int agx_phase_matrix_residual(agx_ctx* c, double* mr);
 static int d2_x_copy(agx_ctx* c, Block& b, int to_d2);
 #if AGX_FAST
-static void d2_prepare(agx_ctx* c, Block& blk, int write_x, int again);
+static int d2_prepare(agx_ctx* c, Block& blk, int write_x, int again, int norms);
 #endif
 namespace {
 int mg_solver_ok(agx_ctx* c) {
@@ -2807,6 +2887,9 @@ int agx_mg_restrict(agx_ctx* f, agx_ctx* cz, int blk, int what, const int32_t* t
   if (what < AGX_MG_STATE || what > AGX_MG_FORCING) return fail("mg_restrict: bad selector %d", what);
   if (what != AGX_MG_FORCING && !vf) return fail("mg_restrict: volume weights missing");
   if (flush_consn(f) || flush_consn(cz)) return 1;
+  // (AGX_MG_STATE writes the coarse block's state planes; the other selectors leave them)
+  bc.d2_state_current = false;
+  bc.resid_norms_current = false;
   MgMap m;
   if (mg_maps(f, bf, tc, vf, nullptr, bc.d.ni, bc.d.nj, bc.d.nk, &m)) return 1;
   if (what == AGX_MG_UPDATE && mg_x_to_planes(f, bf)) return 1;
@@ -2837,7 +2920,7 @@ int agx_mg_restrict(agx_ctx* f, agx_ctx* cz, int blk, int what, const int32_t* t
   }
 #if AGX_FAST
   // (b of the diagonal-ordered sweeps: formed again, now with the forcing term)
-  if (what == AGX_MG_FORCING && bc.d.d2.base) d2_prepare(cz, bc, 0, 1);
+  if (what == AGX_MG_FORCING && bc.d.d2.base && d2_prepare(cz, bc, 0, 1, 0)) return 1;
 #endif
   HIPCHK(hipGetLastError());
   return 0;
@@ -2946,6 +3029,8 @@ int agx_phase_residual(agx_ctx* c, int mm, double cfl) {
   c->ghost_fill_open = false;
   c->sp.diag_add = c->mg_coarse ? 1 : 0;
   const bool fuse = can_fuse(c);
+  resid_written(c);
+  if (fuse) state_written(c);      // (the fused stage advances the state as it goes)
   const int store_consn = !c->use_gather && all_tile_ok(c) && c->consn_pending && mm == 0;
   if (store_consn) c->consn_pending = false;
   else if (flush_consn(c)) return 1;
@@ -3091,11 +3176,31 @@ static int implicit_begin(agx_ctx* c, int write_x);
 #if AGX_FAST
 // k_lusgs_prepare of one block (write_x: a launch that writes x is a writer launch: it tags
 // the values and advances the epoch)
-static void d2_prepare(agx_ctx* c, Block& blk, int write_x, int again) {
+// norms: fold the residual norms into the block's prepare slot of norm_out (AGX_RESID_NORMS).
+// The lean form where the update left the block's D2 state current (AGX_D2_STATE); an
+// `again` launch keeps the full one.
+static int d2_prepare(agx_ctx* c, Block& blk, int write_x, int again, int norms) {
   const BlockDev& b = blk.d;
   const dim3 grid((b.d2.Pi + TT - 1) / TT, (b.d2.Pj + TT - 1) / TT, b.nk + 2 * b.ng);
-  hipLaunchKernelGGL(k_lusgs_prepare, grid, dim3(256), 0, c->stream, b, c->gas, c->sp,
-                     write_x, write_x ? (unsigned)(++blk.kp_epoch) & 3u : 0u, again);
+  const bool lean = blk.d2_state_current && !again;
+  int ghost_s = 0;
+  for (int q = 0; q < 6; ++q) ghost_s |= b.side_conn[q] != 0;
+  const unsigned tag = write_x ? (unsigned)(++blk.kp_epoch) & 3u : 0u;
+#define AGX_PREP(L, N)                                                                       \
+  hipLaunchKernelGGL((k_lusgs_prepare<L, N>), grid, dim3(256), 0, c->stream, b, c->gas, c->sp, \
+                     write_x, tag, again, ghost_s, c->partials.get())
+  if (lean && norms) AGX_PREP(1, 1);
+  else if (lean) AGX_PREP(1, 0);
+  else if (norms) AGX_PREP(0, 1);
+  else AGX_PREP(0, 0);
+#undef AGX_PREP
+  if (norms) {
+    const size_t n = (size_t)(&blk - c->blocks.data()), nb = c->blocks.size();
+    if (reduce_norms(c, n, (long)grid.x * grid.y * grid.z, c->norm_out.get() + 2 * nb + 64 + n))
+      return 1;
+    blk.resid_norms_current = true;
+  }
+  return 0;
 }
 #endif
 int agx_phase_implicit_begin(agx_ctx* c) { return implicit_begin(c, 1); }
@@ -3113,7 +3218,9 @@ static int implicit_begin(agx_ctx* c, int write_x) {
       bool conn = false;
       for (int q = 0; q < 6; ++q) conn = conn || b.side_conn[q] != 0;
       const int wx = write_x && (c->sp.requires_init || conn) ? 1 : 0;
-      d2_prepare(c, blk, wx, 0);
+      // (the norms ride along on the finest level's launch only: a coarse multigrid level,
+      // write_x = 0, keeps the update's fold)
+      if (d2_prepare(c, blk, wx, 0, write_x && c->resid_norms_prepare ? 1 : 0)) return 1;
       blk.x_is_zero = write_x && !wx;
       continue;
     }

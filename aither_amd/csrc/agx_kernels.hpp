@@ -2412,10 +2412,11 @@ __global__ void k_halo_scatter(Planes5 a, const long* __restrict__ dst, long n,
 
 // workgroup fold of per-thread partial norms (sum of r^2 per equation, signed
 // max with its first location); thread 0 writes the result
-__device__ __forceinline__ void norm_block_fold(double* v, double vmax, long long lin,
-                                                NormPartial* out) {
-  __shared__ double sh[AGX_NEQ + 1][16];
-  __shared__ long long shl[16];
+// (norm_block_fold_in: in LDS of the caller's, AGX_NEQ + 1 rows of 16 doubles and 16 words,
+// which no thread still reads)
+__device__ __forceinline__ void norm_block_fold_in(double* v, double vmax, long long lin,
+                                                   NormPartial* out, double (*sh)[16],
+                                                   long long* shl) {
   for (int off = 32; off > 0; off >>= 1) {
 #pragma unroll
     for (int e = 0; e < AGX_NEQ; ++e) v[e] += __shfl_down(v[e], off, 64);
@@ -2450,6 +2451,12 @@ __device__ __forceinline__ void norm_block_fold(double* v, double vmax, long lon
       }
     *out = p;
   }
+}
+__device__ __forceinline__ void norm_block_fold(double* v, double vmax, long long lin,
+                                                NormPartial* out) {
+  __shared__ double sh[AGX_NEQ + 1][16];
+  __shared__ long long shl[16];
+  norm_block_fold_in(v, vmax, lin, out, sh, shl);
 }
 __device__ __forceinline__ void norm_block_reduce(const double* r, long lin0,
                                                   bool active,
@@ -2556,10 +2563,10 @@ k_store_time_n(BlockDev b, GasDev g, int also_nm1) {
 // implicit: scalar LU-SGS / DPLUR.
 // b-term of linearSolver.cpp:370-374 with procBlock::SolDeltaMmN / SolDeltaNm1
 // procBlock.cpp:1010-1035
-__device__ __forceinline__ void rhs_b(const BlockDev& b, const GasDev& g,
-                                      const SolverDev& sp, long q, double* out) {
-  double r[AGX_NEQ];
-  load5(b.resid, q, r);
+// (rhs_b_r: with the residual r of the cell in the caller's registers)
+__device__ __forceinline__ void rhs_b_r(const BlockDev& b, const GasDev& g,
+                                        const SolverDev& sp, long q, const double* r,
+                                        double* out) {
   const double thetaInv = 1.0 / sp.theta;
   if (sp.un_is_u && !sp.bdf2) {
 #pragma unroll
@@ -2583,16 +2590,29 @@ __device__ __forceinline__ void rhs_b(const BlockDev& b, const GasDev& g,
     for (int e = 0; e < AGX_NEQ; ++e) out[e] += cM * (un[e] - um[e]);
   }
 }
+__device__ __forceinline__ void rhs_b(const BlockDev& b, const GasDev& g,
+                                      const SolverDev& sp, long q, double* out) {
+  double r[AGX_NEQ];
+  load5(b.resid, q, r);
+  rhs_b_r(b, g, sp, q, r, out);
+}
 
 // b of the LU-SGS sweeps on a multigrid level: the forcing term is part of it
 // (linearSolver.cpp:377, :422; DPLUR adds it beside b, :503, and A x - b has none, :72-75)
-__device__ __forceinline__ void rhs_bf(const BlockDev& b, const GasDev& g,
-                                       const SolverDev& sp, long q, double* out) {
-  rhs_b(b, g, sp, q, out);
+__device__ __forceinline__ void rhs_bf_r(const BlockDev& b, const GasDev& g,
+                                         const SolverDev& sp, long q, const double* r,
+                                         double* out) {
+  rhs_b_r(b, g, sp, q, r, out);
   if (b.mg_forcing) {
 #pragma unroll
     for (int e = 0; e < AGX_NEQ; ++e) out[e] += b.mg_forcing[(long)e * b.nplane + q];
   }
+}
+__device__ __forceinline__ void rhs_bf(const BlockDev& b, const GasDev& g,
+                                       const SolverDev& sp, long q, double* out) {
+  double r[AGX_NEQ];
+  load5(b.resid, q, r);
+  rhs_bf_r(b, g, sp, q, r, out);
 }
 
 // procBlock::ImplicitLower / ImplicitUpper procBlock.cpp:1056-1163 with

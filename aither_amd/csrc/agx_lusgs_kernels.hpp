@@ -101,8 +101,18 @@ __global__ void __launch_bounds__(256) k_d2_x_copy(BlockDev b, int to_d2, unsign
 // sweep: the forward sweep writes every physical x before it is read, and
 // without connection surfaces no ghost x is ever a neighbour) -- skip 48 B/cell.
 // Grid: (Pi / 32, Pj / 32, Pk) tiles of the padded box, 256 threads.
+// LEAN: the update of the last iteration left state, c and the viscous factor of every
+// physical cell in the D2 arrays (k_update_d2<1, *>, Block::d2_state_current) -- their state
+// is not read, c and the factor are not formed, PA_S and vf() are not stored.  Ghost
+// positions keep the full path where the block has a connection side (ghost_s: their S
+// feeds the off-diagonals across it, and the ghost fill runs after the update); without one
+// nobody uses a ghost S, and it stays what it was.
+// NORMS: the residual is in registers for b: fold its norms here (one partial per tile, the
+// record of k_update_d2), so that the update need not read it again.
+template <int LEAN, int NORMS>
 __global__ void __launch_bounds__(256)
-k_lusgs_prepare(BlockDev b, GasDev g, SolverDev sp, int write_x, unsigned tag, int again) {
+k_lusgs_prepare(BlockDev b, GasDev g, SolverDev sp, int write_x, unsigned tag, int again,
+                int ghost_s, NormPartial* partials) {
   // (again: a second launch on the same residual -- the forcing term of a multigrid level now
   // exists -- takes the finished diagonal of the first one)
   __shared__ double sv[6][TT][TRS];
@@ -114,6 +124,9 @@ k_lusgs_prepare(BlockDev b, GasDev g, SolverDev sp, int write_x, unsigned tag, i
   const int k = ke - b.ng;
   const int li = tid & (TT - 1);
   double bb[4][AGX_NEQ], x0[4][AGX_NEQ], ainv[4], vf[4];
+  double l2[AGX_NEQ] = {0, 0, 0, 0, 0};
+  double vmax = -1.0e300;
+  long long vlin = 0x7fffffffffffffffLL;
   // ---- round 1: state + speed of sound ----
 #pragma unroll
   for (int m = 0; m < 4; ++m) {
@@ -127,12 +140,14 @@ k_lusgs_prepare(BlockDev b, GasDev g, SolverDev sp, int write_x, unsigned tag, i
     double cs = 0.0;
     if (ie < z.Pi && je < z.Pj) {
       const long q = b.idx(i, j, k);
-      double s[AGX_NEQ];
-#pragma unroll
-      for (int e = 0; e < AGX_NEQ; ++e) { s[e] = b.state[e][q]; sv[e][lj][li] = s[e]; }
-      if (s[0] > 0.0) cs = sound_speed(g, s);
-      if (sp.viscous) vf[m] = cell_visc_factor(g, s);
       const bool phys = i >= 0 && i < b.ni && j >= 0 && j < b.nj && k >= 0 && k < b.nk;
+      if (!LEAN || (ghost_s && !phys)) {
+        double s[AGX_NEQ];
+#pragma unroll
+        for (int e = 0; e < AGX_NEQ; ++e) { s[e] = b.state[e][q]; sv[e][lj][li] = s[e]; }
+        if (s[0] > 0.0) cs = sound_speed(g, s);
+        if (sp.viscous) vf[m] = cell_visc_factor(g, s);
+      }
       if (phys) {
         double dvt = (b.vol[q] * (1.0 + sp.zeta)) / (b.dt[q] * sp.theta);
         if (sp.dual_time_cfl > 0.0) dvt += fmax(b.specrad[q], 0.0) / sp.dual_time_cfl;
@@ -147,7 +162,17 @@ k_lusgs_prepare(BlockDev b, GasDev g, SolverDev sp, int write_x, unsigned tag, i
         // spectral radii to THAT -- SolverDev::diag_add)
         if (sp.diag_add) b.a[q] = a;
         ainv[m] = 1.0 / a;
-        rhs_bf(b, g, sp, q, bb[m]);
+        double r[AGX_NEQ];
+        load5(b.resid, q, r);
+        rhs_bf_r(b, g, sp, q, r, bb[m]);
+        if (NORMS) {         // (the fold and the tie rule of k_update_d2)
+          const long lin0 = (((long)k * b.nj + j) * b.ni + i) * AGX_NEQ;
+#pragma unroll
+          for (int e = 0; e < AGX_NEQ; ++e) {
+            l2[e] += r[e] * r[e];
+            if (r[e] > vmax || (r[e] == vmax && lin0 + e < vlin)) { vmax = r[e]; vlin = lin0 + e; }
+          }
+        }
         if (sp.requires_init) {
 #pragma unroll
           for (int e = 0; e < AGX_NEQ; ++e) x0[m][e] = bb[m][e] * ainv[m];
@@ -159,17 +184,25 @@ k_lusgs_prepare(BlockDev b, GasDev g, SolverDev sp, int write_x, unsigned tag, i
   __syncthreads();
   long pos[4];
   int tli[4], tlj[4];
+  bool st_s[4];        // this position's S and viscous factor are stored (LEAN: ghosts at most)
 #pragma unroll
   for (int m = 0; m < 4; ++m) {
     const unsigned tl = s_tab[tid + 256 * m];
     tli[m] = tl & 0xff; tlj[m] = tl >> 8;
     const int ie = i0 + tli[m], je = j0 + tlj[m];
     pos[m] = -1;
+    st_s[m] = !LEAN;
     if (ie < z.Pi && je < z.Pj) {
       pos[m] = (long)ke * z.ps + z.pos2(ie, je);
+      if (LEAN) {
+        const int i = ie - b.ng, j = je - b.ng;
+        st_s[m] = ghost_s && !(i >= 0 && i < b.ni && j >= 0 && j < b.nj && k >= 0 && k < b.nk);
+      }
+      if (st_s[m]) {
 #pragma unroll
-      for (int h = 0; h < 3; ++h)
-        z.pa(PA_S + h)[pos[m]] = make_double2(sv[2 * h][tlj[m]][tli[m]], sv[2 * h + 1][tlj[m]][tli[m]]);
+        for (int h = 0; h < 3; ++h)
+          z.pa(PA_S + h)[pos[m]] = make_double2(sv[2 * h][tlj[m]][tli[m]], sv[2 * h + 1][tlj[m]][tli[m]]);
+      }
     }
   }
   __syncthreads();
@@ -192,29 +225,40 @@ k_lusgs_prepare(BlockDev b, GasDev g, SolverDev sp, int write_x, unsigned tag, i
         z.pa(PA_B + h)[pos[m]] = make_double2(sv[2 * h][tlj[m]][tli[m]], sv[2 * h + 1][tlj[m]][tli[m]]);
     }
   }
-  __syncthreads();
   // ---- round 3: initial x (zero unless the solver needs b / a) + viscous factor ----
+  if (!LEAN || write_x || ghost_s) {     // (uniform; LEAN without either: nothing to store)
+    __syncthreads();
 #pragma unroll
-  for (int m = 0; m < 4; ++m) {
-    const int lj = (tid >> 5) + 8 * m;
+    for (int m = 0; m < 4; ++m) {
+      const int lj = (tid >> 5) + 8 * m;
 #pragma unroll
-    for (int e = 0; e < AGX_NEQ; ++e) sv[e][lj][li] = x0[m][e];
-    sv[5][lj][li] = vf[m];
-  }
-  __syncthreads();
-#pragma unroll
-  for (int m = 0; m < 4; ++m) {
-    if (pos[m] >= 0) {
-      if (write_x) {
-        // (every writer of x tags it: KpArgs)
-        z.pa(PA_X + 0)[pos[m]] = make_double2(kp_tagged(sv[0][tlj[m]][tli[m]], tag),
-                                              kp_tagged(sv[1][tlj[m]][tli[m]], tag));
-        z.pa(PA_X + 1)[pos[m]] = make_double2(kp_tagged(sv[2][tlj[m]][tli[m]], tag),
-                                              kp_tagged(sv[3][tlj[m]][tli[m]], tag));
-        z.pa(PA_X + 2)[pos[m]] = make_double2(kp_tagged(sv[4][tlj[m]][tli[m]], tag), ai2[m]);
-      }
-      if (sp.viscous) z.vf()[pos[m]] = sv[5][tlj[m]][tli[m]];
+      for (int e = 0; e < AGX_NEQ; ++e) sv[e][lj][li] = x0[m][e];
+      sv[5][lj][li] = vf[m];
     }
+    __syncthreads();
+#pragma unroll
+    for (int m = 0; m < 4; ++m) {
+      if (pos[m] >= 0) {
+        if (write_x) {
+          // (every writer of x tags it: KpArgs)
+          z.pa(PA_X + 0)[pos[m]] = make_double2(kp_tagged(sv[0][tlj[m]][tli[m]], tag),
+                                                kp_tagged(sv[1][tlj[m]][tli[m]], tag));
+          z.pa(PA_X + 1)[pos[m]] = make_double2(kp_tagged(sv[2][tlj[m]][tli[m]], tag),
+                                                kp_tagged(sv[3][tlj[m]][tli[m]], tag));
+          z.pa(PA_X + 2)[pos[m]] = make_double2(kp_tagged(sv[4][tlj[m]][tli[m]], tag), ai2[m]);
+        }
+        if (sp.viscous && st_s[m]) z.vf()[pos[m]] = sv[5][tlj[m]][tli[m]];
+      }
+    }
+  }
+  if (NORMS) {
+    // (the fold's scratch inside the tile arrays: LDS of its own would cost the third
+    // workgroup of a CU)
+    __syncthreads();
+    const long bid = ((long)blockIdx.z * gridDim.y + blockIdx.y) * gridDim.x + blockIdx.x;
+    norm_block_fold_in(l2, vmax, vlin, partials + bid,
+                       reinterpret_cast<double(*)[16]>(&sv[0][0][0]),
+                       reinterpret_cast<long long*>(&sv[1][0][0]));
   }
 }
 
@@ -846,6 +890,12 @@ k_matrix_resid_d2m(BlockDev b, GasDev g, SolverDev sp, int kc, NormPartial* part
 // procBlock::UpdateBlock / ImplicitTimeAdvance (procBlock.cpp:826-872, :902)
 // with x read from the D2 array through the tile transposition; norms as in
 // k_update.  Grid: (ni / 32, nj / 32, nk) tiles of the physical cells.
+// WRITE_S: the new state is in registers -- form its speed of sound and viscous factor (the
+// expressions of k_lusgs_prepare on the doubles just stored: the same bits) and carry them
+// back through the tile into PA_S and vf(), so that the next prepare need not read the state
+// of the physical cells (its LEAN form).
+// NORMS = 0: k_lusgs_prepare folded the norms of this residual; it is not read here.
+template <int WRITE_S, int NORMS>
 __global__ void __launch_bounds__(256)
 k_update_d2(BlockDev b, GasDev g, SolverDev sp, int last_mm, NormPartial* partials) {
   __shared__ double sv[AGX_NEQ][TT][TRS];
@@ -855,16 +905,20 @@ k_update_d2(BlockDev b, GasDev g, SolverDev sp, int last_mm, NormPartial* partia
   tile_table(s_tab);
   __syncthreads();
   const int i0 = blockIdx.x * TT, j0 = blockIdx.y * TT, k = blockIdx.z;
+  long pos[4];
+  int tli[4], tlj[4];
 #pragma unroll
   for (int m = 0; m < 4; ++m) {
     const unsigned tl = s_tab[tid + 256 * m];
-    const int tli = tl & 0xff, tlj = tl >> 8;
-    const int i = i0 + tli, j = j0 + tlj;
+    tli[m] = tl & 0xff; tlj[m] = tl >> 8;
+    const int i = i0 + tli[m], j = j0 + tlj[m];
+    pos[m] = -1;
     if (i < b.ni && j < b.nj) {
       const long p = (long)(k + b.ng) * z.ps + z.pos2(i + b.ng, j + b.ng);
+      pos[m] = p;
       const double2 x0 = z.pa(PA_X)[p], x1 = z.pa(PA_X + 1)[p], x2 = z.pa(PA_X + 2)[p];
-      sv[0][tlj][tli] = x0.x; sv[1][tlj][tli] = x0.y; sv[2][tlj][tli] = x1.x;
-      sv[3][tlj][tli] = x1.y; sv[4][tlj][tli] = x2.x;
+      sv[0][tlj[m]][tli[m]] = x0.x; sv[1][tlj[m]][tli[m]] = x0.y; sv[2][tlj[m]][tli[m]] = x1.x;
+      sv[3][tlj[m]][tli[m]] = x1.y; sv[4][tlj[m]][tli[m]] = x2.x;
     }
   }
   __syncthreads();
@@ -872,19 +926,32 @@ k_update_d2(BlockDev b, GasDev g, SolverDev sp, int last_mm, NormPartial* partia
   double l2[AGX_NEQ] = {0, 0, 0, 0, 0};
   double vmax = -1.0e300;
   long long vlin = 0x7fffffffffffffffLL;
+  double nsk[4][AGX_NEQ], cs[4], vf[4];
 #pragma unroll
   for (int m = 0; m < 4; ++m) {
     const int lj = (tid >> 5) + 8 * m;
     const int i = i0 + li, j = j0 + lj;
+    cs[m] = 0.0;
+    vf[m] = 0.0;
+    if (WRITE_S) {
+#pragma unroll
+      for (int e = 0; e < AGX_NEQ; ++e) nsk[m][e] = 0.0;
+    }
     if (i < b.ni && j < b.nj) {
       const long q = b.idx(i, j, k);
       double r[AGX_NEQ], s[AGX_NEQ], du[AGX_NEQ], ns[AGX_NEQ];
-      load5(b.resid, q, r);
+      if (NORMS) load5(b.resid, q, r);
       load5(b.state, q, s);
 #pragma unroll
       for (int e = 0; e < AGX_NEQ; ++e) du[e] = sv[e][lj][li];
       update_prim_with_cons(g, s, du, ns);
       store5(b.state, q, ns);
+      if (WRITE_S) {
+#pragma unroll
+        for (int e = 0; e < AGX_NEQ; ++e) nsk[m][e] = ns[e];
+        if (ns[0] > 0.0) cs[m] = sound_speed(g, ns);
+        if (sp.viscous) vf[m] = cell_visc_factor(g, ns);
+      }
       // (gridLevel::ResetDiagonal: the inviscid residual kernels ASSIGN the scalar
       // diagonal, so there is nothing to reset on this path)
       if (sp.bdf2 && last_mm) {           // gridLevel.cpp:425-428
@@ -892,16 +959,56 @@ k_update_d2(BlockDev b, GasDev g, SolverDev sp, int last_mm, NormPartial* partia
         load5(b.consn, q, u);
         store5(b.consnm1, q, u);
       }
-      const long lin0 = (((long)k * b.nj + j) * b.ni + i) * AGX_NEQ;
+      if (NORMS) {
+        const long lin0 = (((long)k * b.nj + j) * b.ni + i) * AGX_NEQ;
 #pragma unroll
-      for (int e = 0; e < AGX_NEQ; ++e) {
-        l2[e] += r[e] * r[e];
-        if (r[e] > vmax || (r[e] == vmax && lin0 + e < vlin)) { vmax = r[e]; vlin = lin0 + e; }
+        for (int e = 0; e < AGX_NEQ; ++e) {
+          l2[e] += r[e] * r[e];
+          if (r[e] > vmax || (r[e] == vmax && lin0 + e < vlin)) { vmax = r[e]; vlin = lin0 + e; }
+        }
       }
     }
   }
-  const long bid = ((long)blockIdx.z * gridDim.y + blockIdx.y) * gridDim.x + blockIdx.x;
-  norm_block_fold(l2, vmax, vlin, partials + bid);
+  if (WRITE_S) {
+    // the new state back into tile-diagonal order, in two rounds through the five arrays:
+    // (rho,u) (v,w) with p kept in a register, then c and the viscous factor
+    __syncthreads();                      // (every x of the tile has been read)
+#pragma unroll
+    for (int m = 0; m < 4; ++m) {
+      const int lj = (tid >> 5) + 8 * m;
+#pragma unroll
+      for (int e = 0; e < AGX_NEQ; ++e) sv[e][lj][li] = nsk[m][e];
+    }
+    __syncthreads();
+    double pp[4];
+#pragma unroll
+    for (int m = 0; m < 4; ++m) {
+      pp[m] = sv[4][tlj[m]][tli[m]];
+      if (pos[m] >= 0) {
+        z.pa(PA_S + 0)[pos[m]] = make_double2(sv[0][tlj[m]][tli[m]], sv[1][tlj[m]][tli[m]]);
+        z.pa(PA_S + 1)[pos[m]] = make_double2(sv[2][tlj[m]][tli[m]], sv[3][tlj[m]][tli[m]]);
+      }
+    }
+    __syncthreads();
+#pragma unroll
+    for (int m = 0; m < 4; ++m) {
+      const int lj = (tid >> 5) + 8 * m;
+      sv[0][lj][li] = cs[m];
+      sv[1][lj][li] = vf[m];
+    }
+    __syncthreads();
+#pragma unroll
+    for (int m = 0; m < 4; ++m) {
+      if (pos[m] >= 0) {
+        z.pa(PA_S + 2)[pos[m]] = make_double2(pp[m], sv[0][tlj[m]][tli[m]]);
+        if (sp.viscous) z.vf()[pos[m]] = sv[1][tlj[m]][tli[m]];
+      }
+    }
+  }
+  if (NORMS) {
+    const long bid = ((long)blockIdx.z * gridDim.y + blockIdx.y) * gridDim.x + blockIdx.x;
+    norm_block_fold(l2, vmax, vlin, partials + bid);
+  }
 }
 
 }  // namespace agx
