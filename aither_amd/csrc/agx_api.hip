@@ -8,6 +8,7 @@
 #include "agx_kernels.hpp"
 #include "agx_geometry.hpp"
 #include "agx_mem.hpp"
+#include "agx_switches.hpp"
 #include <rccl/rccl.h>
 #include <cstdarg>
 #include <cstdio>
@@ -19,6 +20,8 @@
 #include <map>
 #include <string>
 #include <algorithm>
+#include <memory>
+#include <type_traits>
 
 using namespace agx;
 
@@ -37,17 +40,26 @@ static int fail(const char* fmt, ...) {
       return fail("%s failed: %s (%s:%d)", #call, hipGetErrorString(e_),   \
                   __FILE__, __LINE__);                                     \
   } while (0)
-// a kernel templated on the solver mode (solver_mode_of, agx_kernels.hpp)
-#define AGX_BY_MODE(sp, kernel, grid, block, stream, ...)                                  \
-  do {                                                                                     \
-    switch (agx::solver_mode_of(sp)) {                                                     \
-      case 0: hipLaunchKernelGGL(kernel<0>, grid, block, 0, stream, __VA_ARGS__); break;   \
-      case 1: hipLaunchKernelGGL(kernel<1>, grid, block, 0, stream, __VA_ARGS__); break;   \
-      default: hipLaunchKernelGGL(kernel<2>, grid, block, 0, stream, __VA_ARGS__); break;  \
-    }                                                                                      \
-  } while (0)
 
 namespace {
+
+// A run-time value as a template argument: f is called with the std::integral_constant of
+// the value, which a generic lambda puts into a template argument list -- so the launch of a
+// kernel that is templated on run-time choices is written once, with one argument list.
+// by_int takes the constants a value may have; one that matches none of them gets the last
+// (the `default:` of a switch).  Only what f names is instantiated: where a template argument
+// is meant for some values of another only, nest the calls accordingly.  (Inside a nested
+// lambda the constant is named through its type, decltype(x)::value: a captured x is no
+// constant expression.)
+template <class F>
+auto by_bool(bool v, F f) {
+  return v ? f(std::true_type{}) : f(std::false_type{});
+}
+template <int V0, int... Vs, class F>
+auto by_int(int v, F f) {
+  if constexpr (sizeof...(Vs) == 0) return f(std::integral_constant<int, V0>{});
+  else return v == V0 ? f(std::integral_constant<int, V0>{}) : by_int<Vs...>(v, f);
+}
 
 // The sweep graphs of one block, or of all blocks in one launch: a slot per direction,
 // triangle set and value of un_is_u.  They hold the BlockDev they were captured with.
@@ -73,18 +85,18 @@ struct Block {
   DevBuf<double> blockmat;    // block-matrix solvers: a_ | aInv_ | velocityGrad_ planes
   DevBuf<double> sweep_rec;   // plane-by-plane sweeps: geo | dyn | rhs records (k_sweep_records)
   bool sweep_geo_built = false; // the (static) geometry records exist
-  bool x_planes_current = false; // D2 path: the planes of x equal the D2 arrays (multigrid calls)
-  // D2 path: agx_phase_implicit_begin left x_ = 0 unwritten (the first half sweep does not read
-  // it); until that sweep has run a download of x returns the zeros the reference holds
+  // Which derived data of the D2 path are current.  Assigned by the events below agx_ctx
+  // ("what happened") and nowhere else; DESIGN.md section 4 has the table of event x flag.
+  bool x_planes_current = false; // the planes of x equal the D2 arrays (multigrid calls)
+  // agx_phase_implicit_begin left x_ = 0 unwritten (the first half sweep does not read it);
+  // until that sweep has run a download of x returns the zeros the reference holds
   bool x_is_zero = false;
-  // D2 path: PA_S and vf() of the physical cells hold the state planes' values (k_update_d2
-  // wrote both last), so the next prepare takes its lean form.  Only the D2 branch of
-  // update_pass sets it; whatever else may write the state planes of physical cells clears it
-  // (state_written, upload_aos).  A cleared flag costs a full prepare, never a result.
+  // PA_S and vf() of the physical cells hold the state planes' values (k_update_d2 wrote both
+  // last), so the next prepare takes its lean form.  A cleared flag costs a full prepare,
+  // never a result.
   bool d2_state_current = false;
-  // D2 path: k_lusgs_prepare folded the norms of the residual planes as they are now into
-  // its slot of norm_out, so the update neither reads the residual nor folds.  Prepare sets
-  // it; agx_phase_residual and uploads clear it (resid_written, upload_aos).
+  // k_lusgs_prepare folded the norms of the residual planes as they are now into its slot of
+  // norm_out, so the update neither reads the residual nor folds.
   bool resid_norms_current = false;
   // multigrid: forcing | matrix residual | saved update planes (each allocated on first
   // use); the transfer maps of this block as the FINE side (device copies, keyed by the
@@ -152,7 +164,9 @@ enum { G_RESID = 0, G_UPDATE = 1, G_BC = 2, G_SWEEP = 3, G_VISC = 4, G_PREPARE =
 
 }  // namespace
 
-struct agx_ctx {
+// (the values of the AGX_* switches are its base: c->use_gather, c->spin_limit, ... as
+// agx_ctx_create parsed them, agx_switches.hpp)
+struct agx_ctx : agx::Switches {
   int device = 0, rank = 0;
   hipStream_t stream = nullptr;
   bool have_cfg = false, finalized = false;
@@ -176,33 +190,34 @@ struct agx_ctx {
   ncclComm_t nccl = nullptr;
   DevBuf<NormPartial> partials;
   long n_partials = 0;
-  DevBuf<NormPartial> norm_out;         // one per block
+  // norm_out, four regions for nb blocks: the update's norms (the matrix residual of the
+  // phase API lands there between prepare and update) | NORM_FOLD partials, scratch of the
+  // two-level fold | the matrix residual agx_iterate reads back with the update's norms | the
+  // residual norms k_lusgs_prepare folds.  norm_host: what the update's read-back brings | the
+  // matrix residual that rides with it.
+  static constexpr size_t NORM_FOLD = 64;
+  DevBuf<NormPartial> norm_out;
   PinnedBuf<NormPartial> norm_host;
+  size_t norm_nb() const { return std::max<size_t>(blocks.size(), 1); }
+  NormPartial* norm_update() const { return norm_out.get(); }
+  NormPartial* norm_fold() const { return norm_update() + norm_nb(); }
+  NormPartial* norm_mres() const { return norm_fold() + NORM_FOLD; }
+  NormPartial* norm_prepare() const { return norm_mres() + norm_nb(); }
+  NormPartial* norm_end() const { return norm_prepare() + norm_nb(); }
+  NormPartial* host_update() const { return norm_host.get(); }
+  NormPartial* host_mres() const { return host_update() + norm_nb(); }
+  NormPartial* host_end() const { return host_mres() + norm_nb(); }
   DevBuf<int> err_dev;
   PinnedBuf<int> err_host;
   DevBuf<double> halo_buf;
   DevBuf<double> stage_buf;      // AoS staging of uploads / downloads (stage_buffer)
   DevBuf<double> rans_rec;       // face records of the rans viscous residual (k_rans_faces),
                                  // sized for the largest block, shared by all of them
-  bool use_gather = false;   // AGX_KERNEL=gather: one-thread-per-cell gather kernel
-  bool use_tile = true;      // AGX_KERNEL=tile (default) | march
-  int num_cu = 256;          // persistent workgroups of the tile kernel
-  bool eager_ghosts = true;  // AGX_EAGER_GHOSTS=0: fill ghost cells at the start of agx_iterate
-  // AGX_OVERLAP=0: the slabs of x travel before a DPLUR sweep starts (default: while its
-  // interior cells are relaxed, on ov_stream)
-  bool overlap = true;
+  int num_cu = 256;          // persistent workgroups of the tile kernel (AGX_WORKGROUPS, or one per CU)
+  // the DPLUR sweeps that overlap the exchange of x (AGX_OVERLAP) run it on ov_stream
   hipStream_t ov_stream = nullptr;
   hipEvent_t ov_ready = nullptr, ov_done = nullptr;
-  bool visc_gather = false;  // AGX_VISC=gather: one-thread-per-cell viscous kernel
-  bool visc_march = false;   // AGX_VISC=march: face-once form without LDS staging
-  int lusgs_mode = 1;        // AGX_LUSGS=plane (0: launch per hyperplane on the SoA
-                             // planes, comparison form) | kp (1, default: agx_lusgs.hpp)
-  int spin_limit = 4000000;  // AGX_SPIN_LIMIT: polls before a waiting plane gives up
-  bool allow_fuse = true;    // AGX_NO_FUSE=1: separate update kernel
   bool fused_pending = false;
-  bool use_graphs = true;    // AGX_GRAPHS=0: launch the hyperplane sweeps one by one
-  bool sweep_records = true; // AGX_SWEEP_RECORDS=0: the hyperplane sweeps read the plane-major arrays
-  bool sweep_three = true;   // AGX_SWEEP_THREE=0: one lane per cell in the hyperplane sweeps
   hipStream_t cap_stream = nullptr;   // stream the sweep graphs are recorded on
   // several blocks swept hyperplane by hyperplane: the blocks of a half sweep are
   // independent (ghost x comes from the exchange before it), so their chains of
@@ -212,14 +227,12 @@ struct agx_ctx {
   // ... or, hyperplane step by step, all blocks in one launch (k_lusgs_plane_all) from a
   // table of their BlockDev in device memory, one graph per direction / triangle set /
   // un_is_u (AGX_SWEEP_ALL=0: the branch streams)
-  bool sweep_all_launch = true;
   DevBuf<BlockDev> blocks_tab;
   PinnedBuf<BlockDev> blocks_tab_host;
   SweepGraphs sweep_graph_all;
   // the pipelined half sweep (k_lusgs_pipe): a workgroup per k-plane of every block
   bool mg_coarse = false;                // a coarse multigrid level (agx_mg_restrict made it one)
   bool mres_plane_form = false;          // agx_mg_matrix_residual: k_matrix_resid on every block
-  bool sweep_pipe = true;                // AGX_SWEEP_PIPE=0: one launch per hyperplane
   DevBuf<PipeJob> pipe_jobs[2];          // pipeline order back / forward
   DevBuf<int> pipe_slot0;
   DevBuf<long long> pipe_progress;       // 16 words per plane
@@ -229,9 +242,8 @@ struct agx_ctx {
   long long pipe_launches = 0;
   // local connections exchanged in one gather + one scatter launch (AGX_HALO_BATCH=0: a
   // launch pair per connection).  Legal when no slice reads a cell another connection's
-  // insert writes (checked at agx_setup_finalize); tables per halo selector in device memory
-  bool halo_batch = true;
-  bool halo_batch_required = false;
+  // insert writes (checked at agx_setup_finalize, which clears halo_batch where no batch
+  // forms); tables per halo selector in device memory
   int halo_batch_sides = 0;
   long halo_batch_nmax = 0;
   // levels of the batched exchange (halo_batch_plan): the local connections in table order,
@@ -245,20 +257,8 @@ struct agx_ctx {
   bool halo_tab_valid[5][2] = {};
   int halo_set[5] = {};
   PinnedBuf<HaloSide> halo_tab_host;      // staging, 2 * sides entries
-  // the order in which the tile kernels' workgroups visit their (column, k) steps
-  // (agx_tile_plan.hpp); AGX_TILE_ORDER=step|column sets both.  Each kernel's default is the
-  // order that measured faster at 256^3
-  int tile_order_inv = TILE_ORDER_STEP;      // k_residual_tile
-  int tile_order_visc = TILE_ORDER_STEP;     // k_visc_tile
-  std::map<std::array<int, 6>, TilePlan> tile_plans;   // (made once per shape)
-  int mresid_split = 1;      // bands of diagonals per XCD in k_matrix_resid_d2 (AGX_MRESID_SPLIT)
-  bool mresid_march = true;  // AGX_MRESID=plane: one plane position per thread (comparison form)
-  // AGX_D2_STATE=update (default): k_update_d2 writes the D2 state of the next iteration and
-  // prepare skips the physical cells | prepare: prepare re-lays the state every iteration
-  bool d2_state_update = true;
-  // AGX_RESID_NORMS=prepare (default): k_lusgs_prepare folds the residual norms and the
-  // update does not read the residual | update: k_update_d2 reads it for the norms
-  bool resid_norms_prepare = true;
+  // the tile kernels' plans per shape, charge and order (AGX_TILE_ORDER), made once each
+  std::map<std::array<int, 6>, TilePlan> tile_plans;
   bool have_time_n = false;  // agx_store_time_n has run (nonreflecting BCs read consVarsN)
   bool have_wall_data = false;   // a residual's viscous ghost fill has stored the wall-law data
   // agx_iterate fills the ghost cells for the NEXT call right after the update,
@@ -284,11 +284,80 @@ struct agx_ctx {
   long t_n[G_NGROUP] = {};
 };
 
+// ---- what the file uses before it defines it (the entry points: aither_gfx950.h) ----
 static int my_side(const agx_ctx* c, const Conn& k);
+static int implicit_begin(agx_ctx* c, int write_x);
+static int halo_exchange_remote(agx_ctx* c, int what);
+#if AGX_FAST
+static int d2_prepare(agx_ctx* c, Block& blk, int write_x, int again, int norms);
+#endif
+namespace {
+void resolve_timing(agx_ctx* c);
+int lusgs_sweep(agx_ctx* c, Block& blk, bool forward, int full, hipStream_t st = nullptr);
+}  // namespace
 
 namespace {
+// ---- what happened, and which derived data it leaves stale or current ---------------------
+// The only statements that assign Block::x_planes_current, x_is_zero, d2_state_current,
+// resid_norms_current and agx_ctx::ghosts_prefilled, state_is_time_n: a writer says what it
+// did.  DESIGN.md section 4 has the table of event x flag with the reasons.
+//
+// x: something is about to write it where it lives (the D2 arrays on the diagonal-ordered
+// path) / k_d2_x_copy made a block's planes and its D2 arrays equal
+void x_changed(agx_ctx* c) {
+  for (auto& blk : c->blocks) blk.x_planes_current = false;
+}
+void x_planes_copied(Block& b) { b.x_planes_current = true; }
+// prepare left a block's x = 0 unwritten (or not) / an upload wrote a block's x / the first
+// half sweep writes every block's
+void x_prepared(Block& b, bool left_zero) { b.x_is_zero = left_zero; }
+void x_uploaded(Block& b) { b.x_is_zero = false; }
+void x_swept(agx_ctx* c) {
+  for (auto& blk : c->blocks) blk.x_is_zero = false;
+}
+// the state planes of physical cells: something other than k_update_d2 is about to write
+// those of all blocks / of one block / k_update_d2 stored a block's new state, and with
+// wrote_d2 (AGX_D2_STATE=update) the D2 state of the next prepare as well
+void state_written(agx_ctx* c) {
+  for (auto& blk : c->blocks) blk.d2_state_current = false;
+}
+void state_written(Block& b) { b.d2_state_current = false; }
+void state_updated_d2(Block& b, bool wrote_d2) { b.d2_state_current = wrote_d2; }
+// the residual planes: something is about to write them / k_lusgs_prepare folded a block's
+// norms of them / the update took the folded norms (one use: a second update on the same
+// residual reads it itself)
+void resid_written(agx_ctx* c) {
+  for (auto& blk : c->blocks) blk.resid_norms_current = false;
+}
+void resid_norms_folded(Block& b) { b.resid_norms_current = true; }
+void resid_norms_used(Block& b) { b.resid_norms_current = false; }
+// an upload or a multigrid restriction wrote planes of a block: whichever they were, its D2
+// state and its folded norms are taken for stale
+void planes_uploaded(Block& b) {
+  b.d2_state_current = false;
+  b.resid_norms_current = false;
+}
+// the ghost cells: the fill for the next agx_iterate was queued behind the update's norms /
+// it is used up, or something wrote ghost cells or the state since
+void ghosts_filled_ahead(agx_ctx* c) { c->ghosts_prefilled = true; }
+void ghost_fill_gone(agx_ctx* c) { c->ghosts_prefilled = false; }
+// the state became time level n (agx_store_time_n; nonreflecting ghost states read
+// consVarsN, ghostStates.cpp:435-462: a ghost fill queued behind the last update saw the old
+// time level) / an update is about to advance it
+void state_became_time_n(agx_ctx* c) {
+  for (auto& blk : c->blocks)
+    if (blk.nr_max > 0) c->ghosts_prefilled = false;
+  c->state_is_time_n = true;
+}
+void state_left_time_n(agx_ctx* c) { c->state_is_time_n = false; }
+// the caller wrote a field of a block (an upload of whichever field, a restriction of the
+// state): the ghost cells and consVarsN no longer belong to the state
+void field_written_by_caller(agx_ctx* c) {
+  ghost_fill_gone(c);
+  state_left_time_n(c);
+}
+// --------------------------------------------------------------------------------------------
 
-void resolve_timing(agx_ctx* c);
 
 struct Timer {   // hipEvents on the library's stream around one kernel group
   agx_ctx* c;
@@ -389,10 +458,7 @@ int upload_aos(agx_ctx* c, Block& b, const double* host, double* const* dst,
                int ncomp, int ci, int cj, int ck, int gsrc) {
   const long n = (long)ci * cj * ck;
   double* tmp = nullptr;
-  // (whichever planes of the block this writes: its D2 state and its folded norms are taken
-  // for stale)
-  b.d2_state_current = false;
-  b.resid_norms_current = false;
+  planes_uploaded(b);
   if (stage_buffer(c, (size_t)n * ncomp, &tmp)) return 1;
   HIPCHK(hipMemcpyAsync(tmp, host, sizeof(double) * n * ncomp,
                         hipMemcpyHostToDevice, c->stream));
@@ -492,19 +558,6 @@ int ensure_halo_buf(agx_ctx* c, long ndoubles) {
 // what a halo exchange moves: the state planes, or x -- which the D2 LU-SGS path
 // keeps in its own arrays and index space (1; 0: the planes -- the index of ConnSide::map)
 int halo_in_d2(const Block& b, int what) { return what == AGX_HALO_UPDATE && b.d.d2.base ? 1 : 0; }
-// something is about to write x where it lives (the D2 arrays on the diagonal-ordered path)
-void x_changed(agx_ctx* c) {
-  for (auto& blk : c->blocks) blk.x_planes_current = false;
-}
-// something other than k_update_d2 is about to write the state planes of physical cells /
-// something is about to write the residual planes (Block::d2_state_current,
-// Block::resid_norms_current)
-void state_written(agx_ctx* c) {
-  for (auto& blk : c->blocks) blk.d2_state_current = false;
-}
-void resid_written(agx_ctx* c) {
-  for (auto& blk : c->blocks) blk.resid_norms_current = false;
-}
 Planes5 halo_planes(Block& b, int what) {
   Planes5 r;
   // (the scatter of an exchange of x also refreshes the sweep records' copy)
@@ -622,25 +675,18 @@ void launch_inv_kernel(agx_ctx* c, const BlockDev& b, double cfl, bool fuse,
   const dim3 tb(64, g_march_tj + 2);
 #if AGX_FAST
   if (tile_ok(c, b)) {
-    if (fuse && ma.store_consn)
-      hipLaunchKernelGGL((k_residual_tile<RECON, LIM, FLUX, 2, 6>), mp.grid, tb, 0,
+    // FUSE: 0 residual only, 1 + explicit stage update, 2 + AssignSolToTimeN (stage 0)
+    by_int<2, 1, 0>(!fuse ? 0 : ma.store_consn ? 2 : 1, [&](auto fuse_mode) {
+      hipLaunchKernelGGL((k_residual_tile<RECON, LIM, FLUX, fuse_mode, 6>), mp.grid, tb, 0,
                          c->stream, sd, c->gas, c->sp, cfl, ma);
-    else if (fuse)
-      hipLaunchKernelGGL((k_residual_tile<RECON, LIM, FLUX, 1, 6>), mp.grid, tb, 0,
-                         c->stream, sd, c->gas, c->sp, cfl, ma);
-    else
-      hipLaunchKernelGGL((k_residual_tile<RECON, LIM, FLUX, 0, 6>), mp.grid, tb, 0,
-                         c->stream, sd, c->gas, c->sp, cfl, ma);
-  } else
-#endif
-  {
-    if (fuse)
-      hipLaunchKernelGGL((k_residual_march<RECON, LIM, FLUX, true, 6>), mp.grid, tb, 0,
-                         c->stream, sd, c->gas, c->sp, cfl, ma);
-    else
-      hipLaunchKernelGGL((k_residual_march<RECON, LIM, FLUX, false, 6>), mp.grid, tb, 0,
-                         c->stream, sd, c->gas, c->sp, cfl, ma);
+    });
+    return;
   }
+#endif
+  by_bool(fuse, [&](auto fused) {
+    hipLaunchKernelGGL((k_residual_march<RECON, LIM, FLUX, fused, 6>), mp.grid, tb, 0,
+                       c->stream, sd, c->gas, c->sp, cfl, ma);
+  });
 }
 template <int RECON, int LIM>
 void launch_inv_flux(agx_ctx* c, const BlockDev& b, double cfl, bool fuse,
@@ -670,37 +716,24 @@ void launch_inv(agx_ctx* c, const BlockDev& b, double cfl, bool fuse,
 }
 
 // block-matrix solvers: the inviscid part of the main diagonal (k_block_diag_inv)
-template <int RECON>
-void launch_block_diag_lim(agx_ctx* c, const BlockDev& b) {
-  const dim3 grid = cell_grid(b, CELL_BLOCK);
-  switch (RECON == AGX_RECON_MUSCL ? c->cfg.limiter : AGX_LIMITER_NONE) {
-    case AGX_LIMITER_VANALBADA:
-      hipLaunchKernelGGL((k_block_diag_inv<RECON, AGX_LIMITER_VANALBADA>), grid, CELL_BLOCK, 0,
-                         c->stream, b, c->gas, c->sp);
-      break;
-    case AGX_LIMITER_MINMOD:
-      hipLaunchKernelGGL((k_block_diag_inv<RECON, AGX_LIMITER_MINMOD>), grid, CELL_BLOCK, 0,
-                         c->stream, b, c->gas, c->sp);
-      break;
-    default:
-      hipLaunchKernelGGL((k_block_diag_inv<RECON, AGX_LIMITER_NONE>), grid, CELL_BLOCK, 0,
-                         c->stream, b, c->gas, c->sp);
-      break;
-  }
-}
+// (every reconstruction is built with every limiter here; only MUSCL reads the configured one)
 void launch_block_diag(agx_ctx* c, const BlockDev& b) {
-  switch (c->cfg.recon) {
-    case AGX_RECON_CONSTANT: launch_block_diag_lim<AGX_RECON_CONSTANT>(c, b); break;
-    case AGX_RECON_MUSCL: launch_block_diag_lim<AGX_RECON_MUSCL>(c, b); break;
-    case AGX_RECON_WENO: launch_block_diag_lim<AGX_RECON_WENO>(c, b); break;
-    default: launch_block_diag_lim<AGX_RECON_WENOZ>(c, b); break;
-  }
+  by_int<AGX_RECON_CONSTANT, AGX_RECON_MUSCL, AGX_RECON_WENO, AGX_RECON_WENOZ>(
+      c->cfg.recon, [&](auto recon) {
+        constexpr int RECON = decltype(recon)::value;
+        by_int<AGX_LIMITER_VANALBADA, AGX_LIMITER_MINMOD, AGX_LIMITER_NONE>(
+            RECON == AGX_RECON_MUSCL ? c->cfg.limiter : AGX_LIMITER_NONE, [&](auto lim) {
+              hipLaunchKernelGGL((k_block_diag_inv<RECON, decltype(lim)::value>),
+                                 cell_grid(b, CELL_BLOCK), CELL_BLOCK, 0, c->stream, b, c->gas,
+                                 c->sp);
+            });
+      });
 }
 
 bool can_fuse(const agx_ctx* c) {
   // (nonreflecting surfaces read the gradients of the residual's own state after it)
   for (const auto& blk : c->blocks) if (blk.nr_max > 0) return false;
-  return c->allow_fuse && !c->use_gather && !c->sp.implicit && !c->sp.viscous;
+  return !c->no_fuse && !c->use_gather && !c->sp.implicit && !c->sp.viscous;
 }
 
 // the D2 LU-SGS path (agx_lusgs.hpp) serves scalar LU-SGS unless AGX_LUSGS=plane
@@ -786,21 +819,6 @@ int lusgs_kp_launch(agx_ctx* c, Block& blk) {
 }
 // diagonals longer than 256 cells are walked in CH chunks per step
 constexpr int KP_MAX_DIAG = 512;   // LDS: 2 * 19 * 8 * (n + 2) bytes <= 160 KiB
-template <bool FWD, bool FULL, bool CONN>
-int lusgs_kp_chunks(agx_ctx* c, Block& blk) {
-  const int n = std::min(blk.d.ni, blk.d.nj);
-  if (n <= 256) return lusgs_kp_launch<FWD, FULL, CONN, 1>(c, blk);
-  return lusgs_kp_launch<FWD, FULL, CONN, 2>(c, blk);
-}
-template <bool FWD>
-int lusgs_kp_variant(agx_ctx* c, Block& blk, int full) {
-  bool conn = false;
-  for (int q = 0; q < 6; ++q) conn = conn || blk.d.side_conn[q] != 0;
-  if (full) return conn ? lusgs_kp_chunks<FWD, true, true>(c, blk)
-                        : lusgs_kp_chunks<FWD, true, false>(c, blk);
-  return conn ? lusgs_kp_chunks<FWD, false, true>(c, blk)
-              : lusgs_kp_chunks<FWD, false, false>(c, blk);
-}
 
 #else
 constexpr int KP_MAX_DIAG = 1 << 30;
@@ -815,16 +833,14 @@ static void launch_plane_sweep(agx_ctx* c, const BlockDev& b, bool forward, int 
   const int nplanes = b.ni + b.nj + b.nk - 2;
   for (int t = 0; t < nplanes; ++t) {
     const int p = forward ? t : nplanes - 1 - t;
-    if (three) {
-      if (forward)
-        hipLaunchKernelGGL((k_lusgs_plane3<true>), grid, tb, 0, st, b, c->gas, c->sp, p, full);
-      else
-        hipLaunchKernelGGL((k_lusgs_plane3<false>), grid, tb, 0, st, b, c->gas, c->sp, p, full);
-    } else if (forward) {
-      hipLaunchKernelGGL((k_lusgs_plane<true>), grid, tb, 0, st, b, c->gas, c->sp, p, full);
-    } else {
-      hipLaunchKernelGGL((k_lusgs_plane<false>), grid, tb, 0, st, b, c->gas, c->sp, p, full);
-    }
+    if (three)
+      by_bool(forward, [&](auto fwd) {
+        hipLaunchKernelGGL((k_lusgs_plane3<fwd>), grid, tb, 0, st, b, c->gas, c->sp, p, full);
+      });
+    else
+      by_bool(forward, [&](auto fwd) {
+        hipLaunchKernelGGL((k_lusgs_plane<fwd>), grid, tb, 0, st, b, c->gas, c->sp, p, full);
+      });
   }
 }
 
@@ -836,7 +852,6 @@ static bool plane_sweep_all_applicable(const agx_ctx* c) {
     if (blk.d.d2.base || blk.d.ni + blk.d.nj + blk.d.nk - 2 < 8) return false;
   return true;
 }
-int lusgs_sweep(agx_ctx* c, Block& blk, bool forward, int full, hipStream_t st = nullptr);
 // The launches of a half sweep are the same every iteration: captured once into the slot's
 // hipGraph, replayed on st.  (Recorded on a stream of its own: the library's stream may be
 // the legacy default stream, which cannot capture; a graph is launched on any stream.)
@@ -955,10 +970,10 @@ static int lusgs_sweep_pipe(agx_ctx* c, bool forward, int full) {
   ++c->pipe_launches;
   const dim3 grid((unsigned)c->pipe_njobs);
   const dim3 tb(64, c->pipe_waves);
-  if (forward)
-    hipLaunchKernelGGL((k_lusgs_pipe<true>), grid, tb, 0, c->stream, c->blocks_tab.get(), c->gas, c->sp, full, pa);
-  else
-    hipLaunchKernelGGL((k_lusgs_pipe<false>), grid, tb, 0, c->stream, c->blocks_tab.get(), c->gas, c->sp, full, pa);
+  by_bool(forward, [&](auto fwd) {
+    hipLaunchKernelGGL((k_lusgs_pipe<fwd>), grid, tb, 0, c->stream, c->blocks_tab.get(), c->gas,
+                       c->sp, full, pa);
+  });
   HIPCHK(hipGetLastError());
 #ifdef AGX_PIPE_TRACE
   if (pa.trace) {   // diagnostic build only: dump the step timestamps of this launch
@@ -992,17 +1007,16 @@ static int lusgs_sweep_all_one_launch(agx_ctx* c, bool forward, int full) {
   const BlockDev* const tab = c->blocks_tab.get();
   auto launch_all = [&](hipStream_t st) {
     for (int t = 0; t < steps; ++t) {
-      if (three) {
-        if (forward)
-          hipLaunchKernelGGL((k_lusgs_plane_all3<true>), grid, tb, 0, st, tab, c->gas, c->sp, t, full);
-        else
-          hipLaunchKernelGGL((k_lusgs_plane_all3<false>), grid, tb, 0, st, tab, c->gas, c->sp, t, full);
-        continue;
-      }
-      if (forward)
-        hipLaunchKernelGGL((k_lusgs_plane_all<true>), grid, tb, 0, st, tab, c->gas, c->sp, t, full);
+      if (three)
+        by_bool(forward, [&](auto fwd) {
+          hipLaunchKernelGGL((k_lusgs_plane_all3<fwd>), grid, tb, 0, st, tab, c->gas, c->sp, t,
+                             full);
+        });
       else
-        hipLaunchKernelGGL((k_lusgs_plane_all<false>), grid, tb, 0, st, tab, c->gas, c->sp, t, full);
+        by_bool(forward, [&](auto fwd) {
+          hipLaunchKernelGGL((k_lusgs_plane_all<fwd>), grid, tb, 0, st, tab, c->gas, c->sp, t,
+                             full);
+        });
     }
   };
   return replay_captured(c, c->sweep_graph_all.at(forward, full != 0, c->sp.un_is_u != 0),
@@ -1035,6 +1049,26 @@ static int lusgs_sweep_all(agx_ctx* c, bool forward, int full) {
   return 0;
 }
 
+#if AGX_FAST
+// the form of k_lusgs_kp for a half sweep of this block: direction, triangle set, connections
+// on any side, chunks per step (2 x 2 x 2 x 2 forms)
+int lusgs_kp_variant(agx_ctx* c, Block& blk, bool forward, int full) {
+  bool conn = false;
+  for (int q = 0; q < 6; ++q) conn = conn || blk.d.side_conn[q] != 0;
+  const int chunks = std::min(blk.d.ni, blk.d.nj) <= 256 ? 1 : 2;
+  return by_bool(forward, [&](auto fwd) {
+    return by_bool(full != 0, [&](auto fl) {
+      return by_bool(conn, [&](auto cn) {
+        return by_int<1, 2>(chunks, [&](auto ch) {
+          return lusgs_kp_launch<decltype(fwd)::value, decltype(fl)::value,
+                                 decltype(cn)::value, decltype(ch)::value>(c, blk);
+        });
+      });
+    });
+  });
+}
+#endif
+
 int lusgs_sweep(agx_ctx* c, Block& blk, bool forward, int full, hipStream_t st) {
   const BlockDev& b = blk.d;
   if (!st) st = c->stream;
@@ -1052,7 +1086,7 @@ int lusgs_sweep(agx_ctx* c, Block& blk, bool forward, int full, hipStream_t st) 
                            launch_all, st);
   }
 #if AGX_FAST
-  return forward ? lusgs_kp_variant<true>(c, blk, full) : lusgs_kp_variant<false>(c, blk, full);
+  return lusgs_kp_variant(c, blk, forward, full);
 #else
   return fail("no diagonal-ordered sweep in this build");
 #endif
@@ -1104,12 +1138,14 @@ int bc_pass(agx_ctx* c, bool faces, int viscous) {
 }
 
 int reduce_norms(agx_ctx* c, size_t blk_index, long nparts, NormPartial* out = nullptr) {
-  if (!out) out = c->norm_out.get() + blk_index;
+  if (!out) out = c->norm_update() + blk_index;
   if (nparts > 4096) {
-    // two levels: 64 workgroups fold slices into the scratch behind norm_out
-    NormPartial* tmp = c->norm_out.get() + c->blocks.size();
-    hipLaunchKernelGGL(k_norm_final, dim3(64), dim3(256), 0, c->stream, c->partials.get(), nparts, tmp);
-    hipLaunchKernelGGL(k_norm_final, dim3(1), dim3(256), 0, c->stream, tmp, 64L, out);
+    // two levels: NORM_FOLD workgroups fold slices into the scratch region of norm_out
+    NormPartial* tmp = c->norm_fold();
+    hipLaunchKernelGGL(k_norm_final, dim3((unsigned)agx_ctx::NORM_FOLD), dim3(256), 0, c->stream,
+                       c->partials.get(), nparts, tmp);
+    hipLaunchKernelGGL(k_norm_final, dim3(1), dim3(256), 0, c->stream, tmp,
+                       (long)agx_ctx::NORM_FOLD, out);
   } else {
     hipLaunchKernelGGL(k_norm_final, dim3(1), dim3(256), 0, c->stream,
                        c->partials.get(), nparts, out);
@@ -1130,10 +1166,10 @@ int fill_ghosts(agx_ctx* c) {
   return bc_edges(c);
 }
 int update_pass(agx_ctx* c, int mode, int mm, double* l2, agx_linf* linf) {
-  c->state_is_time_n = false;
+  state_left_time_n(c);
   const double alpha[4] = {0.25, 1.0 / 3.0, 0.5, 1.0};   // procBlock.cpp:938
   const size_t nb = c->blocks.size();
-  // blocks whose norms sit in prepare's slots of norm_out, [2 nb + 64, 3 nb + 64)
+  // blocks whose norms sit in prepare's region of norm_out
   std::vector<size_t> from_prepare;
   if (mode != 2 && c->fused_pending) {
     // the marching kernel already advanced the state into the second buffer
@@ -1145,7 +1181,7 @@ int update_pass(agx_ctx* c, int mode, int mm, double* l2, agx_linf* linf) {
       BlockDev& b = c->blocks[n].d;
       const MarchPlan mp = march_plan(c, b);
       hipLaunchKernelGGL(k_norm_final, dim3(1), dim3(256), 0, c->stream,
-                         c->partials.get() + off, mp.nparts, c->norm_out.get() + n);
+                         c->partials.get() + off, mp.nparts, c->norm_update() + n);
       off += mp.nparts;
       for (int e = 0; e < AGX_NEQ; ++e) std::swap(b.state[e], b.state2[e]);
     }
@@ -1164,18 +1200,15 @@ int update_pass(agx_ctx* c, int mode, int mm, double* l2, agx_linf* linf) {
         // the D2 state of the next prepare from here (AGX_D2_STATE); the norms from
         // k_lusgs_prepare where it folded those of this residual (AGX_RESID_NORMS)
         const bool ws = c->d2_state_update, pn = blk.resid_norms_current;
-#define AGX_UPD_D2(W, N)                                                                  \
-  hipLaunchKernelGGL((k_update_d2<W, N>), tg, dim3(256), 0, c->stream, b, c->gas, c->sp, \
-                     last, c->partials.get())
-        if (ws && pn) AGX_UPD_D2(1, 0);
-        else if (ws) AGX_UPD_D2(1, 1);
-        else if (pn) AGX_UPD_D2(0, 0);
-        else AGX_UPD_D2(0, 1);
-#undef AGX_UPD_D2
-        blk.d2_state_current = ws;
+        by_bool(ws, [&](auto write_s) {
+          by_bool(pn, [&](auto from_prep) {     // (NORMS: the update folds them itself)
+            hipLaunchKernelGGL((k_update_d2<decltype(write_s)::value, !from_prep>), tg, dim3(256),
+                               0, c->stream, b, c->gas, c->sp, last, c->partials.get());
+          });
+        });
+        state_updated_d2(blk, ws);
         if (pn) {
-          // (one use: a second update on the same residual reads it itself)
-          blk.resid_norms_current = false;
+          resid_norms_used(blk);
           from_prepare.push_back(n);
         } else if (reduce_norms(c, n, (long)tg.x * tg.y * tg.z)) {
           return 1;
@@ -1183,7 +1216,7 @@ int update_pass(agx_ctx* c, int mode, int mm, double* l2, agx_linf* linf) {
         continue;
       }
 #endif
-      blk.d2_state_current = false;
+      state_written(blk);
       const dim3 grid = cell_grid(b, CELL_BLOCK);
       hipLaunchKernelGGL(k_update, grid, CELL_BLOCK, 0, c->stream, b, c->gas,
                          c->sp, mode, mode == 1 ? alpha[mm & 3] : 1.0, last,
@@ -1193,20 +1226,17 @@ int update_pass(agx_ctx* c, int mode, int mm, double* l2, agx_linf* linf) {
   }
   // the same layout either way: every block's norms from prepare's slots, or from the
   // update's (a mix -- an upload into one block between the two -- is gathered there first)
-  const NormPartial* norm_src = c->norm_out.get();
-  if (from_prepare.size() == nb && nb > 0) norm_src += 2 * nb + 64;
+  const NormPartial* norm_src = c->norm_update();
+  if (from_prepare.size() == nb && nb > 0) norm_src = c->norm_prepare();
   else
     for (size_t n : from_prepare)
-      HIPCHK(hipMemcpyAsync(c->norm_out.get() + n, c->norm_out.get() + 2 * nb + 64 + n,
-                            sizeof(NormPartial), hipMemcpyDeviceToDevice, c->stream));
-  HIPCHK(hipMemcpyAsync(c->norm_host.get(), norm_src,
-                        sizeof(NormPartial) * c->blocks.size(),
+      HIPCHK(hipMemcpyAsync(c->norm_update() + n, c->norm_prepare() + n, sizeof(NormPartial),
+                            hipMemcpyDeviceToDevice, c->stream));
+  HIPCHK(hipMemcpyAsync(c->host_update(), norm_src, sizeof(NormPartial) * nb,
                         hipMemcpyDeviceToHost, c->stream));
   if (c->mres_deferred)
-    HIPCHK(hipMemcpyAsync(c->norm_host.get() + c->blocks.size(),
-                          c->norm_out.get() + c->blocks.size() + 64,
-                          sizeof(NormPartial) * c->blocks.size(), hipMemcpyDeviceToHost,
-                          c->stream));
+    HIPCHK(hipMemcpyAsync(c->host_mres(), c->norm_mres(), sizeof(NormPartial) * nb,
+                          hipMemcpyDeviceToHost, c->stream));
   HIPCHK(hipMemcpyAsync(c->err_host.get(), c->err_dev.get(), sizeof(int),
                         hipMemcpyDeviceToHost, c->stream));
   if (c->in_iterate && c->eager_ghosts) {
@@ -1215,14 +1245,14 @@ int update_pass(agx_ctx* c, int mode, int mm, double* l2, agx_linf* linf) {
     if (!c->norm_event) HIPCHK(hipEventCreateWithFlags(&c->norm_event, hipEventDisableTiming));
     HIPCHK(hipEventRecord(c->norm_event, c->stream));
     if (fill_ghosts(c)) return 1;
-    c->ghosts_prefilled = true;
+    ghosts_filled_ahead(c);
     HIPCHK(hipEventSynchronize(c->norm_event));
   } else {
     HIPCHK(hipStreamSynchronize(c->stream));   // the one sync per iteration
   }
   if (check_device_error(c)) return 1;
   for (size_t n = 0; n < c->blocks.size(); ++n) {
-    const NormPartial& p = c->norm_host.get()[n];
+    const NormPartial& p = c->host_update()[n];
     const BlockDev& b = c->blocks[n].d;
     for (int e = 0; e < AGX_NEQ; ++e) l2[e] += p.l2[e];
     if (p.vmax > linf->linf) {           // procBlock.cpp:863-866
@@ -1617,65 +1647,21 @@ int agx_ctx_create(int device, int rank, agx_ctx** out) {
                 "path", hipGetErrorString(e));
   if (device < 0 || device >= ndev) return fail("device %d out of range", device);
   HIPCHK(hipSetDevice(device));
-  agx_ctx* c = new agx_ctx();
+  // (the half-built context goes with every failing return)
+  std::unique_ptr<agx_ctx> c(new agx_ctx());
   c->device = device;
   c->rank = rank;
-  if (const char* kn = getenv("AGX_KERNEL")) {
-    c->use_gather = !strcmp(kn, "gather");
-    c->use_tile = !strcmp(kn, "tile");
-  }
-  c->allow_fuse = !(getenv("AGX_NO_FUSE") && atoi(getenv("AGX_NO_FUSE")) != 0);
-  {
-    int ncu = 0;
-    HIPCHK(hipDeviceGetAttribute(&ncu, hipDeviceAttributeMultiprocessorCount, device));
-    if (ncu > 0) c->num_cu = ncu;
-    if (const char* w = getenv("AGX_WORKGROUPS")) c->num_cu = std::max(1, atoi(w));
-    if (const char* w = getenv("AGX_VISC")) {
-      c->visc_gather = !strcmp(w, "gather");
-      c->visc_march = !strcmp(w, "march");
-    }
-    if (const char* w = getenv("AGX_TILE_ORDER")) {
-      if (strcmp(w, "step") && strcmp(w, "column")) {
-        delete c;
-        return fail("AGX_TILE_ORDER is '%s': step or column", w);
-      }
-      c->tile_order_inv = c->tile_order_visc = !strcmp(w, "step") ? TILE_ORDER_STEP : TILE_ORDER_COLUMN;
-    }
-    if (const char* w = getenv("AGX_EAGER_GHOSTS")) c->eager_ghosts = atoi(w) != 0;
-    if (const char* w = getenv("AGX_OVERLAP")) c->overlap = atoi(w) != 0;
-    if (const char* w = getenv("AGX_LUSGS")) c->lusgs_mode = !strcmp(w, "plane") ? 0 : 1;
-    if (const char* w = getenv("AGX_SPIN_LIMIT")) c->spin_limit = std::max(1, atoi(w));
-    if (const char* w = getenv("AGX_GRAPHS")) c->use_graphs = atoi(w) != 0;
-    if (const char* w = getenv("AGX_SWEEP_ALL")) c->sweep_all_launch = atoi(w) != 0;
-    if (const char* w = getenv("AGX_SWEEP_PIPE")) c->sweep_pipe = atoi(w) != 0;
-    if (const char* w = getenv("AGX_SWEEP_THREE")) c->sweep_three = atoi(w) != 0;
-    if (const char* w = getenv("AGX_SWEEP_RECORDS")) c->sweep_records = atoi(w) != 0;
-    if (const char* w = getenv("AGX_MRESID_SPLIT")) c->mresid_split = std::min(64, std::max(1, atoi(w)));
-    if (const char* w = getenv("AGX_MRESID")) c->mresid_march = strcmp(w, "plane") != 0;
-    if (const char* w = getenv("AGX_D2_STATE")) {
-      if (strcmp(w, "update") && strcmp(w, "prepare")) {
-        delete c;
-        return fail("AGX_D2_STATE is '%s': update or prepare", w);
-      }
-      c->d2_state_update = !strcmp(w, "update");
-    }
-    if (const char* w = getenv("AGX_RESID_NORMS")) {
-      if (strcmp(w, "prepare") && strcmp(w, "update")) {
-        delete c;
-        return fail("AGX_RESID_NORMS is '%s': prepare or update", w);
-      }
-      c->resid_norms_prepare = !strcmp(w, "prepare");
-    }
-    if (const char* w = getenv("AGX_HALO_BATCH")) {   // 0: a launch pair per connection; require:
-      c->halo_batch = strcmp(w, "0") != 0;            // finalize fails where no batch forms
-      c->halo_batch_required = !strcmp(w, "require");
-    }
-  }
+  if (const BadSwitch bad = parse_switches(getenv, *c)) return fail("%s", bad.message().c_str());
+  static_assert(TILE_ORDER_STEP == 1 && TILE_ORDER_COLUMN == 0, "AGX_TILE_ORDER's table values");
+  int ncu = 0;
+  HIPCHK(hipDeviceGetAttribute(&ncu, hipDeviceAttributeMultiprocessorCount, device));
+  if (ncu > 0) c->num_cu = ncu;
+  if (c->workgroups > 0) c->num_cu = c->workgroups;
   HIPCHK(c->err_dev.alloc(1));
   HIPCHK(hipMemset(c->err_dev.get(), 0, sizeof(int)));
   HIPCHK(c->err_host.alloc(1));
   *c->err_host.get() = 0;
-  *out = c;
+  *out = c.release();
   return 0;
 }
 
@@ -2352,20 +2338,15 @@ int agx_setup_finalize(agx_ctx* c) {
   }
   c->n_partials = max_parts;
   HIPCHK(c->partials.alloc((size_t)max_parts));
-  const size_t nb = std::max<size_t>(c->blocks.size(), 1);
-  // [0, nb): norms of the update; [nb, nb + 64): scratch of the two-level fold;
-  // [nb + 64, 2 nb + 64): the matrix residual (read back with the update's norms);
-  // [2 nb + 64, 3 nb + 64): the residual norms k_lusgs_prepare folds (the matrix residual of
-  // the phase API lands in [0, nb) between prepare and update)
-  HIPCHK(c->norm_out.alloc(3 * nb + 64));
-  HIPCHK(c->norm_host.alloc(2 * nb));
+  // (the regions of both: agx_ctx::norm_update() ... host_end())
+  HIPCHK(c->norm_out.alloc((size_t)(c->norm_end() - c->norm_update())));
+  HIPCHK(c->norm_host.alloc((size_t)(c->host_end() - c->host_update())));
   c->finalized = true;
   return 0;
 }
 
 int agx_state_upload(agx_ctx* c, int id, const double* state) {
-  c->ghosts_prefilled = false;
-  c->state_is_time_n = false;
+  field_written_by_caller(c);
   if (flush_consn(c)) return 1;
   if (id < 0 || id >= (int)c->blocks.size()) return fail("bad block id %d", id);
   Block& b = c->blocks[id];
@@ -2418,7 +2399,7 @@ static int geom_field_info(Block& b, int field, double* const** p, int* ncomp, i
 // x of the D2 LU-SGS path <-> the SoA planes the field transfers use
 static int d2_x_copy(agx_ctx* c, Block& b, int to_d2) {
 #if AGX_FAST
-  b.x_planes_current = true;
+  x_planes_copied(b);
   const long n = (long)b.d.d2.Pi * b.d.d2.Pj * (b.d.nk + 2 * b.d.ng);
   hipLaunchKernelGGL(k_d2_x_copy, dim3((n + 255) / 256), dim3(256), 0, c->stream, b.d, to_d2,
                      to_d2 ? (unsigned)(++b.kp_epoch) & 3u : 0u);
@@ -2450,7 +2431,7 @@ static int ghosts_for_output(agx_ctx* c, const char* who) {
     if (bc_pass(c, true, 2)) return 1;     // (2: the stored wall-law data stay the last residual's)
     if (bc_pass(c, false, 1)) return 1;
   }
-  c->ghosts_prefilled = false;   // (the next iteration starts from its own inviscid fill)
+  ghost_fill_gone(c);   // (the next iteration starts from its own inviscid fill)
   return 0;
 }
 
@@ -2759,8 +2740,7 @@ int agx_field_upload(agx_ctx* c, int id, int field, const double* in) {
   // (an upload of x writes this block's planes and, on the D2 path, copies them to its D2
   // arrays below: the planes of this block are current afterwards, those of the other blocks
   // are what they were)
-  c->ghosts_prefilled = false;
-  c->state_is_time_n = false;
+  field_written_by_caller(c);
   if (flush_consn(c)) return 1;
   if (id < 0 || id >= (int)c->blocks.size()) return fail("bad block id %d", id);
   Block& b = c->blocks[id];
@@ -2771,18 +2751,12 @@ int agx_field_upload(agx_ctx* c, int id, int field, const double* in) {
   if (field_info(b, field, &p, &nc, &gh)) return fail("field %d cannot be uploaded", field);
   const int g = gh ? b.d.ng : 0;
   if (upload_aos(c, b, in, p, nc, b.d.ni + 2 * g, b.d.nj + 2 * g, b.d.nk + 2 * g, g)) return 1;
-  if (field == AGX_FIELD_UPDATE) b.x_is_zero = false;
+  if (field == AGX_FIELD_UPDATE) x_uploaded(b);
   if (field == AGX_FIELD_UPDATE && b.d.d2.base) return d2_x_copy(c, b, 1);
   return 0;
 }
 
 // ---- geometric multigrid (include/aither_gfx950.h) -------------------------------------------
-static int implicit_begin(agx_ctx* c, int write_x);
-int agx_phase_matrix_residual(agx_ctx* c, double* mr);
-static int d2_x_copy(agx_ctx* c, Block& b, int to_d2);
-#if AGX_FAST
-static int d2_prepare(agx_ctx* c, Block& blk, int write_x, int again, int norms);
-#endif
 namespace {
 int mg_solver_ok(agx_ctx* c) {
   if (!c->sp.implicit) return fail("multigrid: implicit time integration only");
@@ -2888,8 +2862,7 @@ int agx_mg_restrict(agx_ctx* f, agx_ctx* cz, int blk, int what, const int32_t* t
   if (what != AGX_MG_FORCING && !vf) return fail("mg_restrict: volume weights missing");
   if (flush_consn(f) || flush_consn(cz)) return 1;
   // (AGX_MG_STATE writes the coarse block's state planes; the other selectors leave them)
-  bc.d2_state_current = false;
-  bc.resid_norms_current = false;
+  planes_uploaded(bc);
   MgMap m;
   if (mg_maps(f, bf, tc, vf, nullptr, bc.d.ni, bc.d.nj, bc.d.nk, &m)) return 1;
   if (what == AGX_MG_UPDATE && mg_x_to_planes(f, bf)) return 1;
@@ -2899,8 +2872,7 @@ int agx_mg_restrict(agx_ctx* f, agx_ctx* cz, int blk, int what, const int32_t* t
     // (coarse.Zero(): ghost cells included, procBlock.hpp:641)
     for (int e = 0; e < AGX_NEQ; ++e)
       HIPCHK(hipMemsetAsync(bc.d.state[e], 0, sizeof(double) * bc.d.nplane, cz->stream));
-    cz->ghosts_prefilled = false;
-    cz->state_is_time_n = false;
+    field_written_by_caller(cz);
     cz->mg_coarse = true;
   } else if (what == AGX_MG_UPDATE) {
     for (int e = 0; e < AGX_NEQ; ++e)
@@ -2997,17 +2969,12 @@ int agx_mg_prolong(agx_ctx* cz, agx_ctx* f, int blk, const int32_t* tc, const do
 int agx_store_time_n(agx_ctx* c, int also_nm1) {
   if (flush_consn(c)) return 1;
   c->have_time_n = true;
-  // nonreflecting ghost states read consVarsN (ghostStates.cpp:435-462): a ghost fill
-  // queued behind the last update saw the old time level
-  for (auto& blk : c->blocks)
-    if (blk.nr_max > 0) c->ghosts_prefilled = false;
+  state_became_time_n(c);
   // Explicit fused path: the stage-0 launch of k_residual_tile forms
   // cons(state) anyway and writes it to consVarsN itself (5 stores instead of a
   // separate 5-load/5-store pass); anything else that touches consVarsN or the
-  // state first calls flush_consn().
-  static const bool lazy = !(getenv("AGX_NO_LAZY_CONSN") && atoi(getenv("AGX_NO_LAZY_CONSN")));
-  c->state_is_time_n = true;
-  if (lazy && !also_nm1 && !c->use_gather && all_tile_ok(c)) { c->consn_pending = true; return 0; }
+  // state first calls flush_consn().  (AGX_NO_LAZY_CONSN: always the pass of its own)
+  if (!c->no_lazy_consn && !also_nm1 && !c->use_gather && all_tile_ok(c)) { c->consn_pending = true; return 0; }
   for (auto& blk : c->blocks)
     hipLaunchKernelGGL(k_store_time_n, cell_grid(blk.d, CELL_BLOCK), CELL_BLOCK,
                        0, c->stream, blk.d, c->gas, also_nm1);
@@ -3047,7 +3014,7 @@ int agx_phase_residual(agx_ctx* c, int mm, double cfl) {
       const double rk_alpha[4] = {0.25, 1.0 / 3.0, 0.5, 1.0};   // procBlock.cpp:938
       ma.alpha = rk_alpha[mm & 3];
       ma.partials = c->partials.get() + off;
-      ma.ablate = getenv("AGX_ABLATE") ? atoi(getenv("AGX_ABLATE")) : 0;
+      ma.ablate = c->ablate;      // (0 unless this is a -DAGX_ABLATION build: AGX_ABLATE)
       ma.plan = mp.tile;
       launch_inv(c, blk.d, cfl, fuse, ma, mp);
       off += mp.nparts;
@@ -3130,18 +3097,13 @@ int agx_phase_residual(agx_ctx* c, int mm, double cfl) {
                                          c->tile_order_visc);
         // (largeEddySimulation: the instantiations with the WALE arm, which also write the
         // run's eddy-viscosity plane)
-        if (c->sp.les && fourth)
-          hipLaunchKernelGGL((k_visc_tile<true, true>), dim3(nwg), dim3(VT_L, VT_R), 0, c->stream,
-                             make_slab(vb), c->gas, c->sp, cfl, gx, tp);
-        else if (c->sp.les)
-          hipLaunchKernelGGL((k_visc_tile<false, true>), dim3(nwg), dim3(VT_L, VT_R), 0, c->stream,
-                             make_slab(vb), c->gas, c->sp, cfl, gx, tp);
-        else if (fourth)
-          hipLaunchKernelGGL(k_visc_tile<true>, dim3(nwg), dim3(VT_L, VT_R), 0, c->stream,
-                             make_slab(vb), c->gas, c->sp, cfl, gx, tp);
-        else
-          hipLaunchKernelGGL(k_visc_tile<false>, dim3(nwg), dim3(VT_L, VT_R), 0, c->stream,
-                             make_slab(vb), c->gas, c->sp, cfl, gx, tp);
+        by_bool(c->sp.les != 0, [&](auto les) {
+          by_bool(fourth, [&](auto f4) {
+            hipLaunchKernelGGL((k_visc_tile<f4, decltype(les)::value>), dim3(nwg),
+                               dim3(VT_L, VT_R), 0, c->stream, make_slab(vb), c->gas, c->sp, cfl,
+                               gx, tp);
+          });
+        });
 #endif
       }
     }
@@ -3172,7 +3134,6 @@ int agx_phase_explicit_update(agx_ctx* c, int mm, double* l2, agx_linf* linf) {
   return update_pass(c, mode, mm, l2, linf);
 }
 
-static int implicit_begin(agx_ctx* c, int write_x);
 #if AGX_FAST
 // k_lusgs_prepare of one block (write_x: a launch that writes x is a writer launch: it tags
 // the values and advances the epoch)
@@ -3186,19 +3147,17 @@ static int d2_prepare(agx_ctx* c, Block& blk, int write_x, int again, int norms)
   int ghost_s = 0;
   for (int q = 0; q < 6; ++q) ghost_s |= b.side_conn[q] != 0;
   const unsigned tag = write_x ? (unsigned)(++blk.kp_epoch) & 3u : 0u;
-#define AGX_PREP(L, N)                                                                       \
-  hipLaunchKernelGGL((k_lusgs_prepare<L, N>), grid, dim3(256), 0, c->stream, b, c->gas, c->sp, \
-                     write_x, tag, again, ghost_s, c->partials.get())
-  if (lean && norms) AGX_PREP(1, 1);
-  else if (lean) AGX_PREP(1, 0);
-  else if (norms) AGX_PREP(0, 1);
-  else AGX_PREP(0, 0);
-#undef AGX_PREP
+  by_bool(lean, [&](auto is_lean) {
+    by_bool(norms != 0, [&](auto with_norms) {
+      hipLaunchKernelGGL((k_lusgs_prepare<decltype(is_lean)::value, with_norms>), grid, dim3(256),
+                         0, c->stream, b, c->gas, c->sp, write_x, tag, again, ghost_s,
+                         c->partials.get());
+    });
+  });
   if (norms) {
-    const size_t n = (size_t)(&blk - c->blocks.data()), nb = c->blocks.size();
-    if (reduce_norms(c, n, (long)grid.x * grid.y * grid.z, c->norm_out.get() + 2 * nb + 64 + n))
-      return 1;
-    blk.resid_norms_current = true;
+    const size_t n = (size_t)(&blk - c->blocks.data());
+    if (reduce_norms(c, n, (long)grid.x * grid.y * grid.z, c->norm_prepare() + n)) return 1;
+    resid_norms_folded(blk);
   }
   return 0;
 }
@@ -3221,7 +3180,7 @@ static int implicit_begin(agx_ctx* c, int write_x) {
       // (the norms ride along on the finest level's launch only: a coarse multigrid level,
       // write_x = 0, keeps the update's fold)
       if (d2_prepare(c, blk, wx, 0, write_x && c->resid_norms_prepare ? 1 : 0)) return 1;
-      blk.x_is_zero = write_x && !wx;
+      x_prepared(blk, write_x && !wx);
       continue;
     }
 #endif
@@ -3240,31 +3199,36 @@ static int implicit_begin(agx_ctx* c, int write_x) {
   return 0;
 }
 
+// k_dplur of one block, in the solver mode's form (solver_mode_of, agx_kernels.hpp); waits:
+// the faces whose cells dplur_sweep_overlapped leaves to k_dplur_shell
+static void launch_dplur(agx_ctx* c, const BlockDev& b, int waits) {
+  by_int<0, 1, 2>(solver_mode_of(c->sp), [&](auto mode) {
+    hipLaunchKernelGGL(k_dplur<mode>, cell_grid(b, CELL_BLOCK), CELL_BLOCK, 0, c->stream, b,
+                       c->gas, c->sp, waits);
+  });
+}
+
 int agx_phase_relax_forward(agx_ctx* c, int sweep) {
   x_changed(c);
-  for (auto& blk : c->blocks) blk.x_is_zero = false;
+  x_swept(c);
   Timer t(c, G_SWEEP);
   const int full = sweep > 0 || c->sp.requires_init;
-  bool swept = false;
   if (is_lusgs_solver(c) && pipe_sweep_applicable(c)) return lusgs_sweep_pipe(c, true, full);
   if (is_lusgs_solver(c) && plane_sweep_all_applicable(c)) return lusgs_sweep_all(c, true, full);
   for (auto& blk : c->blocks) {
     BlockDev& b = blk.d;
     if (is_lusgs_solver(c)) {
       if (lusgs_sweep(c, blk, true, full)) return 1;
-      swept = true;
     } else {
       // dplur::DPLUR copies x to xold (linearSolver.cpp:487) and relaxes from the
       // copy; here the two sets of planes change roles instead.  Ghost cells of
       // the new x that nobody rewrites (physical boundaries) are never read
       // (ImplicitLower/Upper only cross physical or connection faces).
       for (int e = 0; e < AGX_NEQ; ++e) std::swap(b.x[e], b.xold[e]);
-      AGX_BY_MODE(c->sp, k_dplur, cell_grid(b, CELL_BLOCK), CELL_BLOCK, c->stream, b, c->gas,
-                  c->sp, 0);
+      launch_dplur(c, b, 0);
     }
   }
   if (!is_lusgs_solver(c)) c->halo_set[AGX_HALO_UPDATE] ^= 1;   // (x and xold changed roles)
-  (void)swept;
   HIPCHK(hipGetLastError());
   return 0;
 }
@@ -3299,7 +3263,7 @@ void matrix_residual_fold(agx_ctx* c, const NormPartial* host, double* mr) {
 
 int agx_phase_matrix_residual(agx_ctx* c, double* mr) {
   const bool defer = c->in_iterate;      // agx_iterate reads it back with the update's norms
-  NormPartial* out = c->norm_out.get() + (defer ? c->blocks.size() + 64 : 0);
+  NormPartial* out = defer ? c->norm_mres() : c->norm_update();
   {
     Timer t(c, G_MRESID);
     for (size_t n = 0; n < c->blocks.size(); ++n) {
@@ -3319,8 +3283,10 @@ int agx_phase_matrix_residual(agx_ctx* c, double* mr) {
       }
 #endif
       const dim3 grid = cell_grid(b, CELL_BLOCK);
-      AGX_BY_MODE(c->sp, k_matrix_resid, grid, CELL_BLOCK, c->stream, b, c->gas, c->sp,
-                  c->partials.get());
+      by_int<0, 1, 2>(solver_mode_of(c->sp), [&](auto mode) {
+        hipLaunchKernelGGL(k_matrix_resid<mode>, grid, CELL_BLOCK, 0, c->stream, b, c->gas, c->sp,
+                           c->partials.get());
+      });
       if (reduce_norms(c, n, (long)grid.x * grid.y * grid.z, out + n)) return 1;
     }
   }
@@ -3329,11 +3295,11 @@ int agx_phase_matrix_residual(agx_ctx* c, double* mr) {
     *mr = 0.0;
     return 0;
   }
-  HIPCHK(hipMemcpyAsync(c->norm_host.get(), c->norm_out.get(),
+  HIPCHK(hipMemcpyAsync(c->host_update(), c->norm_update(),
                         sizeof(NormPartial) * c->blocks.size(),
                         hipMemcpyDeviceToHost, c->stream));
   HIPCHK(hipStreamSynchronize(c->stream));
-  matrix_residual_fold(c, c->norm_host.get(), mr);
+  matrix_residual_fold(c, c->host_update(), mr);
   return 0;
 }
 
@@ -3405,7 +3371,7 @@ int agx_halo_pack(agx_ctx* c, int id, int what, double* dev_buf) {
 }
 int agx_halo_unpack(agx_ctx* c, int id, int what, const double* dev_buf) {
   if (what == AGX_HALO_UPDATE) x_changed(c);
-  c->ghosts_prefilled = false;
+  ghost_fill_gone(c);
   if (id < 0 || id >= (int)c->conns.size()) return fail("bad connection id");
   Conn& k = c->conns[id];
   const int s = my_side(c, k);
@@ -3473,7 +3439,6 @@ int agx_rccl_exchange_create(agx_ctx* c, const void* id128, int nranks, int rank
   return 0;
 }
 
-static int halo_exchange_remote(agx_ctx* c, int what);
 // gridLevel::GetBoundaryConditions (state) / lusgs::Relax, dplur::Relax (update):
 // local connections, then the slabs of connections to other ranks
 int agx_halo_exchange(agx_ctx* c, int what) {
@@ -3541,8 +3506,7 @@ static int dplur_sweep_overlapped(agx_ctx* c) {
     for (size_t n = 0; n < c->blocks.size(); ++n) {
       BlockDev bs = c->blocks[n].d;      // x and xold in the roles they take in this sweep
       for (int e = 0; e < AGX_NEQ; ++e) std::swap(bs.x[e], bs.xold[e]);
-      AGX_BY_MODE(c->sp, k_dplur, cell_grid(bs, CELL_BLOCK), CELL_BLOCK, c->stream, bs, c->gas,
-                  c->sp, waits[n]);
+      launch_dplur(c, bs, waits[n]);
     }
     HIPCHK(hipGetLastError());
   }
@@ -3564,8 +3528,10 @@ static int dplur_sweep_overlapped(agx_ctx* c) {
       for (int e = 0; e < AGX_NEQ; ++e) std::swap(b.x[e], b.xold[e]);
       if (!waits[n]) continue;
       const long nface = std::max({(long)b.ni * b.nj, (long)b.ni * b.nk, (long)b.nj * b.nk});
-      AGX_BY_MODE(c->sp, k_dplur_shell, dim3((unsigned)((nface + 255) / 256), 6), dim3(256),
-                  c->stream, b, c->gas, c->sp, waits[n]);
+      by_int<0, 1, 2>(solver_mode_of(c->sp), [&](auto mode) {
+        hipLaunchKernelGGL(k_dplur_shell<mode>, dim3((unsigned)((nface + 255) / 256), 6),
+                           dim3(256), 0, c->stream, b, c->gas, c->sp, waits[n]);
+      });
     }
     HIPCHK(hipGetLastError());
   }
@@ -3659,7 +3625,7 @@ int agx_iterate(agx_ctx* c, int mm, double cfl, double* l2, agx_linf* linf,
   // gridLevel::GetBoundaryConditions gridLevel.cpp:287-319 (already done behind the
   // previous call's norm read-back unless something touched the state since)
   if (!c->ghosts_prefilled && fill_ghosts(c)) return 1;
-  c->ghosts_prefilled = false;
+  ghost_fill_gone(c);
   struct Scope { agx_ctx* c; ~Scope() { c->in_iterate = false; } } scope{c};
   c->in_iterate = true;
   // gridLevel::CalcResidual :372-400 + CalcTimeStep :240-247
@@ -3695,7 +3661,7 @@ int agx_iterate(agx_ctx* c, int mm, double cfl, double* l2, agx_linf* linf,
     AGX_PHASE(agx_phase_matrix_residual(c, matrix_resid));
     AGX_PHASE(agx_phase_implicit_update(c, mm, l2, linf));
     if (!st && c->mres_deferred)      // came back with the update's norms
-      matrix_residual_fold(c, c->norm_host.get() + c->blocks.size(), matrix_resid);
+      matrix_residual_fold(c, c->host_mres(), matrix_resid);
     c->mres_deferred = false;
   } else {
     AGX_PHASE(agx_phase_explicit_update(c, mm, l2, linf));

@@ -4,14 +4,13 @@ forcing term through the public calls only -- Solver.upload / download of `state
 and `residual`, mg_restrict, mg_save_update, mg_prolong, mg_matrix_residual -- against the
 numpy restatement of tests/mg_ref.py.  Every check returns its worst figure in units of its
 bound."""
-import contextlib
 import ctypes as C
 import functools
-import os
 
 import numpy as np
 
 import mg_ref
+from parity_utils import switches
 from aither_amd import abi
 from aither_amd.case import builder, multigrid, synthetic
 from aither_amd.case.inputfile import Surface
@@ -85,25 +84,11 @@ def levels(path, shape):
     return cases, trs
 
 
-@contextlib.contextmanager
-def _env(env):
-    old = {k: os.environ.get(k) for k in env}
-    os.environ.update(env)
-    try:
-        yield
-    finally:
-        for k, v in old.items():
-            if v is None:
-                os.environ.pop(k, None)
-            else:
-                os.environ[k] = v
-
-
 def open_levels(api, path, shape):
     """A MultigridSolver over the two levels (the AGX_* switches are read when a context is
     created; the environment is restored afterwards)."""
     cases, trs = levels(path, shape)
-    with _env(PATHS[path][1]):
+    with switches(PATHS[path][1]):
         return MultigridSolver(api, cases, trs)
 
 

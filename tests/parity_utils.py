@@ -1,4 +1,7 @@
 """Shared helpers for the parity tests (HIP path vs CPU oracle)."""
+import contextlib
+import os
+
 import numpy as np
 
 from aither_amd.solver import Solver
@@ -10,6 +13,23 @@ MATRIX_RTOL = 1.0e-6   # cap of the bound run_pair DERIVES per case (matrix_tole
                        # 5e-9 .. 1e-7 for the synthetic decks, cancellation factors 12 .. 270)
 MATRIX_FLOOR = 1.0e-14  # below this the matrix residual of a converged / uniform state
                         # is the round-off of O(1) operands
+
+
+@contextlib.contextmanager
+def switches(env=None, **more):
+    """The AGX_* switches `env` (a dict, and / or keywords) in os.environ for the body -- they
+    are read when a context is created -- and the environment as it was afterwards."""
+    env = dict(env or {}, **more)
+    old = {k: os.environ.get(k) for k in env}
+    os.environ.update(env)
+    try:
+        yield
+    finally:
+        for k, v in old.items():
+            if v is None:
+                os.environ.pop(k, None)
+            else:
+                os.environ[k] = v
 
 
 def matrix_tolerance(so):

@@ -1,30 +1,14 @@
 """Lifetime of what a context owns on the device (csrc/agx_mem.hpp): replacing a block's
 boundary surfaces leaves a context that computes what a fresh one does, and contexts that
 come and go give their memory back."""
-import contextlib
-import os
 
 import numpy as np
 import pytest
 
+from parity_utils import switches
 from aither_amd.case import builder as _b
 from aither_amd.case import synthetic
 from aither_amd.solver import Solver
-
-
-@contextlib.contextmanager
-def _env(**env):
-    """AGX_* switches are read when a context is created."""
-    old = {k: os.environ.get(k) for k in env}
-    os.environ.update(env)
-    try:
-        yield
-    finally:
-        for k, v in old.items():
-            if v is None:
-                os.environ.pop(k, None)
-            else:
-                os.environ[k] = v
 
 
 def _two_iterations(s):
@@ -48,7 +32,7 @@ def test_set_bcs_again_equals_a_fresh_context(agx, env):
                                        equation_set="navierStokes",
                                        time_integration="implicitEuler", matrix_solver="lusgs",
                                        cfl=5.0)
-    with _env(**env):
+    with switches(**env):
         fresh, again = Solver(agx, case), Solver(agx, case)
     try:
         ref_hist, ref_state = _two_iterations(fresh)

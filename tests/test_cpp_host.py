@@ -95,6 +95,21 @@ def test_memory_owners_free_exactly_once():
     assert b"host_mem OK" in r.stdout
 
 
+def test_switch_table_defaults_words_and_design_rows():
+    """tests/cpp/host_switches.cpp: the one table of csrc/agx_switches.hpp parsed from a map,
+    built with the address and undefined-behaviour sanitizers -- every entry's default is
+    what a context always started with, every accepted word of every word switch gives its
+    members, any other word is refused with the variable's name and the accepted words, flags
+    and counts keep atoi semantics and their clamps, and the switch table of DESIGN.md
+    section 4 has the same variables, one row each."""
+    subprocess.check_call(["make", "-C", CPP, "host_switches"], stdout=subprocess.DEVNULL)
+    r = subprocess.run([os.path.join(CPP, "host_switches"),
+                        os.path.join(HERE, "..", "DESIGN.md")], stdout=subprocess.PIPE,
+                       stderr=subprocess.STDOUT, timeout=120)
+    assert r.returncode == 0, r.stdout.decode()
+    assert b"host_switches OK" in r.stdout
+
+
 CASES = {
     "rk4_muscl_roe": dict(n=(20, 9, 8), stretch=1.15, skew=0.01, time_integration="rk4",
                           cfl=0.5),

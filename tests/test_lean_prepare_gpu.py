@@ -14,11 +14,11 @@ two 20 x 18 x 6 blocks stacked along k.
 Run on a real MI355X:  python -m pytest tests -m gpu
 """
 import ctypes as C
-import os
 
 import numpy as np
 import pytest
 
+from parity_utils import switches
 from aither_amd import abi
 from aither_amd.case import synthetic
 from aither_amd.solver import PhasedSolver, Solver
@@ -46,16 +46,8 @@ def _single(amplitude=0.05, bcs=WALL, **over):
 
 def _solver(agx, case, env, cls=Solver, **kw):
     """A solver whose context was created under the given AGX_* switches."""
-    old = {k: os.environ.get(k) for k in env}
-    os.environ.update(env)
-    try:
+    with switches(env):
         return cls(agx, case, **kw)
-    finally:
-        for k, v in old.items():
-            if v is None:
-                os.environ.pop(k, None)
-            else:
-                os.environ[k] = v
 
 
 def _iterate(s, case, steps, first=0):

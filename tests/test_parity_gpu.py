@@ -10,7 +10,7 @@ import numpy as np
 import pytest
 
 from conftest import golden_case
-from parity_utils import run_pair, rel_err, assert_components, RTOL
+from parity_utils import run_pair, rel_err, assert_components, switches, RTOL
 from aither_amd.case import synthetic
 from aither_amd.solver import Solver
 
@@ -75,6 +75,49 @@ def test_free_running_explicit_with_time_n(agx, oracle, ti):
 
 
 @pytest.mark.gpu
+def test_unknown_switch_word_is_refused_at_create(agx):
+    """A word switch given a word it does not know fails agx_ctx_create by name -- the
+    variable, the word and the accepted words in agx_last_error -- before the context owns
+    anything on the device (the switches are parsed first: no allocation, no launch); a
+    context created afterwards with the variable unset runs."""
+    case = synthetic.single_block_case(n=(70, 9, 8), time_integration="rk4", cfl=0.5)
+    with switches(AGX_VISC="tiled"):
+        with pytest.raises(RuntimeError, match="AGX_VISC is 'tiled': tile, march or gather"):
+            Solver(agx, case)
+    msg = agx.last_error().decode()
+    assert "AGX_VISC" in msg and all(w in msg for w in ("tile", "march", "gather"))
+    assert "AGX_VISC" not in os.environ
+    s = Solver(agx, case)
+    out = s.step(0)
+    assert np.all(np.isfinite(out["l2"])) and np.all(out["l2"] > 0.0)
+    s.close()
+
+
+@pytest.mark.gpu
+def test_no_lazy_consn_is_read_per_context(agx):
+    """AGX_NO_LAZY_CONSN belongs to the context created under it: three contexts in one
+    process -- set, unset, set -- run the case of test_free_running_explicit_with_time_n.  The
+    first and third store consVarsN in a pass of their own, the second defers it into the
+    stage-0 launch (flushed by the download): the same doubles either way (both forms call
+    prim_to_cons on the same state), so every download is bit for bit the first context's."""
+    case = synthetic.single_block_case(n=(70, 9, 8), stretch=1.15, skew=0.01,
+                                       time_integration="rk4", cfl=0.5)
+    out = []
+    for env in ({"AGX_NO_LAZY_CONSN": "1"}, {}, {"AGX_NO_LAZY_CONSN": "1"}):
+        assert "AGX_NO_LAZY_CONSN" not in os.environ
+        with switches(env):
+            s = Solver(agx, case)
+        for nn in range(3):
+            s.step(nn)
+        s.store_time_n(3)
+        out.append({f: s.download(f, 0) for f in ("state", "cons_n", "residual", "dt")})
+        s.close()
+    for n in (1, 2):
+        for f, ref in out[0].items():
+            assert np.array_equal(out[n][f], ref), (n, f)
+
+
+@pytest.mark.gpu
 @pytest.mark.parametrize("perturb", [0.0, 0.05])
 def test_uniformflow_all_orientations_parity(agx, oracle, perturb):
     """Halo exchange over all eight patch orientations (the reference's
@@ -96,16 +139,8 @@ def test_uniformflow_all_orientations_parity(agx, oracle, perturb):
 def _run_with_env(agx, case, steps, env):
     """State after `steps` time steps with the given AGX_* switches (they are
     read when the context is created)."""
-    old = {k: os.environ.get(k) for k in env}
-    os.environ.update(env)
-    try:
+    with switches(env):
         s = Solver(agx, case)
-    finally:
-        for k, v in old.items():
-            if v is None:
-                os.environ.pop(k, None)
-            else:
-                os.environ[k] = v
     for nn in range(steps):
         s.step(nn)
     g = case.ng        # ghost cells hold whatever the last ghost fill left there
@@ -201,15 +236,8 @@ def test_matrix_residual_forms_agree(agx, kind):
         case = synthetic.stacked_blocks_case(n=(13, 9, 35), nblocks=2, axis="k", **kw)
     out = {}
     for form in ("march", "plane"):
-        old = os.environ.get("AGX_MRESID")
-        os.environ["AGX_MRESID"] = form
-        try:
+        with switches(AGX_MRESID=form):
             s = Solver(agx, case)
-        finally:
-            if old is None:
-                os.environ.pop("AGX_MRESID", None)
-            else:
-                os.environ["AGX_MRESID"] = old
         s.step(0), s.step(1)
         out[form] = [h["matrix"] for h in s.history]
         s.close()
@@ -225,15 +253,8 @@ def test_lusgs_spin_limit_error_path(agx, oracle):
     case = synthetic.single_block_case(n=(40, 36, 12), stretch=1.1,
                                        time_integration="implicitEuler",
                                        matrix_solver="lusgs", cfl=5.0)
-    old = os.environ.get("AGX_SPIN_LIMIT")
-    os.environ["AGX_SPIN_LIMIT"] = "1"
-    try:
+    with switches(AGX_SPIN_LIMIT="1"):
         s = Solver(agx, case)
-    finally:
-        if old is None:
-            os.environ.pop("AGX_SPIN_LIMIT", None)
-        else:
-            os.environ["AGX_SPIN_LIMIT"] = old
     with pytest.raises(RuntimeError, match="spin limit"):
         for nn in range(20):      # one poll is not always too few: repeat
             s.step(nn)
@@ -269,15 +290,8 @@ def test_batched_local_halo_exchange_is_bitwise_the_sequential_one(agx, kind):
     case = synthetic.cube_blocks_case(n=(9, 7, 6), splits=(2, 2, 2), **kw)
     out = {}
     for mode in ("require", "0"):
-        old = os.environ.get("AGX_HALO_BATCH")
-        os.environ["AGX_HALO_BATCH"] = mode
-        try:
+        with switches(AGX_HALO_BATCH=mode):
             s = Solver(agx, case)
-        finally:
-            if old is None:
-                os.environ.pop("AGX_HALO_BATCH", None)
-            else:
-                os.environ["AGX_HALO_BATCH"] = old
         for nn in range(2):
             s.step(nn)
         out[mode] = [s.download("state", gb) for gb in range(8)]
@@ -832,15 +846,8 @@ def test_pipelined_sweep_spin_limit_error_path_and_recovery(agx_rans):
     raises the error flag, every workgroup leaves, agx_iterate returns the error; the SAME
     context then sets its pipeline up afresh -- with a sane limit a fresh context gives the
     states of the launch-per-hyperplane form (wallLaw: two blocks, BLU-SGS)."""
-    old = os.environ.get("AGX_SPIN_LIMIT")
-    os.environ["AGX_SPIN_LIMIT"] = "1"
-    try:
+    with switches(AGX_SPIN_LIMIT="1"):
         s = Solver(agx_rans, golden_case("wallLaw"))
-    finally:
-        if old is None:
-            os.environ.pop("AGX_SPIN_LIMIT", None)
-        else:
-            os.environ["AGX_SPIN_LIMIT"] = old
     with pytest.raises(RuntimeError, match="spin limit"):
         for nn in range(20):
             s.step(nn)
@@ -881,16 +888,8 @@ def test_rans4_at_bench_size_against_the_simple_forms(agx_rans):
     assert case.n_eq == 7 and case.total_cells == 4 * 128 * 128 * 64
 
     def run(env, steps):
-        old = {k: os.environ.get(k) for k in env}
-        os.environ.update(env)
-        try:
+        with switches(env):
             s = Solver(agx_rans, case)
-        finally:
-            for k, v in old.items():
-                if v is None:
-                    os.environ.pop(k, None)
-                else:
-                    os.environ[k] = v
         for nn in range(steps):
             s.step(nn)
         hist = np.array([np.append(h["l2"], h["matrix"]) for h in s.history])
@@ -1153,16 +1152,8 @@ def test_multigrid_other_solvers_parity(agx, oracle, solver, env):
               matrix_solver=solver, matrix_sweeps=2, cfl=20.0)
     cg, tg = synthetic.multigrid_levels(**kw)
     co, to = synthetic.multigrid_levels(**kw)
-    old = {k: os.environ.get(k) for k in env}
-    os.environ.update(env)
-    try:
+    with switches(env):
         sg = MultigridSolver(agx, cg, tg)
-    finally:
-        for k, v in old.items():
-            if v is None:
-                os.environ.pop(k, None)
-            else:
-                os.environ[k] = v
     so = MultigridSolver(oracle, co, to)
     g = cg[0].ng
     for nn in range(3):
@@ -1194,16 +1185,8 @@ def test_multigrid_seven_equations_parity(agx_rans, oracle, solver, env):
               matrix_solver=solver, matrix_sweeps=2, cfl=10.0)
     cg, tg = synthetic.multigrid_levels(**kw)
     co, to = synthetic.multigrid_levels(**kw)
-    old = {k: os.environ.get(k) for k in env}
-    os.environ.update(env)
-    try:
+    with switches(env):
         sg = MultigridSolver(agx_rans, cg, tg)
-    finally:
-        for k, v in old.items():
-            if v is None:
-                os.environ.pop(k, None)
-            else:
-                os.environ[k] = v
     so = MultigridSolver(oracle, co, to)
     g = cg[0].ng
     for nn in range(3):

@@ -13,7 +13,6 @@ covering a branch.
 
 Run on a real MI355X:  python -m pytest tests -m gpu
 """
-import contextlib
 import gc
 import os
 import resource
@@ -22,7 +21,7 @@ import numpy as np
 import pytest
 
 from conftest import GOLDEN
-from parity_utils import run_pair, rel_err, assert_components, RTOL
+from parity_utils import run_pair, rel_err, assert_components, switches, RTOL
 from aither_amd import abi
 from aither_amd.case import connections as conn_mod
 from aither_amd.case import synthetic
@@ -39,7 +38,7 @@ RANS_WALL = dict(FARFIELD)
 RANS_WALL[3] = ("viscousWall", 2)
 
 # ---- the dispatch conditions, restated from aither_amd/csrc/agx_api.hip ----------------
-KP_CHUNK = 256            # lusgs_kp_chunks: CH = 2 when min(ni, nj) > 256
+KP_CHUNK = 256            # lusgs_kp_variant: CH = 2 when min(ni, nj) > 256
 KP_MAX_DIAG = 512         # refused above (block creation)
 # k_lusgs_kp runs min(per_cu * num_cu, nk) workgroups of 256 threads.  A CU holds at most 32
 # waves = 2048 threads = 8 such workgroups (maxThreadsPerMultiProcessor), the MI355X has 256
@@ -71,21 +70,6 @@ def can_fuse(kw):
     """can_fuse: explicit, inviscid, no non-reflecting surface."""
     return kw.get("time_integration", "rk4") in ("rk4", "explicitEuler") and \
         kw.get("equation_set", "euler") == "euler"
-
-
-@contextlib.contextmanager
-def _env(**env):
-    """AGX_* switches are read when a context is created."""
-    old = {k: os.environ.get(k) for k in env}
-    os.environ.update(env)
-    try:
-        yield
-    finally:
-        for k, v in old.items():
-            if v is None:
-                os.environ.pop(k, None)
-            else:
-                os.environ[k] = v
 
 
 def _pair(lib, oracle, case, steps, **kw):
@@ -178,7 +162,7 @@ def test_kp_diagonal_limit_refused_by_name_and_served_by_the_plane_form(agx, ora
     with pytest.raises(RuntimeError, match=r"min\(ni, nj\) = 513 exceeds the 512 cells per "
                                            r"diagonal.*AGX_LUSGS=plane"):
         Solver(agx, case)
-    with _env(AGX_LUSGS="plane"):
+    with switches(AGX_LUSGS="plane"):
         _pair(agx, oracle, case, 2)
 
 

@@ -9,14 +9,13 @@ both pitches (64 and 62 cells) and takes two chunks of 6 and 3 planes on 8 workg
 (65, 7, 20) is 2 x 2 tiles of centralFourth's 60-cell pitch in two chunks of 10
 (tests/cpp/tile_plan.cpp holds the plans of exactly these shapes to that).
 """
-import contextlib
 import gc
-import os
 
 import numpy as np
 import pytest
 
 from parity_utils import run_pair   # (asserts every field to its RTOL, 1e-10)
+from parity_utils import switches
 from aither_amd.case import synthetic
 from aither_amd.solver import Solver
 
@@ -31,23 +30,8 @@ RK4 = dict(stretch=1.1, face_reconstruction="thirdOrder", limiter="vanAlbada",
            inviscid_flux="roe", time_integration="rk4", cfl=0.5)
 
 
-@contextlib.contextmanager
-def _env(**env):
-    """AGX_* switches are read when a context is created."""
-    old = {k: os.environ.get(k) for k in env}
-    os.environ.update(env)
-    try:
-        yield
-    finally:
-        for k, v in old.items():
-            if v is None:
-                os.environ.pop(k, None)
-            else:
-                os.environ[k] = v
-
-
 def _run(api, case, steps, order, workgroups):
-    with _env(AGX_TILE_ORDER=order, AGX_WORKGROUPS=str(workgroups)):
+    with switches(AGX_TILE_ORDER=order, AGX_WORKGROUPS=str(workgroups)):
         s = Solver(api, case)
     try:
         for nn in range(steps):
@@ -116,7 +100,7 @@ def test_step_order_against_oracle(agx, oracle, n, workgroups):
     if workgroups:
         env["AGX_WORKGROUPS"] = str(workgroups)
     failure = None
-    with _env(**env):
+    with switches(**env):
         try:
             for s in run_pair(agx, oracle, case, 2):
                 s.close()
