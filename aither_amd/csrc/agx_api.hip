@@ -98,6 +98,11 @@ struct Block {
   // k_lusgs_prepare folded the norms of the residual planes as they are now into its slot of
   // norm_out, so the update neither reads the residual nor folds.
   bool resid_norms_current = false;
+  // the viscous tile kernel of this residual took its RHS form: b, 1 / a and the aInv_ plane
+  // are what k_lusgs_prepare would write from the residual planes as they are now, and the
+  // block's norms lie in prepare's slot of norm_out.  agx_phase_residual sets it inside
+  // agx_iterate, the implicit_begin that follows takes it (and skips the pass).
+  bool rhs_in_d2 = false;
   // multigrid: forcing | matrix residual | saved update planes (each allocated on first
   // use); the transfer maps of this block as the FINE side (device copies, keyed by the
   // host pointers they were uploaded from); node values of this block as the coarse side
@@ -299,8 +304,8 @@ int lusgs_sweep(agx_ctx* c, Block& blk, bool forward, int full, hipStream_t st =
 namespace {
 // ---- what happened, and which derived data it leaves stale or current ---------------------
 // The only statements that assign Block::x_planes_current, x_is_zero, d2_state_current,
-// resid_norms_current and agx_ctx::ghosts_prefilled, state_is_time_n: a writer says what it
-// did.  DESIGN.md section 4 has the table of event x flag with the reasons.
+// resid_norms_current, rhs_in_d2 and agx_ctx::ghosts_prefilled, state_is_time_n: a writer says
+// what it did.  DESIGN.md section 4 has the table of event x flag with the reasons.
 //
 // x: something is about to write it where it lives (the D2 arrays on the diagonal-ordered
 // path) / k_d2_x_copy made a block's planes and its D2 arrays equal
@@ -327,15 +332,20 @@ void state_updated_d2(Block& b, bool wrote_d2) { b.d2_state_current = wrote_d2; 
 // norms of them / the update took the folded norms (one use: a second update on the same
 // residual reads it itself)
 void resid_written(agx_ctx* c) {
-  for (auto& blk : c->blocks) blk.resid_norms_current = false;
+  for (auto& blk : c->blocks) blk.resid_norms_current = blk.rhs_in_d2 = false;
 }
 void resid_norms_folded(Block& b) { b.resid_norms_current = true; }
 void resid_norms_used(Block& b) { b.resid_norms_current = false; }
+// the viscous tile kernel finished a block's cells for the sweeps (its RHS form) /
+// implicit_begin took that in place of the prepare pass
+void rhs_written_by_residual(Block& b) { b.rhs_in_d2 = true; }
+void rhs_taken(Block& b) { b.rhs_in_d2 = false; }
 // an upload or a multigrid restriction wrote planes of a block: whichever they were, its D2
 // state and its folded norms are taken for stale
 void planes_uploaded(Block& b) {
   b.d2_state_current = false;
   b.resid_norms_current = false;
+  b.rhs_in_d2 = false;
 }
 // the ghost cells: the fill for the next agx_iterate was queued behind the update's norms /
 // it is used up, or something wrote ghost cells or the state since
@@ -2276,6 +2286,8 @@ int agx_setup_finalize(agx_ctx* c) {
       // k_lusgs_prepare: one per tile of the padded box
       max_parts = std::max(max_parts, (long)((blk.d.d2.Pi + TT - 1) / TT) *
                                           ((blk.d.d2.Pj + TT - 1) / TT) * (blk.d.nk + 2 * blk.d.ng));
+      // k_visc_tile's RHS form: one per wave of its persistent workgroups
+      max_parts = std::max(max_parts, (long)c->num_cu * VT_R);
 #endif
     }
   }
@@ -2990,6 +3002,25 @@ int agx_phase_bc_faces(agx_ctx* c) {
 }
 int agx_phase_bc_edges(agx_ctx* c) { return bc_edges(c); }
 
+#if AGX_FAST
+// May the viscous tile kernel of this residual finish the block's cells for the sweeps (its
+// RHS form), so that implicit_begin skips k_lusgs_prepare?  Only where that pass would be the
+// lean one with the norm fold, would write no x, and forms b from the residual alone.  (A
+// dual-time term is excluded rather than formed: the kernel would have to keep the spectral
+// radius beside a.)  The caller adds: only inside agx_iterate -- through the phase API a
+// caller may read or change the residual between the phases, so there the kernel folds the
+// norms (an upload of the residual makes them stale: planes_uploaded) and the pass stays.
+static bool rhs_form_applies(const agx_ctx* c, const Block& blk) {
+  const BlockDev& b = blk.d;
+  bool conn = false;
+  for (int q = 0; q < 6; ++q) conn = conn || b.side_conn[q] != 0;
+  return b.d2.base && blk.d2_state_current && c->d2_state_update &&
+         c->resid_norms_prepare && !conn && !c->sp.requires_init && c->state_is_time_n &&
+         !c->sp.bdf2 && !b.mg_forcing && !c->sp.diag_add && !c->mg_coarse &&
+         !(c->sp.dual_time_cfl > 0.0) && !c->sp.les;
+}
+#endif
+
 int agx_phase_residual(agx_ctx* c, int mm, double cfl) {
   if (c->cfg.dt_nondim <= 0.0 && cfl <= 0.0)
     return fail("Neither dt or cfl was specified!");   // procBlock.cpp:813-816
@@ -3095,13 +3126,40 @@ int agx_phase_residual(agx_ctx* c, int mm, double cfl) {
         const TilePlan tp = tile_plan_of(c, gx, gy, vb.nk, nwg,
                                          fourth ? TILE_CHARGE_VISC_F4 : TILE_CHARGE_VISC,
                                          c->tile_order_visc);
+        if (!fourth && rhs_form_applies(c, blk)) {
+          // the RHS forms: the residual norms from here, VT_R partials per workgroup, folded
+          // into prepare's slot right behind the launch (the partials are one area for all
+          // blocks) -- and inside agx_iterate b, 1 / a and the aInv_ plane as well
+          if (c->in_iterate) {
+            c->sp.un_is_u = 1;        // (as implicit_begin sets it: state_is_time_n holds)
+            VtRhs<VT_RHS_FULL> rz;
+            rz.partials = c->partials.get();
+            rz.pab = reinterpret_cast<char*>(vb.d2.base + 2L * PA_B * vb.d2.nd2);
+            rz.arr16 = vb.d2.nd2 * 16;
+            rz.ps16 = vb.d2.ps * 16;
+            rz.Pi = vb.d2.Pi;
+            rz.Pj = vb.d2.Pj;
+            hipLaunchKernelGGL((k_visc_tile<false, false, VT_RHS_FULL>), dim3(nwg),
+                               dim3(VT_L, VT_R), 0, c->stream, make_slab(vb), c->gas, c->sp, cfl,
+                               gx, tp, rz);
+            rhs_written_by_residual(blk);
+          } else {
+            hipLaunchKernelGGL((k_visc_tile<false, false, VT_RHS_NORMS>), dim3(nwg),
+                               dim3(VT_L, VT_R), 0, c->stream, make_slab(vb), c->gas, c->sp, cfl,
+                               gx, tp, VtRhs<VT_RHS_NORMS>{c->partials.get()});
+          }
+          const size_t n = (size_t)(&blk - c->blocks.data());
+          if (reduce_norms(c, n, (long)nwg * VT_R, c->norm_prepare() + n)) return 1;
+          resid_norms_folded(blk);
+          continue;
+        }
         // (largeEddySimulation: the instantiations with the WALE arm, which also write the
         // run's eddy-viscosity plane)
         by_bool(c->sp.les != 0, [&](auto les) {
           by_bool(fourth, [&](auto f4) {
             hipLaunchKernelGGL((k_visc_tile<f4, decltype(les)::value>), dim3(nwg),
                                dim3(VT_L, VT_R), 0, c->stream, make_slab(vb), c->gas, c->sp, cfl,
-                               gx, tp);
+                               gx, tp, VtRhs<VT_RHS_NONE>{});
           });
         });
 #endif
@@ -3166,11 +3224,25 @@ int agx_phase_implicit_begin(agx_ctx* c) { return implicit_begin(c, 1); }
 // (write_x = 0: gridLevel::InvertDiagonal alone, for a coarse multigrid level)
 static int implicit_begin(agx_ctx* c, int write_x) {
   x_changed(c);
-  Timer t(c, G_PREPARE);
+  // (the group counts a launch only where a block still takes the pass)
+  bool any_pass = false;
+  for (auto& blk : c->blocks) any_pass = any_pass || !(write_x && blk.rhs_in_d2);
+  std::unique_ptr<Timer> t;
+  if (any_pass) t = std::make_unique<Timer>(c, G_PREPARE);
   c->sp.un_is_u = c->state_is_time_n ? 1 : 0;   // (read by every rhs_b of this iteration)
   for (auto& blk : c->blocks) {
     const BlockDev& b = blk.d;
 #if AGX_FAST
+    const bool rhs_done = write_x && blk.rhs_in_d2;
+    rhs_taken(blk);
+    if (rhs_done) {
+      // the viscous tile kernel of this residual wrote b, 1 / a and the aInv_ plane and its
+      // norms are folded (rhs_form_applies): nothing is left of the pass.  x = 0 stays
+      // unwritten as the lean launch leaves it.
+      x_prepared(blk, true);
+      resid_norms_folded(blk);
+      continue;
+    }
     if (b.d2.base) {
       // diagonal terms, b and x0 straight into the D2 arrays of the sweeps (a coarse
       // multigrid level, write_x = 0: x is the restricted one)
@@ -3178,8 +3250,10 @@ static int implicit_begin(agx_ctx* c, int write_x) {
       for (int q = 0; q < 6; ++q) conn = conn || b.side_conn[q] != 0;
       const int wx = write_x && (c->sp.requires_init || conn) ? 1 : 0;
       // (the norms ride along on the finest level's launch only: a coarse multigrid level,
-      // write_x = 0, keeps the update's fold)
-      if (d2_prepare(c, blk, wx, 0, write_x && c->resid_norms_prepare ? 1 : 0)) return 1;
+      // write_x = 0, keeps the update's fold; not where the viscous tile kernel of this
+      // residual folded them already)
+      const int norms = write_x && c->resid_norms_prepare && !blk.resid_norms_current ? 1 : 0;
+      if (d2_prepare(c, blk, wx, 0, norms)) return 1;
       x_prepared(blk, write_x && !wx);
       continue;
     }

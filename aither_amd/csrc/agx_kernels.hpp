@@ -170,6 +170,26 @@ struct SolverDev {   // scalar run-time parameters of agx_config
 };
 static_assert(sizeof(SolverDev) == 96, "SolverDev::les lies in the tail padding");
 
+// What the scalar LU-SGS path forms per cell from the finished residual, written once for the
+// two kernels that form it (k_lusgs_prepare and the RHS form of k_visc_tile), so that both
+// compile the same expressions on the same doubles:
+//   * b of linearSolver.cpp:370-374 where the state is still time level n and the scheme has
+//     no second level (un_is_u && !bdf2): U - U_n is exactly zero
+//   * V (1 + zeta) / (dt theta) of AddDiagonalTerms (linearSolver.cpp:146-175) and the
+//     finished main diagonal a relax + that
+__device__ __forceinline__ void lusgs_b_time_n(const SolverDev& sp, const double* r,
+                                               double* out) {
+  const double thetaInv = 1.0 / sp.theta;
+#pragma unroll
+  for (int e = 0; e < AGX_NEQ; ++e) out[e] = -thetaInv * r[e] - 0.0;
+}
+__device__ __forceinline__ double lusgs_dvt(const SolverDev& sp, double vol, double dt) {
+  return (vol * (1.0 + sp.zeta)) / (dt * sp.theta);
+}
+__device__ __forceinline__ double lusgs_diag(const SolverDev& sp, double a, double dvt) {
+  return a * sp.relax + dvt;
+}
+
 __device__ __forceinline__ void load5(double* const* p, long q, double* s) {
 #pragma unroll
   for (int e = 0; e < AGX_NEQ; ++e) s[e] = p[e][q];
@@ -2569,8 +2589,7 @@ __device__ __forceinline__ void rhs_b_r(const BlockDev& b, const GasDev& g,
                                         double* out) {
   const double thetaInv = 1.0 / sp.theta;
   if (sp.un_is_u && !sp.bdf2) {
-#pragma unroll
-    for (int e = 0; e < AGX_NEQ; ++e) out[e] = -thetaInv * r[e] - 0.0;
+    lusgs_b_time_n(sp, r, out);
     return;
   }
   double s[AGX_NEQ], u[AGX_NEQ], un[AGX_NEQ];

@@ -76,6 +76,15 @@ struct D2Dev {
   }
 };
 
+// start of diagonal de in a plane of Pi x Pj padded cells, closed form of the dstart table
+__device__ __forceinline__ int d2_dstart_cf(int Pi, int Pj, int de) {
+  const int a = min(Pi, Pj), bm = max(Pi, Pj);
+  if (de <= a) return de * (de + 1) / 2;
+  if (de <= bm) return a * (a + 1) / 2 + (de - a) * a;
+  const int r = Pi + Pj - 1 - de;
+  return Pi * Pj - r * (r + 1) / 2;
+}
+
 // What the sweep kernel needs of a block and of the gas model.  Passing the whole
 // BlockDev / GasDev (about 100 kernel-argument SGPRs) made the compiler park
 // scalars in VGPR lanes: ~400 v_readlane / v_writelane in the step loop.
@@ -89,13 +98,7 @@ struct KpBlk {
   int side_conn[6];
   // start of diagonal de in a plane, closed form of the dstart table (scalar
   // arithmetic: a table lookup is a memory access in the step loop)
-  __device__ __forceinline__ int dstart_cf(int de) const {
-    const int a = min(Pi, Pj), bm = max(Pi, Pj);
-    if (de <= a) return de * (de + 1) / 2;
-    if (de <= bm) return a * (a + 1) / 2 + (de - a) * a;
-    const int r = Pi + Pj - 1 - de;
-    return Pi * Pj - r * (r + 1) / 2;
-  }
+  __device__ __forceinline__ int dstart_cf(int de) const { return d2_dstart_cf(Pi, Pj, de); }
   // array `id` (pair arrays: 16 bytes per cell) as a byte pointer, wave-uniform
   __device__ __forceinline__ const char* pab(int id) const {
     return reinterpret_cast<const char*>(base) + (size_t)id * (size_t)nd2 * 16;

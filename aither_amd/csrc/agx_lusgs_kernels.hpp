@@ -149,13 +149,13 @@ k_lusgs_prepare(BlockDev b, GasDev g, SolverDev sp, int write_x, unsigned tag, i
         if (sp.viscous) vf[m] = cell_visc_factor(g, s);
       }
       if (phys) {
-        double dvt = (b.vol[q] * (1.0 + sp.zeta)) / (b.dt[q] * sp.theta);
+        double dvt = lusgs_dvt(sp, b.vol[q], b.dt[q]);
         if (sp.dual_time_cfl > 0.0) dvt += fmax(b.specrad[q], 0.0) / sp.dual_time_cfl;
         // (the plane-major a_ itself is not written back on the finest level: the next
         // residual assigns it afresh.  The finished diagonal goes to the D2 arrays as 1/a
         // and, for the multigrid calls that work on the planes, into the aInv_ plane,
         // which nothing else uses on this path.)
-        const double a = again ? b.ainv[q] : b.a[q] * sp.relax + dvt;
+        const double a = again ? b.ainv[q] : lusgs_diag(sp, b.a[q], dvt);
         b.ainv[q] = a;
         // (a coarse multigrid level: the reference's a_ holds the finished diagonal from
         // here on, and a second restriction to the level within the iteration adds its

@@ -239,10 +239,41 @@ __device__ __forceinline__ void vt_face(VShared sh, const GasDev& g, const VRef&
 // the window stays 8 x 64 x 39 doubles), and the own column's rotates in a register (MU0r).
 // Overhang threads and the `pre` pass contribute nothing: their fi / fj stay zero, and the
 // `pre` pass forms exactly the lower k-face a re-primed segment needs, mut included.
-template <bool F4, bool LES = false>
+//
+// RHS (scalar LU-SGS, `central` without LES; the host says when: agx_phase_residual).
+// VT_RHS_FULL: the store block holds everything k_lusgs_prepare's lean form would read back --
+// the five residuals, a, dt, the volume -- so it finishes the cell for the sweeps itself:
+// b = -(1/theta) r and 1/a as three double2 at the cell's place in the diagonal-ordered PA_B
+// arrays, a into the aInv_ plane, and the residual norms (prepare's record and tie rule), one
+// partial per wave folded by shuffles when the workgroup's range is done (the LDS is the
+// window's, all of it).  A thread owns cell (i, j) and marches k, so its D2 position is one
+// lane offset per segment -- dstart[ie + je] + je - jlo(ie + je) -- on a plane base that
+// advances by the plane stride.  Neighbouring lanes sit one diagonal apart: the three 16-byte
+// stores scatter, and the tiles that march beside this one complete the cache lines.
+// VT_RHS_NORMS: the norms alone, the same partials -- for the same block driven through the
+// phases, where the pass stays: the L2 sums a caller gets are agx_iterate's to the bit.
+enum { VT_RHS_NONE = 0, VT_RHS_NORMS = 1, VT_RHS_FULL = 2 };
+template <int RHS>
+struct VtRhs {};
+template <>
+struct VtRhs<VT_RHS_NORMS> {
+  NormPartial* partials; // VT_R per workgroup
+};
+template <>
+struct VtRhs<VT_RHS_FULL> {
+  NormPartial* partials;
+  char* pab;             // PA_B + 0 of the block's D2 arrays
+  long arr16, ps16;      // bytes from one pair array to the next / from a k-plane to the next
+  int Pi, Pj;            // padded plane dims
+};
+template <bool F4, bool LES = false, int RHS = VT_RHS_NONE>
 __global__ void __launch_bounds__(VT_L * VT_R)
-k_visc_tile(SlabDev b, GasDev g, SolverDev sp, double cfl, int gx, TilePlan tp) {
+k_visc_tile(SlabDev b, GasDev g, SolverDev sp, double cfl, int gx, TilePlan tp, VtRhs<RHS> rz) {
+  static_assert(!RHS || (!F4 && !LES), "the RHS forms exist for `central` without LES");
   __shared__ double sh[VT_R][VT_L][VS_COUNT];
+  // RHS: the residual norms of the cells this thread finished, over the workgroup's whole range
+  double nl2[AGX_NEQ] = {0, 0, 0, 0, 0}, nvmax = -1.0e300;
+  long long nvlin = 0x7fffffffffffffffLL;
   constexpr int NF = LES ? 5 : 4;                       // flux components (+ mut) per face
   constexpr int LO = F4 ? 2 : 1;                        // first owning lane
   constexpr int OI = F4 ? VT_L - 4 : VT_OI;             // owned cells along i
@@ -266,6 +297,14 @@ k_visc_tile(SlabDev b, GasDev g, SolverDev sp, double cfl, int gx, TilePlan tp) 
   const unsigned qc = (unsigned)(b.idx(ic, jc, 0) * 8);
   const unsigned sk = (unsigned)(b.sxy * 8), sj = (unsigned)(b.sx * 8);
   const int kcmax = b.nk + b.ng - 1, kfmax = b.nk + b.ng; // last valid cell / face plane
+  // RHS: byte offset of the column inside a D2 plane of pairs, and lin0 of its cell in plane 0
+  unsigned pd2 = 0;
+  long long lin_c = 0;
+  if constexpr (RHS == VT_RHS_FULL) {
+    const int ie = ic + b.ng, je = jc + b.ng, de = ie + je;
+    pd2 = (unsigned)(d2_dstart_cf(rz.Pi, rz.Pj, de) + je - max(0, de - (rz.Pi - 1))) * 16u;
+  }
+  if constexpr (RHS != VT_RHS_NONE) lin_c = ((long long)jc * b.ni + ic) * AGX_NEQ;
   auto ld_state = [&](int k, double* s4, double& rho, double& mu) {
     const unsigned q = qc + (unsigned)min(k, kcmax) * sk;
     rho = b.ldb(b.st + 0, q);
@@ -495,6 +534,7 @@ k_visc_tile(SlabDev b, GasDev g, SolverDev sp, double cfl, int gx, TilePlan tp) 
       double res[AGX_NEQ];
 #pragma unroll
       for (int e = 1; e < AGX_NEQ; ++e) res[e] = b.ldb(PL_RESID + e, q);
+      if constexpr (RHS != VT_RHS_NONE) res[0] = b.ldb(PL_RESID + 0, q);   // (b and the norms)
       // +lower -upper per direction
 #pragma unroll
       for (int c = 0; c < 4; ++c)
@@ -541,7 +581,32 @@ k_visc_tile(SlabDev b, GasDev g, SolverDev sp, double cfl, int gx, TilePlan tp) 
       for (int e = 1; e < AGX_NEQ; ++e) b.stb(PL_RESID + e, q, res[e]);   // mass: no viscous flux
       b.stb(PL_SPECRAD, q, sr);
       if (sp.implicit) b.stb(PL_A, q, diag);
-      b.stb(PL_DT, q, sp.dt_fixed > 0.0 ? sp.dt_fixed : cfl * (V0 * fast_rcp(fmax(sr, 0.0))));
+      const double dt = sp.dt_fixed > 0.0 ? sp.dt_fixed : cfl * (V0 * fast_rcp(fmax(sr, 0.0)));
+      b.stb(PL_DT, q, dt);
+      if constexpr (RHS == VT_RHS_FULL) {
+        // AddDiagonalTerms, Invert and b (k_lusgs_prepare's expressions on the doubles just
+        // stored; no dual-time term: the host keeps the pass where there is one)
+        const double a = lusgs_diag(sp, diag, lusgs_dvt(sp, V0, dt));
+        b.stb(PL_AINV, q, a);
+        const double ia = 1.0 / a;
+        double bb[AGX_NEQ];
+        lusgs_b_time_n(sp, res, bb);
+        char* pb = rz.pab + (long)(kk + b.ng) * rz.ps16 + pd2;
+        *reinterpret_cast<double2*>(pb) = make_double2(bb[0], bb[1]);
+        *reinterpret_cast<double2*>(pb + rz.arr16) = make_double2(bb[2], bb[3]);
+        *reinterpret_cast<double2*>(pb + 2 * rz.arr16) = make_double2(bb[4], ia);
+      }
+      if constexpr (RHS != VT_RHS_NONE) {
+        const long long lin0 = lin_c + (long long)kk * ((long long)b.nj * b.ni * AGX_NEQ);
+#pragma unroll
+        for (int e = 0; e < AGX_NEQ; ++e) {
+          nl2[e] += res[e] * res[e];
+          if (res[e] > nvmax || (res[e] == nvmax && lin0 + e < nvlin)) {
+            nvmax = res[e];
+            nvlin = lin0 + e;
+          }
+        }
+      }
     }
     // ---- rotate the window in the own LDS slots ----
     {
@@ -591,6 +656,24 @@ k_visc_tile(SlabDev b, GasDev g, SolverDev sp, double cfl, int gx, TilePlan tp) 
     }
   }
   __syncthreads();   // segment boundary: the windows are primed afresh
+  }
+  if constexpr (RHS != VT_RHS_NONE) {
+    // a row is a wave: one partial each (rows 0 and 7 own nothing and hand in the empty one)
+    for (int off = 32; off > 0; off >>= 1) {
+#pragma unroll
+      for (int e = 0; e < AGX_NEQ; ++e) nl2[e] += __shfl_down(nl2[e], off, 64);
+      const double ov = __shfl_down(nvmax, off, 64);
+      const long long ol = __shfl_down(nvlin, off, 64);
+      if (ov > nvmax || (ov == nvmax && ol < nvlin)) { nvmax = ov; nvlin = ol; }
+    }
+    if (threadIdx.x == 0) {
+      NormPartial p;
+#pragma unroll
+      for (int e = 0; e < AGX_NEQ; ++e) p.l2[e] = nl2[e];
+      p.vmax = nvmax;
+      p.lin = nvlin;
+      rz.partials[(long)blockIdx.x * VT_R + threadIdx.y] = p;
+    }
   }
 }
 

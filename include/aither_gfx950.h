@@ -659,7 +659,8 @@ int agx_halo_exchange(agx_ctx *ctx, int what);
  * measured with hipEvents on the library's stream; group: 0 = inviscid residual
  * (+ fused explicit stage), 1 = update + norms, 2 = ghost cells / halo,
  * 3 = LU-SGS / DPLUR sweeps, 4 = viscous residual, 5 = implicit begin
- * (diagonal, right-hand side), 6 = matrix residual */
+ * (diagonal, right-hand side; no launch is counted where the viscous residual of
+ * agx_iterate wrote both itself, and then group 4 carries it), 6 = matrix residual */
 int agx_timing_enable(agx_ctx *ctx, int on);
 int agx_timing_get(agx_ctx *ctx, int group, double *avg_ms, int64_t *launches);
 int agx_timing_reset(agx_ctx *ctx);
