@@ -664,6 +664,13 @@ MarchPlan march_plan(agx_ctx* c, const BlockDev& b) {
   return p;
 }
 
+// does the block have a connection (interblock / periodic) on any side?
+static bool has_connection(const BlockDev& b) {
+  bool conn = false;
+  for (int q = 0; q < 6; ++q) conn = conn || b.side_conn[q] != 0;
+  return conn;
+}
+
 SlabDev make_slab(const BlockDev& b) {
   SlabDev sd;
   sd.base = b.vol - (long)PL_VOL * b.nplane;
@@ -1063,8 +1070,7 @@ static int lusgs_sweep_all(agx_ctx* c, bool forward, int full) {
 // the form of k_lusgs_kp for a half sweep of this block: direction, triangle set, connections
 // on any side, chunks per step (2 x 2 x 2 x 2 forms)
 int lusgs_kp_variant(agx_ctx* c, Block& blk, bool forward, int full) {
-  bool conn = false;
-  for (int q = 0; q < 6; ++q) conn = conn || blk.d.side_conn[q] != 0;
+  const bool conn = has_connection(blk.d);
   const int chunks = std::min(blk.d.ni, blk.d.nj) <= 256 ? 1 : 2;
   return by_bool(forward, [&](auto fwd) {
     return by_bool(full != 0, [&](auto fl) {
@@ -3012,14 +3018,127 @@ int agx_phase_bc_edges(agx_ctx* c) { return bc_edges(c); }
 // norms (an upload of the residual makes them stale: planes_uploaded) and the pass stays.
 static bool rhs_form_applies(const agx_ctx* c, const Block& blk) {
   const BlockDev& b = blk.d;
-  bool conn = false;
-  for (int q = 0; q < 6; ++q) conn = conn || b.side_conn[q] != 0;
   return b.d2.base && blk.d2_state_current && c->d2_state_update &&
-         c->resid_norms_prepare && !conn && !c->sp.requires_init && c->state_is_time_n &&
+         c->resid_norms_prepare && !has_connection(b) && !c->sp.requires_init && c->state_is_time_n &&
          !c->sp.bdf2 && !b.mg_forcing && !c->sp.diag_add && !c->mg_coarse &&
          !(c->sp.dual_time_cfl > 0.0) && !c->sp.les;
 }
 #endif
+
+// The viscous residual of one block, behind its inviscid one (launch_inv).
+#if AGX_NEQ == 7
+static int launch_visc(agx_ctx* c, Block& blk, double cfl) {
+  const int fourth = c->cfg.viscous_recon == AGX_VISC_RECON_CENTRAL_4TH ? 1 : 0;
+  const BlockDev& vb = blk.d;
+  if (c->visc_gather) {
+    hipLaunchKernelGGL(k_visc_residual_rans, cell_grid(vb, CELL_BLOCK), CELL_BLOCK,
+                       0, c->stream, vb, c->gas, c->sp, cfl, fourth);
+    return 0;
+  }
+  // face-once form: every face evaluated by one thread, records through memory (the
+  // blocks run one after the other on the stream and share the record buffer)
+  RansRec rec;
+  rec.ni1 = vb.ni + 1; rec.nj1 = vb.nj + 1;
+  rec.nf = (long)rec.ni1 * rec.nj1 * (vb.nk + 1);
+  const size_t need = (size_t)3 * RANS_REC * rec.nf;
+  if (need > c->rans_rec.size()) {
+    HIPCHK(hipStreamSynchronize(c->stream));     // (before the old one is freed)
+    HIPCHK(c->rans_rec.alloc(need));
+  }
+  rec.p = c->rans_rec.get();
+  const dim3 tb = CELL_BLOCK;
+  auto fgrid = [&](int di, int dj, int dk) {
+    return dim3((vb.ni + di + tb.x - 1) / tb.x, (vb.nj + dj + tb.y - 1) / tb.y, vb.nk + dk);
+  };
+  hipLaunchKernelGGL(k_rans_faces<0>, fgrid(1, 0, 0), tb, 0, c->stream, vb, c->gas, fourth, rec);
+  hipLaunchKernelGGL(k_rans_faces<1>, fgrid(0, 1, 0), tb, 0, c->stream, vb, c->gas, fourth, rec);
+  hipLaunchKernelGGL(k_rans_faces<2>, fgrid(0, 0, 1), tb, 0, c->stream, vb, c->gas, fourth, rec);
+  hipLaunchKernelGGL(k_rans_cells, cell_grid(vb, tb), tb, 0, c->stream, vb, c->gas, c->sp,
+                     cfl, fourth, rec);
+  return 0;
+}
+#else
+#if AGX_FAST
+static int launch_visc_tile(agx_ctx* c, Block& blk, double cfl, bool fourth) {
+  const BlockDev& vb = blk.d;
+  // 62 x 6 owned cells per workgroup and k-step (centralFourth: 60 x 6); persistent
+  // workgroups, one per CU (the kernel's LDS windows fill a CU), each marching its share
+  // of the (column tile, k) steps by the plan (agx_tile_plan.hpp)
+  const int gx = tile_count(vb.ni, fourth ? TILE_VISC_I_F4 : TILE_VISC_I);
+  const int gy = tile_count(vb.nj, TILE_J);
+  const long steps = (long)gx * gy * vb.nk;
+  const int nwg = (int)std::min<long>(c->num_cu, std::max<long>(1, steps / 8));
+  const TilePlan tp = tile_plan_of(c, gx, gy, vb.nk, nwg,
+                                   fourth ? TILE_CHARGE_VISC_F4 : TILE_CHARGE_VISC,
+                                   c->tile_order_visc);
+  if (!fourth && rhs_form_applies(c, blk)) {
+    // the RHS forms: the residual norms from here, VT_R partials per workgroup, folded
+    // into prepare's slot right behind the launch (the partials are one area for all
+    // blocks) -- and inside agx_iterate b, 1 / a and the aInv_ plane as well
+    if (c->in_iterate) {
+      c->sp.un_is_u = 1;        // (as implicit_begin sets it: state_is_time_n holds)
+      VtRhs<VT_RHS_FULL> rz;
+      rz.partials = c->partials.get();
+      rz.pab = reinterpret_cast<char*>(vb.d2.base + 2L * PA_B * vb.d2.nd2);
+      rz.arr16 = vb.d2.nd2 * 16;
+      rz.ps16 = vb.d2.ps * 16;
+      rz.Pi = vb.d2.Pi;
+      rz.Pj = vb.d2.Pj;
+      hipLaunchKernelGGL((k_visc_tile<false, false, VT_RHS_FULL>), dim3(nwg),
+                         dim3(VT_L, VT_R), 0, c->stream, make_slab(vb), c->gas, c->sp, cfl,
+                         gx, tp, rz);
+      rhs_written_by_residual(blk);
+    } else {
+      hipLaunchKernelGGL((k_visc_tile<false, false, VT_RHS_NORMS>), dim3(nwg),
+                         dim3(VT_L, VT_R), 0, c->stream, make_slab(vb), c->gas, c->sp, cfl,
+                         gx, tp, VtRhs<VT_RHS_NORMS>{c->partials.get()});
+    }
+    const size_t n = (size_t)(&blk - c->blocks.data());
+    if (reduce_norms(c, n, (long)nwg * VT_R, c->norm_prepare() + n)) return 1;
+    resid_norms_folded(blk);
+    return 0;
+  }
+  // (largeEddySimulation: the instantiations with the WALE arm, which also write the
+  // run's eddy-viscosity plane)
+  by_bool(c->sp.les != 0, [&](auto les) {
+    by_bool(fourth, [&](auto f4) {
+      hipLaunchKernelGGL((k_visc_tile<f4, decltype(les)::value>), dim3(nwg),
+                         dim3(VT_L, VT_R), 0, c->stream, make_slab(vb), c->gas, c->sp, cfl,
+                         gx, tp, VtRhs<VT_RHS_NONE>{});
+    });
+  });
+  return 0;
+}
+#endif
+static int launch_visc(agx_ctx* c, Block& blk, double cfl) {
+  const bool fourth = c->cfg.viscous_recon == AGX_VISC_RECON_CENTRAL_4TH;
+  const bool wide_plane = (double)blk.d.nplane * 8.0 >= 4294967296.0;
+  if (!AGX_FAST || c->visc_gather || ((fourth || c->sp.les) && (c->visc_march || wide_plane))) {
+    // (one thread per cell, the stencil straight from the planes: AGX_VISC=gather, and
+    // centralFourth or largeEddySimulation -- k_visc_march has no WALE arm -- where the
+    // tile kernel's 32-bit plane offsets do not reach)
+    hipLaunchKernelGGL(c->sp.les ? k_visc_residual_les : k_visc_residual,
+                       cell_grid(blk.d, CELL_BLOCK), CELL_BLOCK, 0, c->stream, blk.d, c->gas,
+                       c->sp, cfl, fourth ? 1 : 0);
+    return 0;
+  }
+  const BlockDev& vb = blk.d;
+  if (c->visc_march || wide_plane) {
+    const int gx = (vb.ni + VTI - 1) / VTI, gy = (vb.nj + VTJ - 1) / VTJ;
+    int nz = std::max(1, std::min(vb.nk / 8, (int)std::lround(2048.0 / (gx * gy))));
+    const int kchunk = (vb.nk + nz - 1) / nz;
+    nz = (vb.nk + kchunk - 1) / kchunk;
+    hipLaunchKernelGGL(k_visc_march, dim3(gx, gy, nz), dim3(64, VTJ + 1), 0, c->stream,
+                       vb, c->gas, c->sp, cfl, kchunk);
+    return 0;
+  }
+#if AGX_FAST    // (no other build has the tile kernel; there the first arm took every block)
+  return launch_visc_tile(c, blk, cfl, fourth);
+#else
+  return 0;
+#endif
+}
+#endif  // AGX_NEQ == 7
 
 int agx_phase_residual(agx_ctx* c, int mm, double cfl) {
   if (c->cfg.dt_nondim <= 0.0 && cfl <= 0.0)
@@ -3063,109 +3182,7 @@ int agx_phase_residual(agx_ctx* c, int mm, double cfl) {
     }
     Timer t(c, G_VISC);
     for (auto& blk : c->blocks)
-#if AGX_NEQ == 7
-      {
-        const int fourth = c->cfg.viscous_recon == AGX_VISC_RECON_CENTRAL_4TH ? 1 : 0;
-        const BlockDev& vb = blk.d;
-        if (c->visc_gather) {
-          hipLaunchKernelGGL(k_visc_residual_rans, cell_grid(vb, CELL_BLOCK), CELL_BLOCK,
-                             0, c->stream, vb, c->gas, c->sp, cfl, fourth);
-          continue;
-        }
-        // face-once form: every face evaluated by one thread, records through memory (the
-        // blocks run one after the other on the stream and share the record buffer)
-        RansRec rec;
-        rec.ni1 = vb.ni + 1; rec.nj1 = vb.nj + 1;
-        rec.nf = (long)rec.ni1 * rec.nj1 * (vb.nk + 1);
-        const size_t need = (size_t)3 * RANS_REC * rec.nf;
-        if (need > c->rans_rec.size()) {
-          HIPCHK(hipStreamSynchronize(c->stream));     // (before the old one is freed)
-          HIPCHK(c->rans_rec.alloc(need));
-        }
-        rec.p = c->rans_rec.get();
-        const dim3 tb = CELL_BLOCK;
-        auto fgrid = [&](int di, int dj, int dk) {
-          return dim3((vb.ni + di + tb.x - 1) / tb.x, (vb.nj + dj + tb.y - 1) / tb.y, vb.nk + dk);
-        };
-        hipLaunchKernelGGL(k_rans_faces<0>, fgrid(1, 0, 0), tb, 0, c->stream, vb, c->gas, fourth, rec);
-        hipLaunchKernelGGL(k_rans_faces<1>, fgrid(0, 1, 0), tb, 0, c->stream, vb, c->gas, fourth, rec);
-        hipLaunchKernelGGL(k_rans_faces<2>, fgrid(0, 0, 1), tb, 0, c->stream, vb, c->gas, fourth, rec);
-        hipLaunchKernelGGL(k_rans_cells, cell_grid(vb, tb), tb, 0, c->stream, vb, c->gas, c->sp,
-                           cfl, fourth, rec);
-      }
-#else
-    {
-      const bool fourth = c->cfg.viscous_recon == AGX_VISC_RECON_CENTRAL_4TH;
-      const bool wide_plane = (double)blk.d.nplane * 8.0 >= 4294967296.0;
-      if (!AGX_FAST || c->visc_gather || ((fourth || c->sp.les) && (c->visc_march || wide_plane))) {
-        // (one thread per cell, the stencil straight from the planes: AGX_VISC=gather, and
-        // centralFourth or largeEddySimulation -- k_visc_march has no WALE arm -- where the
-        // tile kernel's 32-bit plane offsets do not reach)
-        hipLaunchKernelGGL(c->sp.les ? k_visc_residual_les : k_visc_residual,
-                           cell_grid(blk.d, CELL_BLOCK), CELL_BLOCK, 0, c->stream, blk.d, c->gas,
-                           c->sp, cfl, fourth ? 1 : 0);
-      } else {
-        const BlockDev& vb = blk.d;
-        if (c->visc_march || wide_plane) {
-          const int gx = (vb.ni + VTI - 1) / VTI, gy = (vb.nj + VTJ - 1) / VTJ;
-          int nz = std::max(1, std::min(vb.nk / 8, (int)std::lround(2048.0 / (gx * gy))));
-          const int kchunk = (vb.nk + nz - 1) / nz;
-          nz = (vb.nk + kchunk - 1) / kchunk;
-          hipLaunchKernelGGL(k_visc_march, dim3(gx, gy, nz), dim3(64, VTJ + 1), 0, c->stream,
-                             vb, c->gas, c->sp, cfl, kchunk);
-          continue;
-        }
-#if AGX_FAST
-        // 62 x 6 owned cells per workgroup and k-step (centralFourth: 60 x 6); persistent
-        // workgroups, one per CU (the kernel's LDS windows fill a CU), each marching its share
-        // of the (column tile, k) steps by the plan (agx_tile_plan.hpp)
-        const int gx = tile_count(vb.ni, fourth ? TILE_VISC_I_F4 : TILE_VISC_I);
-        const int gy = tile_count(vb.nj, TILE_J);
-        const long steps = (long)gx * gy * vb.nk;
-        const int nwg = (int)std::min<long>(c->num_cu, std::max<long>(1, steps / 8));
-        const TilePlan tp = tile_plan_of(c, gx, gy, vb.nk, nwg,
-                                         fourth ? TILE_CHARGE_VISC_F4 : TILE_CHARGE_VISC,
-                                         c->tile_order_visc);
-        if (!fourth && rhs_form_applies(c, blk)) {
-          // the RHS forms: the residual norms from here, VT_R partials per workgroup, folded
-          // into prepare's slot right behind the launch (the partials are one area for all
-          // blocks) -- and inside agx_iterate b, 1 / a and the aInv_ plane as well
-          if (c->in_iterate) {
-            c->sp.un_is_u = 1;        // (as implicit_begin sets it: state_is_time_n holds)
-            VtRhs<VT_RHS_FULL> rz;
-            rz.partials = c->partials.get();
-            rz.pab = reinterpret_cast<char*>(vb.d2.base + 2L * PA_B * vb.d2.nd2);
-            rz.arr16 = vb.d2.nd2 * 16;
-            rz.ps16 = vb.d2.ps * 16;
-            rz.Pi = vb.d2.Pi;
-            rz.Pj = vb.d2.Pj;
-            hipLaunchKernelGGL((k_visc_tile<false, false, VT_RHS_FULL>), dim3(nwg),
-                               dim3(VT_L, VT_R), 0, c->stream, make_slab(vb), c->gas, c->sp, cfl,
-                               gx, tp, rz);
-            rhs_written_by_residual(blk);
-          } else {
-            hipLaunchKernelGGL((k_visc_tile<false, false, VT_RHS_NORMS>), dim3(nwg),
-                               dim3(VT_L, VT_R), 0, c->stream, make_slab(vb), c->gas, c->sp, cfl,
-                               gx, tp, VtRhs<VT_RHS_NORMS>{c->partials.get()});
-          }
-          const size_t n = (size_t)(&blk - c->blocks.data());
-          if (reduce_norms(c, n, (long)nwg * VT_R, c->norm_prepare() + n)) return 1;
-          resid_norms_folded(blk);
-          continue;
-        }
-        // (largeEddySimulation: the instantiations with the WALE arm, which also write the
-        // run's eddy-viscosity plane)
-        by_bool(c->sp.les != 0, [&](auto les) {
-          by_bool(fourth, [&](auto f4) {
-            hipLaunchKernelGGL((k_visc_tile<f4, decltype(les)::value>), dim3(nwg),
-                               dim3(VT_L, VT_R), 0, c->stream, make_slab(vb), c->gas, c->sp, cfl,
-                               gx, tp, VtRhs<VT_RHS_NONE>{});
-          });
-        });
-#endif
-      }
-    }
-#endif  // AGX_NEQ == 7
+      if (launch_visc(c, blk, cfl)) return 1;
 #if AGX_NEQ != 7     // (the rans viscous kernel accumulates its Jacobians itself)
     if (c->sp.implicit && c->sp.block)
       for (auto& blk : c->blocks)
@@ -3202,8 +3219,7 @@ static int d2_prepare(agx_ctx* c, Block& blk, int write_x, int again, int norms)
   const BlockDev& b = blk.d;
   const dim3 grid((b.d2.Pi + TT - 1) / TT, (b.d2.Pj + TT - 1) / TT, b.nk + 2 * b.ng);
   const bool lean = blk.d2_state_current && !again;
-  int ghost_s = 0;
-  for (int q = 0; q < 6; ++q) ghost_s |= b.side_conn[q] != 0;
+  const int ghost_s = has_connection(b) ? 1 : 0;
   const unsigned tag = write_x ? (unsigned)(++blk.kp_epoch) & 3u : 0u;
   by_bool(lean, [&](auto is_lean) {
     by_bool(norms != 0, [&](auto with_norms) {
@@ -3246,9 +3262,7 @@ static int implicit_begin(agx_ctx* c, int write_x) {
     if (b.d2.base) {
       // diagonal terms, b and x0 straight into the D2 arrays of the sweeps (a coarse
       // multigrid level, write_x = 0: x is the restricted one)
-      bool conn = false;
-      for (int q = 0; q < 6; ++q) conn = conn || b.side_conn[q] != 0;
-      const int wx = write_x && (c->sp.requires_init || conn) ? 1 : 0;
+      const int wx = write_x && (c->sp.requires_init || has_connection(b)) ? 1 : 0;
       // (the norms ride along on the finest level's launch only: a coarse multigrid level,
       // write_x = 0, keeps the update's fold; not where the viscous tile kernel of this
       // residual folded them already)

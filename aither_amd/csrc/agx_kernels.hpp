@@ -202,6 +202,14 @@ __device__ __forceinline__ void load_area(const BlockDev& b, int d, long q, doub
 #pragma unroll
   for (int c = 0; c < 4; ++c) a[c] = b.fa[d][c][q];
 }
+// The cell of a thread of the one-thread-per-cell launches (threads over i and j, blockIdx.z
+// is k); false: the thread has no cell.
+__device__ __forceinline__ bool cell_ijk(const BlockDev& b, int& i, int& j, int& k) {
+  i = blockIdx.x * blockDim.x + threadIdx.x;
+  j = blockIdx.y * blockDim.y + threadIdx.y;
+  k = blockIdx.z;
+  return i < b.ni && j < b.nj;
+}
 
 // ---------------------------------------------------------------------------
 // Inviscid residual, one thread per cell (gather form): the six face fluxes
@@ -261,10 +269,8 @@ __device__ __forceinline__ void face_flux_1d(const GasDev& g, double kappa,
 template <int RECON, int LIM>
 __global__ void __launch_bounds__(256)
 k_block_diag_inv(BlockDev b, GasDev g, SolverDev sp) {
-  const int i = blockIdx.x * blockDim.x + threadIdx.x;
-  const int j = blockIdx.y * blockDim.y + threadIdx.y;
-  const int k = blockIdx.z;
-  if (i >= b.ni || j >= b.nj) return;
+  int i, j, k;
+  if (!cell_ijk(b, i, j, k)) return;
   constexpr int H = RECON == AGX_RECON_CONSTANT ? 1
                     : (RECON == AGX_RECON_MUSCL ? 2 : 3);
   constexpr int NS = 2 * H + 1;
@@ -311,10 +317,8 @@ k_block_diag_inv(BlockDev b, GasDev g, SolverDev sp) {
 template <int RECON, int LIM, int FLUX>
 __global__ void __launch_bounds__(256)
 k_inv_residual(BlockDev b, GasDev g, SolverDev sp, double cfl) {
-  const int i = blockIdx.x * blockDim.x + threadIdx.x;
-  const int j = blockIdx.y * blockDim.y + threadIdx.y;
-  const int k = blockIdx.z;
-  if (i >= b.ni || j >= b.nj) return;
+  int i, j, k;
+  if (!cell_ijk(b, i, j, k)) return;
   constexpr int H = RECON == AGX_RECON_CONSTANT ? 1
                     : (RECON == AGX_RECON_MUSCL ? 2 : 3);
   constexpr int NS = 2 * H + 1;
@@ -1406,10 +1410,8 @@ __device__ __forceinline__ void visc_face(const BlockDev& b, const GasDev& g,
 // (:1397, :1432), which the off-diagonal terms of the neighbours read.
 __global__ void __launch_bounds__(256)
 k_block_diag_visc(BlockDev b, GasDev g, SolverDev sp, int fourth) {
-  const int i = blockIdx.x * blockDim.x + threadIdx.x;
-  const int j = blockIdx.y * blockDim.y + threadIdx.y;
-  const int k = blockIdx.z;
-  if (i >= b.ni || j >= b.nj) return;
+  int i, j, k;
+  if (!cell_ijk(b, i, j, k)) return;
   const long q = b.idx(i, j, k);
   double D[AGX_NJ], vg[9];
 #pragma unroll
@@ -1447,10 +1449,8 @@ k_block_diag_visc(BlockDev b, GasDev g, SolverDev sp, int fourth) {
 
 __global__ void __launch_bounds__(256)
 k_visc_residual(BlockDev b, GasDev g, SolverDev sp, double cfl, int fourth) {
-  const int i = blockIdx.x * blockDim.x + threadIdx.x;
-  const int j = blockIdx.y * blockDim.y + threadIdx.y;
-  const int k = blockIdx.z;
-  if (i >= b.ni || j >= b.nj) return;
+  int i, j, k;
+  if (!cell_ijk(b, i, j, k)) return;
   const long q = b.idx(i, j, k);
   double res[AGX_NEQ];
   load5(b.resid, q, res);
@@ -1530,10 +1530,8 @@ __device__ __forceinline__ void visc_residual_cell_les(const BlockDev& b, const 
 }
 __global__ void __launch_bounds__(256)
 k_visc_residual_les(BlockDev b, GasDev g, SolverDev sp, double cfl, int fourth) {
-  const int i = blockIdx.x * blockDim.x + threadIdx.x;
-  const int j = blockIdx.y * blockDim.y + threadIdx.y;
-  const int k = blockIdx.z;
-  if (i >= b.ni || j >= b.nj) return;
+  int i, j, k;
+  if (!cell_ijk(b, i, j, k)) return;
   visc_residual_cell_les(b, g, sp, cfl, fourth, b.idx(i, j, k));
 }
 #endif
@@ -1938,10 +1936,8 @@ __device__ inline void rans_cell_finish(const BlockDev& b, const GasDev& g, cons
 // form the face-once kernels below are tested against (AGX_RANS_VISC=gather).
 __global__ void __launch_bounds__(256)
 k_visc_residual_rans(BlockDev b, GasDev g, SolverDev sp, double cfl, int fourth) {
-  const int i = blockIdx.x * blockDim.x + threadIdx.x;
-  const int j = blockIdx.y * blockDim.y + threadIdx.y;
-  const int k = blockIdx.z;
-  if (i >= b.ni || j >= b.nj) return;
+  int i, j, k;
+  if (!cell_ijk(b, i, j, k)) return;
   const long q = b.idx(i, j, k);
   RansCell c;
   double D[AGX_NJ], Dt[2];
@@ -2009,10 +2005,8 @@ k_rans_faces(BlockDev b, GasDev g, int fourth, RansRec rec) {
 }
 __global__ void __launch_bounds__(256, RANS_CELLS_WAVES)
 k_rans_cells(BlockDev b, GasDev g, SolverDev sp, double cfl, int fourth, RansRec rec) {
-  const int i = blockIdx.x * blockDim.x + threadIdx.x;
-  const int j = blockIdx.y * blockDim.y + threadIdx.y;
-  const int k = blockIdx.z;
-  if (i >= b.ni || j >= b.nj) return;
+  int i, j, k;
+  if (!cell_ijk(b, i, j, k)) return;
   const long q = b.idx(i, j, k);
   RansCell c;
   double D[AGX_NJ], Dt[2];
@@ -2496,10 +2490,8 @@ __global__ void __launch_bounds__(256)
 k_update(BlockDev b, GasDev g, SolverDev sp, int mode, double alpha, int last_mm,
          NormPartial* partials) {
   // mode: 0 explicit Euler, 1 RK stage, 2 implicit
-  const int i = blockIdx.x * blockDim.x + threadIdx.x;
-  const int j = blockIdx.y * blockDim.y + threadIdx.y;
-  const int k = blockIdx.z;
-  const bool active = i < b.ni && j < b.nj;
+  int i, j, k;
+  const bool active = cell_ijk(b, i, j, k);
   double r[AGX_NEQ] = {0, 0, 0, 0, 0};
   if (active) {
     const long q = b.idx(i, j, k);
@@ -2567,10 +2559,8 @@ __global__ void k_norm_final(const NormPartial* partials, long n, NormPartial* o
 // procBlock::AssignSolToTimeN / AssignSolToTimeNm1 procBlock.cpp:1037-1054
 __global__ void __launch_bounds__(256)
 k_store_time_n(BlockDev b, GasDev g, int also_nm1) {
-  const int i = blockIdx.x * blockDim.x + threadIdx.x;
-  const int j = blockIdx.y * blockDim.y + threadIdx.y;
-  const int k = blockIdx.z;
-  if (i >= b.ni || j >= b.nj) return;
+  int i, j, k;
+  if (!cell_ijk(b, i, j, k)) return;
   const long q = b.idx(i, j, k);
   double s[AGX_NEQ], u[AGX_NEQ];
   load5(b.state, q, s);
@@ -2830,10 +2820,8 @@ __device__ __forceinline__ void add_off_diag_rec(const BlockDev& b, const GasDev
 // InitializeMatrixUpdate :111-144
 __global__ void __launch_bounds__(256)
 k_implicit_begin(BlockDev b, GasDev g, SolverDev sp, int* err, int write_x) {
-  const int i = blockIdx.x * blockDim.x + threadIdx.x;
-  const int j = blockIdx.y * blockDim.y + threadIdx.y;
-  const int k = blockIdx.z;
-  if (i >= b.ni || j >= b.nj) return;
+  int i, j, k;
+  if (!cell_ijk(b, i, j, k)) return;
   const long q = b.idx(i, j, k);
   if (b.sw_rhs) {       // the right-hand side, cell-major, for the plane-by-plane sweeps
     double rb[AGX_NEQ];
@@ -3255,10 +3243,8 @@ template <int MODE>
 __global__ void __launch_bounds__(256)
 k_dplur(BlockDev b, GasDev g, SolverDev sp_, int wait_mask) {
   const SolverDev sp = solver_mode<MODE>(sp_);
-  const int i = blockIdx.x * blockDim.x + threadIdx.x;
-  const int j = blockIdx.y * blockDim.y + threadIdx.y;
-  const int k = blockIdx.z;
-  if (i >= b.ni || j >= b.nj) return;
+  int i, j, k;
+  if (!cell_ijk(b, i, j, k)) return;
   if (wait_mask && dplur_waits(b, wait_mask, i, j, k)) return;
   dplur_cell(b, g, sp, i, j, k);
 }
@@ -3292,10 +3278,8 @@ template <int MODE>
 __global__ void __launch_bounds__(256)
 k_matrix_resid(BlockDev b, GasDev g, SolverDev sp_, NormPartial* partials) {
   const SolverDev sp = solver_mode<MODE>(sp_);
-  const int i = blockIdx.x * blockDim.x + threadIdx.x;
-  const int j = blockIdx.y * blockDim.y + threadIdx.y;
-  const int k = blockIdx.z;
-  const bool active = i < b.ni && j < b.nj;
+  int i, j, k;
+  const bool active = cell_ijk(b, i, j, k);
   double r[AGX_NEQ] = {0, 0, 0, 0, 0};
   if (active) {
     const long q = b.idx(i, j, k);
@@ -3345,10 +3329,8 @@ struct MgMap {
 // what 0: state, volume weighted; 1: x, volume weighted; 2: matrix residual -> forcing, summed
 __global__ void __launch_bounds__(256)
 k_mg_restrict(BlockDev f, BlockDev c, MgMap m, int what) {
-  const int i = blockIdx.x * blockDim.x + threadIdx.x;
-  const int j = blockIdx.y * blockDim.y + threadIdx.y;
-  const int k = blockIdx.z;
-  if (i >= c.ni || j >= c.nj) return;
+  int i, j, k;
+  if (!cell_ijk(c, i, j, k)) return;
   double acc[AGX_NEQ];
 #pragma unroll
   for (int e = 0; e < AGX_NEQ; ++e) acc[e] = 0.0;
@@ -3376,10 +3358,8 @@ k_mg_restrict(BlockDev f, BlockDev c, MgMap m, int what) {
 // forcing += A x - b of the level (linearSolver::AXmB :58-90, gridLevel.cpp:579-589)
 __global__ void __launch_bounds__(256)
 k_mg_axmb(BlockDev b, GasDev g, SolverDev sp) {
-  const int i = blockIdx.x * blockDim.x + threadIdx.x;
-  const int j = blockIdx.y * blockDim.y + threadIdx.y;
-  const int k = blockIdx.z;
-  if (i >= b.ni || j >= b.nj) return;
+  int i, j, k;
+  if (!cell_ijk(b, i, j, k)) return;
   const long q = b.idx(i, j, k);
   double acc[AGX_NEQ] = {0, 0, 0, 0, 0}, rb[AGX_NEQ], xc[AGX_NEQ];
   add_off_diag(b, g, sp, b.x, i, j, k, q, true, 1.0, acc);

@@ -306,6 +306,49 @@ def test_tile_unfused_instances_viscous(agx, oracle, recon, lim, flux):
     _pair(agx, oracle, case, 2)
 
 
+MARCH_N = (70, 7, 5)       # past one 64-wide tile in i and one 6-row tile in j, a short k-chunk
+
+
+def test_march_fused_norms_against_the_update_pass(agx):
+    """k_residual_march<.., FUSE = true, 6> (AGX_KERNEL=march) folds the residual norms itself;
+    with AGX_NO_FUSE=1 the same kernel leaves the stage and the norms to k_update.  An RK4 stage
+    is consVarsN - fac * residual, one product and the same fused multiply-add in both kernels,
+    so the states are equal bit for bit, both runs form the same residuals, and the L-inf value
+    and its location are equal (a maximum with its first location does not depend on the order
+    of the fold).  The two passes add the same n = 2450 non-negative squares per equation in two
+    orders: each sum is within (n - 1) u of the exact one, relatively, hence the two within
+    2 (n - 1) u of each other, u = 2^-53.  Three steps, twelve stages, each compared.
+    (explicitEuler is not run here: its stage rho v - fac * residual has two products, the
+    fused kernels and k_update round them differently by an ulp)"""
+    case = synthetic.single_block_case(n=MARCH_N, stretch=1.1, skew=0.01,
+                                       time_integration="rk4", cfl=0.4)
+    n = MARCH_N[0] * MARCH_N[1] * MARCH_N[2]
+    bound = 2 * (n - 1) * 2.0 ** -53
+    runs = []
+    for env in ({"AGX_KERNEL": "march"}, {"AGX_KERNEL": "march", "AGX_NO_FUSE": "1"}):
+        with switches(env):
+            s = Solver(agx, case)
+        out = []
+        for nn in range(3):
+            s.store_time_n(nn)
+            for mm in range(case.deck.nonlinear_iterations):
+                l2, linf, _ = s.iterate(mm, case.deck.cfl(nn))
+                out.append((l2, (linf.linf, linf.block, linf.i, linf.j, linf.k, linf.eqn)))
+        g = case.ng        # (ghost cells hold whatever the last ghost fill left there)
+        runs.append((out, s.download("state", 0)[g:-g, g:-g, g:-g]))
+        s.close()
+    (fused, state_f), (plain, state_p) = runs
+    assert np.all(np.isfinite(state_f))
+    assert np.array_equal(state_f, state_p)
+    assert len(fused) == len(plain) == 12
+    for it, ((l2f, linf_f), (l2p, linf_p)) in enumerate(zip(fused, plain)):
+        assert linf_f == linf_p, (it, linf_f, linf_p)
+        assert np.all(l2p > 0.0)
+        err = np.abs(l2f - l2p) / l2p
+        print("march fused l2", it, err.max())
+        assert err.max() <= bound, (it, err, bound)
+
+
 THIN_SHAPES = [(1, 1, 40), (33, 1, 2), (2, 3, 1), (65, 5, 3)]
 _IMPL = dict(time_integration="implicitEuler", cfl=5.0)
 _VISC = dict(bcs=WALL_J, equation_set="navierStokes", matrix_solver="lusgs", **_IMPL)
