@@ -169,6 +169,9 @@ SYMBOLS = {
     "field_upload": (_i, [_vp, _i, _i, c_dp]),
     "output_pack": (_i, [_vp, _i, _i, C.POINTER(C.c_int32), c_dp]),
     "restart_pack": (_i, [_vp, _i, _i, c_dp]),
+    "state_fill": (_i, [_vp, _i, c_dp]),
+    "state_from_cloud": (_i, [_vp, _i, C.c_int64, c_dp, c_dp, c_dp]),
+    "restart_unpack": (_i, [_vp, _i, _i, c_dp]),
     "plot3d_metrics": (_i, [_vp, _i, _i, _i] + [c_dp] * 9),
     "nearest_wall_distance": (_i, [_vp, C.c_int64, c_dp, C.c_int64, c_dp, c_dp]),
     "mg_restrict": (_i, [_vp, _vp, _i, _i, C.POINTER(C.c_int32), c_dp]),
@@ -203,16 +206,32 @@ SYMBOLS = {
 }
 
 
+# Entries that form data on the device and have no host counterpart in the CPU oracle of the
+# test suite (the start and resume of a run: the host arrays they replace are the reference
+# there).  The product library must export them like every other entry; under any other prefix
+# a library may lack them, and the bound name then refuses by name when it is called.
+DEVICE_ONLY = ("state_fill", "state_from_cloud", "restart_unpack")
+
+
 class Api:
     """Namespace of bound functions without the prefix."""
 
     def __init__(self, lib, prefix):
         self.lib, self.prefix = lib, prefix
         for name, (res, args) in SYMBOLS.items():
+            if name in DEVICE_ONLY and prefix != "agx_" and not hasattr(lib, prefix + name):
+                setattr(self, name, self._not_exported(name))
+                continue
             fn = getattr(lib, prefix + name)   # AttributeError if missing
             fn.restype = res
             fn.argtypes = args
             setattr(self, name, fn)
+
+    def _not_exported(self, name):
+        def refuse(*_args):
+            raise NotImplementedError(f"{self.prefix}{name}: this library does not export it "
+                                      "(a device-only entry, abi.DEVICE_ONLY)")
+        return refuse
 
     def check(self, rc, what=""):
         if rc != 0:

@@ -16,10 +16,22 @@ from .. import abi
 
 
 @dataclass
+class StateRecipe:
+    """What a block's initial state is made from, in place of the ghost-padded array
+    (build_case, initial="device"): kind "uniform" with prim[n_eq] (initial_primitive), or
+    kind "cloud" with the pts[npts, 3], st[npts, n_eq] of cloud_states.  A Solver realises it
+    on the device (agx_state_fill / agx_state_from_cloud); realise() gives the host array."""
+    kind: str
+    prim: np.ndarray = None
+    pts: np.ndarray = None
+    st: np.ndarray = None
+
+
+@dataclass
 class Block:
     geom: "_geo.BlockGeometry"
     surfaces: list
-    state: np.ndarray          # [nk+2g, nj+2g, ni+2g, n_eq]
+    state: object              # [nk+2g, nj+2g, ni+2g, n_eq], or a StateRecipe
     parent: int = 0
     global_pos: int = 0
     rank: int = 0
@@ -123,8 +135,13 @@ def cloud_states(deck, gas, path):
 def initial_from_cloud(deck, gas, geom, path):
     """procBlock::InitializeStates, file branch (procBlock.cpp:287-320): every physical
     cell takes the state of the cloud point nearest to its centre."""
-    from scipy.spatial import cKDTree
     pts, st = cloud_states(deck, gas, path)
+    return nearest_cloud_state(geom, pts, st)
+
+
+def nearest_cloud_state(geom, pts, st):
+    """The physical cells' states [nk, nj, ni, n_eq] from a cloud: scipy's k-d tree."""
+    from scipy.spatial import cKDTree
     ng = geom.ng
     if isinstance(geom, _geo.NodeGeometry):     # (the centroids alone, plot3d.cpp:35-43)
         x = geom.nodes
@@ -213,22 +230,52 @@ def _wall_distance(blocks, nearest=None):
                     sign * wd.v(rs["i"], rs["j"], rs["k"])
 
 
+def padded_state(geom, prim):
+    """The host layout of a block's state: prim (one state, or [nk, nj, ni, n_eq]) in the
+    physical cells, zero in the ghost cells."""
+    ng = geom.ng
+    prim = np.asarray(prim, dtype=np.float64)
+    st = np.zeros((geom.nk + 2 * ng, geom.nj + 2 * ng, geom.ni + 2 * ng, prim.shape[-1]))
+    st[ng:ng + geom.nk, ng:ng + geom.nj, ng:ng + geom.ni, :] = prim
+    return st
+
+
+def realise(recipe, geom):
+    """The ghost-padded host array a StateRecipe stands for, by the host path's own code
+    (the uniform state, or scipy's k-d tree over the cloud): what build_case's default
+    initial="host" puts into Block.state."""
+    if recipe.kind == "uniform":
+        return padded_state(geom, recipe.prim)
+    if recipe.kind == "cloud":
+        return padded_state(geom, nearest_cloud_state(geom, recipe.pts, recipe.st))
+    raise ValueError(f"state recipe of kind {recipe.kind!r}: 'uniform' or 'cloud'")
+
+
 def build_case(inp_path, grid_dir=None, deck=None, coords=None, ranks=None, setup=None,
-               geometry="host"):
+               geometry="host", initial="host"):
     """Build a Case from an .inp file (and its .xyz grid).  `deck`/`coords`
     may be given directly for synthetic cases.  setup: a solver.DeviceSetup -- the
     volume-sized parts (metrics, wall distance) then run in the library.
     geometry="device": the blocks carry their nodes, sizes, surfaces and initial state and
     no metric arrays (geometry.NodeGeometry); the library forms the whole geometry on the
     device when a Solver creates them (agx_block_geom.nodes), SwapGeomSlice's border update
-    of the connections included.  Connections are still found here."""
+    of the connections included.  Connections are still found here.
+    initial="device": the blocks carry a StateRecipe in place of the ghost-padded state array
+    (the uniform icState's primitive, or the points and states of the cloud file); a Solver
+    realises it in the library (agx_state_fill, agx_state_from_cloud), realise() on the host.
+    Single grid level only: the coarsening of case.multigrid works on the arrays."""
     if geometry not in ("host", "device"):
         raise ValueError(f"geometry={geometry!r}: 'host' or 'device'")
+    if initial not in ("host", "device"):
+        raise ValueError(f"initial={initial!r}: 'host' or 'device'")
     if geometry == "device" and ranks is not None and len(set(ranks)) > 1:
         raise NotImplementedError("geometry='device' with blocks on several ranks: ghost "
                                   "geometry and wall points would have to cross ranks")
     if deck is None:
         deck = parse_input(inp_path)
+    if initial == "device" and deck.multigrid_levels != 1:
+        raise NotImplementedError("initial='device' with multigridLevels != 1: the coarse "
+                                  "levels' states are restricted from the state arrays")
     deck.validate()
     fluid_name = deck.fluids[0] if deck.fluids else "air"
     gas = _fluid.make_gas(fluid_name, deck.t_ref, deck.rho_ref, deck.l_ref,
@@ -258,11 +305,11 @@ def build_case(inp_path, grid_dir=None, deck=None, coords=None, ranks=None, setu
         ic_file = deck.ic_for_block(b).get("file")
         if ic_file is not None:       # (relative to the case directory, as the reference runs)
             base = grid_dir or os.path.dirname(os.path.abspath(inp_path))
-            prim = initial_from_cloud(deck, gas, g, os.path.join(base, ic_file))
+            pts, cst = cloud_states(deck, gas, os.path.join(base, ic_file))
+            recipe = StateRecipe("cloud", pts=pts, st=cst)
         else:
-            prim = initial_primitive(deck, gas, b)
-        st = np.zeros((g.nk + 2 * ng, g.nj + 2 * ng, g.ni + 2 * ng, prim.shape[-1]))
-        st[ng:ng + g.nk, ng:ng + g.nj, ng:ng + g.ni, :] = prim
+            recipe = StateRecipe("uniform", prim=initial_primitive(deck, gas, b))
+        st = recipe if initial == "device" else realise(recipe, g)
         blocks.append(Block(g, deck.bcs[b], st, b, b, ranks[b], local_pos[b]))
         total += g.ni * g.nj * g.nk
     conns = _conn.find_connections(deck.bcs, coords, deck, ranks, local_pos)

@@ -139,28 +139,30 @@ def box_surfaces(ni, nj, nk, bcs=None):
 
 
 def single_block_case(n=(16, 16, 16), stretch=1.0, skew=0.0, bcs=None,
-                      amplitude=0.05, setup=None, geometry="host", **deck_kw):
+                      amplitude=0.05, setup=None, geometry="host", initial="host", **deck_kw):
     """geometry="device" (builder.build_case): no cell centres on the host, so the state is
-    left uniform whatever `amplitude` says (perturbed_state reads the centres)."""
+    left uniform whatever `amplitude` says (perturbed_state reads the centres); so it is with
+    initial="device", where there is no state array to perturb."""
     ni, nj, nk = n
     deck = make_deck(**deck_kw)
     deck.bcs = [box_surfaces(ni, nj, nk, bcs)]
     coords = [box_nodes(ni, nj, nk, stretch, skew=skew)]
-    case = _b.build_case(None, deck=deck, coords=coords, setup=setup, geometry=geometry)
-    if amplitude and geometry == "host":
+    case = _b.build_case(None, deck=deck, coords=coords, setup=setup, geometry=geometry,
+                         initial=initial)
+    if amplitude and geometry == "host" and initial == "host":
         perturbed_state(case, amplitude)
     return case
 
 
 def stacked_blocks_case(n=(16, 16, 16), nblocks=2, axis="k", stretch=1.0,
                         bcs=None, amplitude=0.05, ranks=None, setup=None, geometry="host",
-                        **deck_kw):
+                        initial="host", **deck_kw):
     """nblocks boxes stacked along `axis`, joined by interblock connections
     (orientation 1, lower <-> upper)."""
     deck, coords = _stacked(n, nblocks, axis, stretch, bcs, deck_kw)
     case = _b.build_case(None, deck=deck, coords=coords, ranks=ranks, setup=setup,
-                         geometry=geometry)
-    if amplitude and geometry == "host":
+                         geometry=geometry, initial=initial)
+    if amplitude and geometry == "host" and initial == "host":
         perturbed_state(case, amplitude)
     return case
 
@@ -209,7 +211,7 @@ def _stacked(n, nblocks, axis, stretch, bcs, deck_kw):
 
 
 def cube_blocks_case(n=(8, 8, 8), splits=(2, 2, 2), bcs=None, amplitude=0.05,
-                     ranks=None, setup=None, geometry="host", **deck_kw):
+                     ranks=None, setup=None, geometry="host", initial="host", **deck_kw):
     """splits[0] x splits[1] x splits[2] boxes of n cells each tiling one box
     (BASELINE configs[3] style: 2x2x2 = 8 blocks), joined face to face by
     interblock connections; block id = bi + si * (bj + sj * bk)."""
@@ -236,7 +238,7 @@ def cube_blocks_case(n=(8, 8, 8), splits=(2, 2, 2), bcs=None, amplitude=0.05,
                 all_bcs.append(box_surfaces(ni, nj, nk, blk))
     deck.bcs = all_bcs
     case = _b.build_case(None, deck=deck, coords=coords, ranks=ranks, setup=setup,
-                         geometry=geometry)
-    if amplitude and geometry == "host":
+                         geometry=geometry, initial=initial)
+    if amplitude and geometry == "host" and initial == "host":
         perturbed_state(case, amplitude)
     return case

@@ -7,6 +7,7 @@
 // path here: every entry point fails loudly if HIP is unavailable.
 #include "agx_kernels.hpp"
 #include "agx_geometry.hpp"
+#include "agx_start.hpp"
 #include "agx_mem.hpp"
 #include "agx_switches.hpp"
 #include <rccl/rccl.h>
@@ -2697,6 +2698,131 @@ int agx_restart_pack(agx_ctx* c, int id, int which, double* out) {
   hipLaunchKernelGGL(k_restart_pack, cell_grid(b.d, CELL_BLOCK), CELL_BLOCK, 0, c->stream, b.d,
                      out_spec(c, b), which, tmp);
   return copy_out(c, out, tmp, (size_t)(AGX_NEQ + 1) * ncell);
+}
+
+// ---- start and resume on the device (agx_start.hpp) ------------------------------------------
+namespace {
+// what the three entries refuse alike, in this order; nothing has been touched when they do
+int start_refused(agx_ctx* c, int id, const char* who, const void* p0, const void* p1 = "") {
+  if (!c->finalized) return fail("%s: agx_setup_finalize has not been called", who);
+  if (id < 0 || id >= (int)c->blocks.size()) return fail("bad block id %d", id);
+  if (!p0 || !p1) return fail("%s: null pointer", who);
+  return 0;
+}
+// the reference's "nonphysical density / pressure" asserts (procBlock.cpp:304-305, :329-330)
+// on one nondimensional primitive state; row < 0: the state of agx_state_fill
+int start_state_refused(const char* who, const double* s, long row) {
+  char where[48] = "";
+  if (row >= 0) snprintf(where, sizeof where, " (cloud state %ld)", row);
+  for (int e = 0; e < AGX_NEQ; ++e)
+    if (!std::isfinite(s[e])) return fail("%s: non-finite value%s", who, where);
+  if (!(s[0] > 0.0)) return fail("%s: nonphysical density%s", who, where);
+  if (!(s[4] > 0.0)) return fail("%s: nonphysical pressure%s", who, where);
+  return 0;
+}
+// the bookkeeping of agx_state_upload before it writes, and its tail after the state planes
+// have been written by a kernel here
+int start_state_begin(agx_ctx* c, Block& b) {
+  field_written_by_caller(c);
+  if (flush_consn(c)) return 1;
+  planes_uploaded(b);
+  return 0;
+}
+int start_state_end(agx_ctx* c, Block& b) {
+  HIPCHK(hipGetLastError());
+#if AGX_NEQ == 7
+  // (agx_state_upload: viscosity_ before the first iteration)
+  hipLaunchKernelGGL(k_aux_field, dim3((b.d.nplane + 255) / 256), dim3(256), 0, c->stream, b.d,
+                     c->gas, 1, b.d.viscp);
+  HIPCHK(hipGetLastError());
+#endif
+  HIPCHK(hipStreamSynchronize(c->stream));
+  return 0;
+}
+void start_fill(agx_ctx* c, Block& b, const StartPrim& prim, int physical) {
+  const BlockDev& d = b.d;
+  const long n = (long)(d.nk + 2 * d.ng) * (d.nj + 2 * d.ng) * d.sx;
+  hipLaunchKernelGGL(k_state_fill, geo_grid(n), dim3(256), 0, c->stream, d, prim, physical);
+}
+// the divisors of ReadSolFromRestart (output.cpp:1197-1222) / ReadSolNm1FromRestart
+// (:1262-1287), formed in the reference's order
+RestartDiv restart_divisors(const agx_ctx* c, int which) {
+  const double rR = c->cfg.gas.rho_ref, aR = c->cfg.gas.a_ref, muR = c->gas.mu_ref;
+  const double prim[7] = {rR, aR, aR, aR, rR * aR * aR, aR * aR, aR * aR * rR / muR};
+  const double cons[7] = {rR, aR * rR, aR * rR, aR * rR, rR * aR * aR, aR * aR * rR,
+                          aR * aR * rR * rR / muR};
+  RestartDiv dv;
+  dv.rho = rR;
+  for (int e = 0; e < AGX_NEQ; ++e) dv.v[e] = which == 0 ? prim[e] : cons[e];
+  return dv;
+}
+}  // namespace
+
+int agx_state_fill(agx_ctx* c, int id, const double* prim) {
+  if (start_refused(c, id, "agx_state_fill", prim)) return 1;
+  if (start_state_refused("agx_state_fill", prim, -1)) return 1;
+  Block& b = c->blocks[id];
+  if (start_state_begin(c, b)) return 1;
+  StartPrim pv;
+  for (int e = 0; e < AGX_NEQ; ++e) pv.v[e] = prim[e];
+  start_fill(c, b, pv, 1);
+  return start_state_end(c, b);
+}
+
+int agx_state_from_cloud(agx_ctx* c, int id, int64_t npts, const double* points,
+                         const double* states, double* max_dist) {
+  if (start_refused(c, id, "agx_state_from_cloud", points, states)) return 1;
+  if (npts < 1) return fail("agx_state_from_cloud: npts %lld < 1", (long long)npts);
+  for (int64_t r = 0; r < npts; ++r)
+    if (start_state_refused("agx_state_from_cloud", states + AGX_NEQ * r, (long)r)) return 1;
+  Block& b = c->blocks[id];
+  const BlockDev& d = b.d;
+  const long ncell = (long)d.ni * d.nj * d.nk;
+  constexpr int CPT = AGX_CLOUD_CPT;           // cells of a thread (k_cloud_nearest)
+  const long nwg = (ncell + 256 * CPT - 1) / (256 * CPT);
+  if (start_state_begin(c, b)) return 1;
+  double* buf = nullptr;
+  if (stage_buffer(c, (size_t)((3 + AGX_NEQ) * npts + nwg), &buf)) return 1;
+  double *dp = buf, *ds = buf + 3 * npts, *part = ds + AGX_NEQ * npts;
+  HIPCHK(hipMemcpyAsync(dp, points, sizeof(double) * 3 * npts, hipMemcpyHostToDevice, c->stream));
+  HIPCHK(hipMemcpyAsync(ds, states, sizeof(double) * AGX_NEQ * npts, hipMemcpyHostToDevice,
+                        c->stream));
+  start_fill(c, b, StartPrim{}, 0);
+  hipLaunchKernelGGL(k_cloud_nearest<CPT>, dim3((unsigned)nwg), dim3(256), 0, c->stream, d,
+                     (long)npts, dp, ds, part);
+  if (max_dist) {
+    std::vector<double> host((size_t)nwg);
+    if (copy_out(c, host.data(), part, (size_t)nwg)) return 1;
+    *max_dist = *std::max_element(host.begin(), host.end());
+  }
+  return start_state_end(c, b);
+}
+
+int agx_restart_unpack(agx_ctx* c, int id, int which, const double* in) {
+  if (start_refused(c, id, "agx_restart_unpack", in)) return 1;
+  if (which != 0 && which != 1)
+    return fail("agx_restart_unpack: which is 0 (state) or 1 (consVarsNm1)");
+  Block& b = c->blocks[id];
+  if (which == 1) {       // (what agx_field_upload refuses of this field, in its words)
+    double* const* p; int nc, gh;
+    if (field_info(b, AGX_FIELD_CONS_NM1, &p, &nc, &gh))
+      return fail("field %d cannot be uploaded", AGX_FIELD_CONS_NM1);
+  }
+  const BlockDev& d = b.d;
+  const long ncell = (long)d.ni * d.nj * d.nk;
+  if (start_state_begin(c, b)) return 1;
+  // the payload through the staging buffer of upload_aos
+  double* tmp = nullptr;
+  if (stage_buffer(c, (size_t)RST_NV * ncell, &tmp)) return 1;
+  HIPCHK(hipMemcpyAsync(tmp, in, sizeof(double) * RST_NV * ncell, hipMemcpyHostToDevice,
+                        c->stream));
+  if (which == 0) start_fill(c, b, StartPrim{}, 0);
+  hipLaunchKernelGGL(k_restart_unpack, geo_grid(ncell), dim3(256), 0, c->stream, d,
+                     restart_divisors(c, which), which, tmp);
+  if (which == 0) return start_state_end(c, b);
+  HIPCHK(hipGetLastError());
+  HIPCHK(hipStreamSynchronize(c->stream));
+  return 0;
 }
 
 // ---- set-up helpers -------------------------------------------------

@@ -169,7 +169,11 @@ class Solver:
             self.conn_ids.append(cid.value)
         api.check(api.setup_finalize(self.ctx), "setup_finalize")
         for gb, bid in self.block_ids.items():
-            self.upload("state", gb, case.blocks[gb].state)
+            st = case.blocks[gb].state
+            if isinstance(st, _b.StateRecipe):      # build_case(initial="device")
+                self.realise(gb, st)
+            else:
+                self.upload("state", gb, st)
         self.l2_first = None
         self.history = []
 
@@ -343,6 +347,48 @@ class Solver:
         self.api.check(self.api.restart_pack(self.ctx, self.block_ids[gb], which,
                                              out.ctypes.data_as(abi.c_dp)), "restart_pack")
         return out
+
+    # -- the state a run starts or resumes from, formed by the library ------------------
+    def state_fill(self, gb, prim):
+        """procBlock::InitializeStates, non-file branch: every physical cell of block gb takes
+        the nondimensional primitive prim[n_eq], every ghost cell zero (agx_state_fill)."""
+        p = np.ascontiguousarray(prim, dtype=np.float64)
+        assert p.shape == (self.cfg.n_eq,), p.shape
+        self.api.check(self.api.state_fill(self.ctx, self.block_ids[gb],
+                                           p.ctypes.data_as(abi.c_dp)), "state_fill")
+
+    def state_from_cloud(self, gb, pts, st):
+        """The file branch: every physical cell takes the state of the nearest of the cloud's
+        points (pts[npts, 3], st[npts, n_eq] of builder.cloud_states; among equally near points
+        the lowest index), every ghost cell zero.  Returns the reference's maxDist."""
+        pts = np.ascontiguousarray(pts, dtype=np.float64)
+        st = np.ascontiguousarray(st, dtype=np.float64)
+        assert pts.ndim == 2 and pts.shape[1] == 3 and st.shape == (len(pts), self.cfg.n_eq), \
+            (pts.shape, st.shape)
+        far = C.c_double(0.0)
+        self.api.check(self.api.state_from_cloud(
+            self.ctx, self.block_ids[gb], len(pts), pts.ctypes.data_as(abi.c_dp),
+            st.ctypes.data_as(abi.c_dp), C.byref(far)), "state_from_cloud")
+        return far.value
+
+    def restart_unpack(self, gb, payload, which=0):
+        """The inverse of restart_pack: a block's restart payload [nk, nj, ni, n_eq + 1],
+        nondimensionalised by the library into the state (which = 0, ghost cells zero) or
+        consVarsNm1 (which = 1)."""
+        g = self.case.blocks[gb].geom
+        ni, nj, nk = g.n
+        a = np.ascontiguousarray(payload, dtype=np.float64)
+        assert a.shape == (nk, nj, ni, self.cfg.n_eq + 1), a.shape
+        self.api.check(self.api.restart_unpack(self.ctx, self.block_ids[gb], which,
+                                               a.ctypes.data_as(abi.c_dp)), "restart_unpack")
+
+    def realise(self, gb, recipe):
+        """A builder.StateRecipe into the state of block gb, on the device."""
+        if recipe.kind == "uniform":
+            return self.state_fill(gb, recipe.prim)
+        if recipe.kind == "cloud":
+            return self.state_from_cloud(gb, recipe.pts, recipe.st)
+        raise ValueError(f"state recipe of kind {recipe.kind!r}: 'uniform' or 'cloud'")
 
     def download(self, field, gb):
         if field in abi.GEOM_FIELDS:

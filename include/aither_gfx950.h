@@ -518,6 +518,47 @@ int agx_output_pack(agx_ctx *ctx, int block, int nvar, const int32_t *vars, doub
  * solution of multilevel time integration: conserved variables, :700-750). */
 int agx_restart_pack(agx_ctx *ctx, int block, int which, double *out);
 
+/* ---- start and resume: the state a run starts from, formed on the device -------------
+ * After each of the three calls below the block is exactly as if the caller had made the
+ * matching upload of a host array -- agx_state_upload of the ghost-padded state with those
+ * physical cells and ZERO in every ghost cell, or (agx_restart_unpack, which = 1)
+ * agx_field_upload(AGX_FIELD_CONS_NM1) -- the same bits in the planes and the same
+ * bookkeeping.  They are legal wherever those uploads are, but only after
+ * agx_setup_finalize (the cloud search reads the cell centres, which a node-built block
+ * has from then on).  Refused with a message, the block untouched: a call before
+ * agx_setup_finalize, a bad block id, a null pointer, and what each entry names.
+ *
+ * procBlock::InitializeStates, non-file branch (procBlock.cpp:325-354): every physical cell
+ * takes prim[n_eq], the nondimensional primitive of primitive::NondimensionalInitialize
+ * (the caller forms these n_eq scalars; rans: k, omega of ApplyFarfieldTurbBC included).
+ * Refused: density <= 0, pressure <= 0 ("nonphysical density / pressure", :329-330), a
+ * non-finite value. */
+int agx_state_fill(agx_ctx *ctx, int block, const double *prim);
+/* file branch (procBlock.cpp:287-323; CalcTreeFromCloud utility.cpp:521-605,
+ * kdtree::NearestNeighbor kdtree.cpp:123-225): every physical cell takes states[id] of the
+ * cloud point nearest to its centre.  points[npts][3], states[npts][n_eq], nondimensional,
+ * host memory.  *max_dist (may be NULL): the largest distance from a cell centre to its
+ * point, the reference's maxDist (without its floor of DBL_MIN: 0 where every centre is a
+ * cloud point).
+ * TIE RULE: among points at equal squared distance the LOWEST index wins (the reference's
+ * k-d tree leaves ties to its build order).
+ * The search is exhaustive, tiled through LDS: its work is cells x points.  128^3 cells x
+ * 1e5 points is the size it is meant for (DESIGN section 8 has the measured time); a cloud
+ * the size of a 256^3 grid against such a grid is over a thousand times that work and keeps the host's
+ * k-d tree (case.builder, initial="host").
+ * Refused: npts < 1; a cloud state with density <= 0, pressure <= 0 (:304-305) or a
+ * non-finite value (a host scan of the npts rows before anything is written). */
+int agx_state_from_cloud(agx_ctx *ctx, int block, int64_t npts, const double *points,
+                         const double *states, double *max_dist);
+/* ReadSolFromRestart (output.cpp:1177-1240) + GetStatesFromRestart, which = 0;
+ * ReadSolNm1FromRestart (:1242-1305) + GetSolNm1FromRestart, which = 1: the inverse of
+ * agx_restart_pack, same payload layout (cell by cell, i fastest, n_eq + 1 dimensional
+ * values).  The values are divided by the reference's divisors, formed in its order, with
+ * correctly rounded divisions; density is (raw / rho_ref) * mass fraction.
+ * Refused: which other than 0 or 1; which = 1 where agx_field_upload refuses
+ * AGX_FIELD_CONS_NM1. */
+int agx_restart_unpack(agx_ctx *ctx, int block, int which, const double *in);
+
 /* ---- set-up: the volume-sized parts of the reference's grid set-up -------
  * plot3dBlock::Volume / Centroid / FaceAreaI,J,K / FaceCenterI,J,K (plot3d.cpp:35-360) of
  * one block from its node coordinates nodes[nk+1][nj+1][ni+1][3] (i fastest, as

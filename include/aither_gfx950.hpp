@@ -36,6 +36,16 @@
 #define AGX_CAT(a, b) AGX_CAT2(a, b)
 #define AGX_SYM(name) AGX_CAT(AGX_SYMBOL_PREFIX, name)
 
+// The start-and-resume entries are the library's alone (the CPU oracle of the test suite has
+// no device to form a state on): declared here under the prefix in use, so that a driver built
+// against the oracle compiles and links as long as it does not call them.
+extern "C" {
+int AGX_SYM(state_fill)(AGX_CAT(AGX_SYMBOL_PREFIX, ctx) *, int, const double *);
+int AGX_SYM(state_from_cloud)(AGX_CAT(AGX_SYMBOL_PREFIX, ctx) *, int, int64_t, const double *,
+                              const double *, double *);
+int AGX_SYM(restart_unpack)(AGX_CAT(AGX_SYMBOL_PREFIX, ctx) *, int, int, const double *);
+}
+
 namespace aither_gfx950 {
 
 // The library that serves a deck: numEqns 5 (euler / navierStokes) or 7 (rans), and
@@ -191,6 +201,26 @@ class hotPath {
   void RestartPack(int block, bool secondSolution, double *out) const {
     Check(AGX_SYM(restart_pack)(ctx_, block, secondSolution ? 1 : 0, out),
           "hotPath::RestartPack");
+  }
+  // procBlock::InitializeStates (procBlock.cpp:280-355) on the device, after Finalize(): the
+  // non-file branch from the nondimensional primitive of NondimensionalInitialize ...
+  void FillState(int block, const double *prim) {
+    Check(AGX_SYM(state_fill)(ctx_, block, prim), "hotPath::FillState");
+  }
+  // ... and the file branch from the cloud of CalcTreeFromCloud (points[numPts][3],
+  // states[numPts][numEqns], nondimensional); returns the reference's maxDist.  Among
+  // points at equal distance the lowest index wins
+  double StateFromCloud(int block, int64_t numPts, const double *points, const double *states) {
+    double maxDist = 0.0;
+    Check(AGX_SYM(state_from_cloud)(ctx_, block, numPts, points, states, &maxDist),
+          "hotPath::StateFromCloud");
+    return maxDist;
+  }
+  // ReadSolFromRestart / ReadSolNm1FromRestart (output.cpp:1177-1305): the payload RestartPack
+  // hands out, nondimensionalised on the device into the state or (secondSolution) consVarsNm1
+  void RestartUnpack(int block, bool secondSolution, const double *in) {
+    Check(AGX_SYM(restart_unpack)(ctx_, block, secondSolution ? 1 : 0, in),
+          "hotPath::RestartUnpack");
   }
 
   // mgSolution::StoreOldSolution: consVarsN <- cons(state) (and N-1 on the first

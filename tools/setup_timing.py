@@ -2,12 +2,15 @@
 """Wall time of the grid set-up, from node coordinates in host memory to a finalized context:
 the host pipeline with the library's helpers (build_case(setup=DeviceSetup): device metrics and
 wall search, ghost geometry in numpy, nine arrays through agx_block_create) against
-build_case(geometry="device") (the nodes alone; everything formed on the device).
+build_case(geometry="device") (the nodes alone; everything formed on the device), and that
+with initial="device" as well (no state array either: the uniform icState through
+agx_state_fill).
 python tools/setup_timing.py [n] [repeats]
 Two viscous cases: one n^3 block (BASELINE configs[2]; default n = 256) and 2 x 2 x 2 blocks
 of (n/2)^3 (configs[3]), each `repeats` (3) times per path in one process: median and spread,
 and the peak host RSS.  The peak is the process's high-water mark, so both cases run on the
-device path first: its figures are its own, the host path's are the larger ones.
+device paths first, the one without a state array before the other: each path's figures are
+its own or an earlier, smaller path's; the host path's are the largest.
 Under `rocprofv3 --kernel-trace --stats` the k_ghost_geom / k_edge_geom / k_geo_* /
 k_cell_widths / k_metrics_planes / k_nearest_wall_planes rows are the device path."""
 import os
@@ -40,8 +43,8 @@ def rss_gb():
 
 def one(make, path):
     t0 = time.time()
-    if path == "device":
-        case = make(geometry="device")
+    if path in ("device", "start"):
+        case = make(geometry="device", initial="device" if path == "start" else "host")
         t1 = time.time()
         s = Solver(api, case)
     else:
@@ -56,7 +59,7 @@ def one(make, path):
     return t2 - t0, t1 - t0, t2 - t1
 
 
-for path in ("device", "host"):
+for path in ("start", "device", "host"):
     for name, make in CASES:
         runs = [one(make, path) for _ in range(repeats)]
         tot = [r[0] for r in runs]
