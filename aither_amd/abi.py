@@ -26,6 +26,21 @@ FIELD = {"state": 0, "residual": 1, "dt": 2, "spec_radius": 3, "cons_n": 4,
          # the geometry the device holds (download only), ghost cells included
          "volume": 14, "center": 15, "farea_i": 16, "farea_j": 17, "farea_k": 18,
          "width_i": 19, "width_j": 20, "width_k": 21, "wall_dist": 22}
+# time statistics: one weight (upload only) / the raw accumulators of a block.  Payloads of
+# their own layout, not arrays over the block's cells: FIELD resolves their names
+# (FIELD["stat_sample"]), but iterating FIELD gives the block-shaped fields only -- the ones
+# Solver.upload / download move (Solver.stats_* move these two).  Only FIELD[name] sees the two
+# names: `name in FIELD`, FIELD.get(name), len and iteration do NOT (tests/probe.py holds the
+# iterated set to the block-shaped fields); ask STAT_FIELD for those.
+STAT_FIELD = {"stat_sample": 23, "stat_accum": 24}
+
+
+class _Fields(dict):
+    def __missing__(self, name):
+        return STAT_FIELD[name]
+
+
+FIELD = _Fields(FIELD)
 # geometry fields: (components, direction with one more entry or None)
 GEOM_FIELDS = {"volume": (1, None), "center": (3, None), "farea_i": (4, "i"),
                "farea_j": (4, "j"), "farea_k": (4, "k"), "width_i": (1, None),
@@ -65,6 +80,23 @@ for _n, _base in (("pressureMoment", 11), ("viscousMoment", 14)):
     for _q, _c in enumerate("xyz"):
         LOAD_OUT[f"{_n}_{_c}"] = LOAD_BASE + _base + _q
 LOAD_MOMENTS = tuple(_n for _n in LOAD_OUT if "Moment" in _n)
+# time statistics of the cells (AGX_STAT_BASE + n): means, velocity co-moments, variances
+STAT_BASE, STAT_END = 512, 533
+STAT_OUT = {_n: STAT_BASE + _q for _q, _n in enumerate(
+    ["mean_density", "mean_vel_x", "mean_vel_y", "mean_vel_z", "mean_pressure",
+     "mean_temperature", "mean_mom_x", "mean_mom_y", "mean_mom_z", "mean_turbulentViscosity",
+     "mean_tke", "mean_sdr", "cov_uu", "cov_uv", "cov_uw", "cov_vv", "cov_vw", "cov_ww",
+     "var_density", "var_pressure", "var_temperature"])}
+# ... and of the viscousWall faces (AGX_WSTAT_BASE + n): the mean of every wall variable, then
+# the variances of the wall pressure and the shear components
+WSTAT_BASE, WSTAT_END = 576, 594
+WALL_STAT_OUT = {"mean_" + _n: WSTAT_BASE + _v - 64 for _n, _v in WALL_OUT.items()}
+for _q, _n in enumerate(("pressure", "shearStress_x", "shearStress_y", "shearStress_z")):
+    WALL_STAT_OUT["var_" + _n] = WSTAT_BASE + len(WALL_OUT) + _q
+# cell planes of the accumulators: 9 means + extras (eddy viscosity; k, omega) + 9 second
+# moments; wall values per face
+STAT_SECOND = 9
+STAT_WALL_VALUES = len(WALL_OUT) + 4
 
 c_dp = C.POINTER(C.c_double)
 

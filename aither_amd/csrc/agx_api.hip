@@ -8,6 +8,7 @@
 #include "agx_kernels.hpp"
 #include "agx_geometry.hpp"
 #include "agx_start.hpp"
+#include "agx_stats.hpp"
 #include "agx_mem.hpp"
 #include "agx_switches.hpp"
 #include <rccl/rccl.h>
@@ -147,6 +148,11 @@ struct Block {
   DevBuf<LoadSurfDev> load_tab_dev;
   long load_faces = 0, load_chunks = 0;
   DevBuf<double> load_partial, load_fcen;
+  // time statistics (agx_stats.hpp): the cell accumulator planes (null before the first
+  // sample: a context that never samples allocates nothing), the wall rows of a viscous block
+  // with viscousWall faces, the sum of weights and the number of samples
+  DevBuf<double> stat_cells, stat_wall;
+  double stat_W = 0.0, stat_n = 0.0;
 };
 
 struct ConnSide {          // what side s receives / sends
@@ -294,6 +300,9 @@ struct agx_ctx : agx::Switches {
 static int my_side(const agx_ctx* c, const Conn& k);
 static int implicit_begin(agx_ctx* c, int write_x);
 static int halo_exchange_remote(agx_ctx* c, int what);
+static int stats_field_upload(agx_ctx* c, int id, int field, const double* in);
+static int stats_field_download(agx_ctx* c, int id, int field, double* out);
+static int stats_pack(agx_ctx* c, int id, bool wall, int nvar, const int32_t* vars, double* out);
 #if AGX_FAST
 static int d2_prepare(agx_ctx* c, Block& blk, int write_x, int again, int norms);
 #endif
@@ -2457,6 +2466,8 @@ static int ghosts_for_output(agx_ctx* c, const char* who) {
 int agx_field_download(agx_ctx* c, int id, int field, double* out) {
   if (flush_consn(c)) return 1;
   if (id < 0 || id >= (int)c->blocks.size()) return fail("bad block id %d", id);
+  if (field == AGX_FIELD_STAT_SAMPLE || field == AGX_FIELD_STAT_ACCUM)
+    return stats_field_download(c, id, field, out);
   Block& b = c->blocks[id];
   // (the D2 arrays hold x with the writer's tag in its two lowest mantissa bits: while the
   // planes are current -- an upload or a multigrid transfer wrote them last -- they are the
@@ -2640,16 +2651,36 @@ int agx_output_pack(agx_ctx* c, int id, int nvar, const int32_t* vars, double* o
   if (nvar < 1 || nvar > AGX_OUT_COUNT) return fail("agx_output_pack: nvar %d out of range", nvar);
   // cell variables, wall variables (WriteWallFun), node variables (WriteNodeFun) or integrated
   // wall loads, each range with its own bound on nvar
-  int n_wall = 0, n_node = 0, n_load = 0;
+  int n_wall = 0, n_node = 0, n_load = 0, n_stat = 0, n_wstat = 0;
   for (int v = 0; v < nvar; ++v) {
     const bool cell = vars[v] >= 0 && vars[v] < AGX_OUT_COUNT;
     const bool wall = vars[v] >= AGX_WALL_YPLUS && vars[v] < AGX_WALL_END;
     const bool node = vars[v] >= AGX_NODE_BASE && vars[v] < AGX_NODE_END;
     const bool load = vars[v] >= AGX_LOAD_BASE && vars[v] < AGX_LOAD_END;
-    if (!cell && !wall && !node && !load) return fail("unknown output variable %d", vars[v]);
+    const bool stat = vars[v] >= AGX_STAT_BASE && vars[v] < AGX_STAT_END;
+    const bool wstat = vars[v] >= AGX_WSTAT_BASE && vars[v] < AGX_WSTAT_END;
+    if (!cell && !wall && !node && !load && !stat && !wstat)
+      return fail("unknown output variable %d", vars[v]);
     n_wall += wall;
     n_node += node;
     n_load += load;
+    n_stat += stat;
+    n_wstat += wstat;
+  }
+  // the two statistics ranges (cell statistics, wall statistics)
+  if (n_stat > 0 || n_wstat > 0) {
+    const char* mine = n_stat > 0 ? "statistics" : "wall statistics";
+    if (n_stat > 0 && n_wstat > 0)
+      return fail("agx_output_pack: statistics and wall statistics variables in one call (a "
+                  "call holds ids of one range)");
+    const char* other = n_load > 0 ? "load" : n_node > 0 ? "node" : n_wall > 0 ? "wall"
+                        : n_stat + n_wstat != nvar ? "cell" : nullptr;
+    if (other)
+      return fail("agx_output_pack: %s and %s variables in one call (a call holds ids of one "
+                  "range)", other, mine);
+    if (nvar > (n_stat > 0 ? AGX_STAT_END - AGX_STAT_BASE : AGX_WSTAT_END - AGX_WSTAT_BASE))
+      return fail("agx_output_pack: nvar %d out of range", nvar);
+    return stats_pack(c, id, n_wstat > 0, nvar, vars, out);
   }
   if (n_load > 0) {
     if (n_node > 0)
@@ -2685,6 +2716,185 @@ int agx_output_pack(agx_ctx* c, int id, int nvar, const int32_t* vars, double* o
     return wall_pack(c, id, nvar, vars, out);
   }
   return point_pack(c, id, false, nvar, vars, out);
+}
+
+// ---- time statistics (agx_stats.hpp; include/aither_gfx950.h at AGX_STAT_BASE) ---------------
+namespace {
+// extras of the sampled cell vector: the eddy viscosity (largeEddySimulation, 7 equations),
+// k and omega (7 equations); the cell planes and the wall values per face of a block
+int stat_nx(const agx_ctx* c) { return AGX_NEQ == 7 ? 3 : (c->sp.les ? 1 : 0); }
+int stat_planes(const agx_ctx* c) { return 9 + stat_nx(c) + STAT_NSECOND; }
+int stat_wall_values(const agx_ctx* c, const Block& b) {
+  return c->cfg.is_viscous && !b.wall_tab.empty() ? STAT_NWALL : 0;
+}
+long stat_ncell(const Block& b) { return (long)b.d.ni * b.d.nj * b.d.nk; }
+long stat_pitch(const Block& b) { return (stat_ncell(b) + 1) & ~1L; }
+void stats_reset(Block& b) {
+  b.stat_cells.reset();
+  b.stat_wall.reset();
+  b.stat_W = b.stat_n = 0.0;
+}
+// zeroed accumulators (the first sample, or an upload into a block without)
+int stats_alloc(agx_ctx* c, Block& b) {
+  const size_t nc = (size_t)stat_planes(c) * stat_pitch(b);
+  const size_t nw = (size_t)stat_wall_values(c, b) * b.wall_faces;
+  HIPCHK(b.stat_cells.alloc(nc));
+  HIPCHK(hipMemsetAsync(b.stat_cells.get(), 0, sizeof(double) * nc, c->stream));
+  if (nw) {
+    // (both or neither: a block is never left with the cell planes alone)
+    if (b.stat_wall.alloc(nw) != hipSuccess) {
+      stats_reset(b);
+      return fail("time statistics: no device memory for the wall rows of %zu doubles", nw);
+    }
+    HIPCHK(hipMemsetAsync(b.stat_wall.get(), 0, sizeof(double) * nw, c->stream));
+  }
+  return 0;
+}
+// the accumulators a block holds are the size its surfaces ask for now (an agx_block_set_bcs
+// after the first sample may have changed its wall faces)
+bool stats_fit(const agx_ctx* c, const Block& b) {
+  return b.stat_cells.size() == (size_t)stat_planes(c) * stat_pitch(b) &&
+         b.stat_wall.size() == (size_t)stat_wall_values(c, b) * b.wall_faces;
+}
+int stats_misfit(const char* who, int id) {
+  return fail("%s: the wall surfaces of block %d changed since its statistics began; discard "
+              "them first (AGX_FIELD_STAT_SAMPLE with w == 0)", who, id);
+}
+int stats_sample(agx_ctx* c, int id, double w) {
+  Block& b = c->blocks[id];
+  if (!std::isfinite(w) || w < 0.0)
+    return fail("agx_field_upload: AGX_FIELD_STAT_SAMPLE: the weight %g is negative or not "
+                "finite (w > 0 samples, w == 0 discards the block's statistics)", w);
+  if (w == 0.0) { stats_reset(b); return 0; }
+  if (!c->finalized) return fail("agx_setup_finalize has not been called");
+  const bool wall = stat_wall_values(c, b) > 0;
+  if (wall) {
+    if (b.d.wallv && !c->have_wall_data)
+      return fail("agx_field_upload: AGX_FIELD_STAT_SAMPLE: the wall-law surfaces hold no wall "
+                  "data before the first residual");
+    // the wall faces are evaluated with the ghost cells the next residual would see
+    if (ghosts_for_output(c, "agx_field_upload")) return 1;
+  }
+  if (b.stat_cells && !stats_fit(c, b)) return stats_misfit("agx_field_upload", id);
+  if (!b.stat_cells && stats_alloc(c, b)) return 1;
+  const double W = b.stat_W + w, r = w / W, cf = w * (1.0 - r);
+  const long ncell = stat_ncell(b), pitch = stat_pitch(b);
+  const dim3 grid((unsigned)((pitch / 2 + 255) / 256));
+  by_int<0, 1, 3>(stat_nx(c), [&](auto nx) {
+    // (a library holds the forms its contexts can ask for)
+    if constexpr ((AGX_NEQ == 7) == (decltype(nx)::value == 3))
+      hipLaunchKernelGGL(k_stats_cells<decltype(nx)::value>, grid, dim3(256), 0, c->stream, b.d,
+                         c->gas, ncell, pitch, r, cf, b.stat_cells.get());
+    return 0;
+  });
+  if (wall) {
+    const int fourth = (c->cfg.viscous_recon == AGX_VISC_RECON_CENTRAL_4TH ? 1 : 0) |
+                       (c->sp.les ? 2 : 0);
+    hipLaunchKernelGGL(k_stats_wall, dim3((unsigned)((b.wall_faces + 255) / 256)), dim3(256), 0,
+                       c->stream, b.d, c->gas, b.wall_tab_dev.get(), (int)b.wall_tab.size(),
+                       b.wall_faces, fourth, r, cf, b.stat_wall.get());
+  }
+  HIPCHK(hipGetLastError());
+  b.stat_W = W;
+  b.stat_n += 1.0;
+  return 0;
+}
+}  // namespace
+
+static int stats_field_upload(agx_ctx* c, int id, int field, const double* in) {
+  if (flush_consn(c)) return 1;
+  if (id < 0 || id >= (int)c->blocks.size()) return fail("bad block id %d", id);
+  if (!in) return fail("agx_field_upload: null pointer");
+  if (!c->have_cfg) return fail("agx_config_set has not been called");
+  if (field == AGX_FIELD_STAT_SAMPLE) return stats_sample(c, id, in[0]);
+  if (!c->finalized) return fail("agx_setup_finalize has not been called");
+  Block& b = c->blocks[id];
+  const int np = stat_planes(c), nwv = stat_wall_values(c, b);
+  if (in[0] != (double)np || in[1] != (double)nwv)
+    return fail("agx_field_upload: AGX_FIELD_STAT_ACCUM: the payload holds %g cell planes and %g "
+                "wall values per face, this library and context keep %d and %d for block %d",
+                in[0], in[1], np, nwv, id);
+  if (!std::isfinite(in[2]) || in[2] < 0.0 || !std::isfinite(in[3]) || in[3] < 0.0)
+    return fail("agx_field_upload: AGX_FIELD_STAT_ACCUM: the sum of weights %g or the sample "
+                "count %g is negative or not finite", in[2], in[3]);
+  // (an upload replaces the statistics: accumulators of another size go)
+  if (b.stat_cells && !stats_fit(c, b)) stats_reset(b);
+  if (!b.stat_cells && stats_alloc(c, b)) return 1;
+  const long ncell = stat_ncell(b), pitch = stat_pitch(b);
+  const double* planes_in = in + 4;
+  HIPCHK(hipMemcpy2DAsync(b.stat_cells.get(), sizeof(double) * pitch, planes_in,
+                          sizeof(double) * ncell, sizeof(double) * ncell, np,
+                          hipMemcpyHostToDevice, c->stream));
+  if (nwv)
+    HIPCHK(hipMemcpyAsync(b.stat_wall.get(), planes_in + (size_t)np * ncell,
+                          sizeof(double) * nwv * b.wall_faces, hipMemcpyHostToDevice, c->stream));
+  HIPCHK(hipStreamSynchronize(c->stream));
+  b.stat_W = in[2];
+  b.stat_n = in[3];
+  return 0;
+}
+
+static int stats_field_download(agx_ctx* c, int id, int field, double* out) {
+  if (field == AGX_FIELD_STAT_SAMPLE)
+    return fail("agx_field_download: AGX_FIELD_STAT_SAMPLE is upload only (a sample's weight); "
+                "AGX_FIELD_STAT_ACCUM holds the accumulators");
+  Block& b = c->blocks[id];
+  if (!b.stat_cells)
+    return fail("agx_field_download: AGX_FIELD_STAT_ACCUM: block %d has no statistics: no "
+                "sample has been taken (AGX_FIELD_STAT_SAMPLE)", id);
+  if (!stats_fit(c, b)) return stats_misfit("agx_field_download", id);
+  const int np = stat_planes(c), nwv = stat_wall_values(c, b);
+  const long ncell = stat_ncell(b), pitch = stat_pitch(b);
+  out[0] = np; out[1] = nwv; out[2] = b.stat_W; out[3] = b.stat_n;
+  HIPCHK(hipMemcpy2DAsync(out + 4, sizeof(double) * ncell, b.stat_cells.get(),
+                          sizeof(double) * pitch, sizeof(double) * ncell, np,
+                          hipMemcpyDeviceToHost, c->stream));
+  if (nwv)
+    HIPCHK(hipMemcpyAsync(out + 4 + (size_t)np * ncell, b.stat_wall.get(),
+                          sizeof(double) * nwv * b.wall_faces, hipMemcpyDeviceToHost, c->stream));
+  HIPCHK(hipStreamSynchronize(c->stream));
+  return 0;
+}
+
+// the statistics of one block's cells or (wall) wall faces; the ids are of that range
+static int stats_pack(agx_ctx* c, int id, bool wall, int nvar, const int32_t* vars, double* out) {
+  Block& b = c->blocks[id];
+  if (wall) {
+    if (!c->cfg.is_viscous)
+      return fail("agx_output_pack: wall statistics need a viscous context (an inviscid run "
+                  "keeps no wallData_)");
+    if (b.wall_tab.empty())
+      return fail("agx_output_pack: block %d has no viscousWall surface", id);
+  }
+  int32_t ids[AGX_OUT_COUNT];
+  for (int v = 0; v < nvar; ++v) {
+    ids[v] = vars[v] - (wall ? AGX_WSTAT_BASE : AGX_STAT_BASE);
+    const int wv = AGX_WALL_YPLUS + ids[v];
+    if (AGX_NEQ == 5 && (wall ? (wv == AGX_WALL_TKE || wv == AGX_WALL_SDR)
+                              : (ids[v] == 10 || ids[v] == 11)))
+      return fail("agx_output_pack: statistics variable %d (mean tke, mean sdr) is not kept by "
+                  "the 5-equation libraries", vars[v]);
+    if (!wall && ids[v] == 9 && stat_nx(c) == 0)
+      return fail("agx_output_pack: statistics variable %d (mean turbulentViscosity): this "
+                  "context has no eddy viscosity (largeEddySimulation and the rans libraries "
+                  "have)", vars[v]);
+  }
+  if (!b.stat_cells)
+    return fail("agx_output_pack: block %d has no statistics: no sample has been taken "
+                "(AGX_FIELD_STAT_SAMPLE)", id);
+  if (!stats_fit(c, b)) return stats_misfit("agx_output_pack", id);
+  const long n = wall ? b.wall_faces : stat_ncell(b);
+  double* tmp = nullptr;
+  if (stage_buffer(c, (size_t)nvar * n, &tmp)) return 1;
+  const dim3 grid((unsigned)((n + 255) / 256));
+  if (wall)
+    hipLaunchKernelGGL(k_stats_wall_pack, grid, dim3(256), 0, c->stream, n, b.stat_W, c->gas,
+                       out_spec(c, b, nvar, ids), b.stat_wall.get(), tmp);
+  else
+    hipLaunchKernelGGL(k_stats_pack, grid, dim3(256), 0, c->stream, n, stat_pitch(b),
+                       9 + stat_nx(c), b.stat_W, out_spec(c, b, nvar, ids), b.stat_cells.get(),
+                       tmp);
+  return copy_out(c, out, tmp, (size_t)nvar * n);
 }
 
 int agx_restart_pack(agx_ctx* c, int id, int which, double* out) {
@@ -2884,6 +3094,10 @@ int agx_field_upload(agx_ctx* c, int id, int field, const double* in) {
   // (an upload of x writes this block's planes and, on the D2 path, copies them to its D2
   // arrays below: the planes of this block are current afterwards, those of the other blocks
   // are what they were)
+  // (the two statistics fields write nothing the solver reads: a sample is a read of the run
+  // and leaves every flag as a read would)
+  if (field == AGX_FIELD_STAT_SAMPLE || field == AGX_FIELD_STAT_ACCUM)
+    return stats_field_upload(c, id, field, in);
   field_written_by_caller(c);
   if (flush_consn(c)) return 1;
   if (id < 0 || id >= (int)c->blocks.size()) return fail("bad block id %d", id);

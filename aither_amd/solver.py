@@ -339,6 +339,112 @@ class Solver:
                         total[n] += float(got[n][q])
         return total
 
+    # -- time statistics, kept by the library on the device -----------------------------
+    def _stat_dims(self, gb):
+        """(cell planes, wall values per face, cells, wall faces) of block gb's accumulators."""
+        cfg = self.cfg
+        eddy = cfg.n_eq == 7 or cfg.equation_set == abi.EQN["largeEddySimulation"]
+        planes = 9 + int(eddy) + (2 if cfg.n_eq == 7 else 0) + abi.STAT_SECOND
+        faces = sum(int(np.prod(s["shape"])) for s in self.wall_surfaces(gb))
+        wall = abi.STAT_WALL_VALUES if cfg.is_viscous and faces else 0
+        ni, nj, nk = self.case.blocks[gb].geom.n
+        return planes, wall, ni * nj * nk, faces
+
+    def _stat_weight(self, gb, w):
+        one = np.array([w], dtype=np.float64)
+        self.api.check(self.api.field_upload(self.ctx, self.block_ids[gb],
+                                             abi.FIELD["stat_sample"],
+                                             one.ctypes.data_as(abi.c_dp)), "stats_sample")
+        # (W, samples) as the library keeps them: the same two additions in float64
+        book = self.__dict__.setdefault("_stat_book", {})
+        if w == 0.0:
+            book.pop(gb, None)
+        else:
+            big_w, n = book.get(gb, (0.0, 0))
+            book[gb] = (big_w + w, n + 1)
+
+    def stats_sample(self, weight=1.0):
+        """The current state of every block of this rank enters its running statistics with
+        this weight (means and second central moments per cell and per viscousWall face, West's
+        recurrence; AGX_FIELD_STAT_SAMPLE).  Call it after a time step has converged.  A weight
+        of 0 discards the statistics; the library refuses a negative or non-finite one.
+        Block by block, not all or nothing: a block with viscousWall faces refuses the sample
+        between phase_bc_faces and phase_residual, a block without takes it there, so a call
+        that raises has sampled the blocks before the refusing one (stats_weight tells).  Call
+        it between time steps, where every block is legal.  Each block with wall faces refills
+        the ghost cells of the whole context before it evaluates its faces."""
+        for gb in sorted(self.block_ids):
+            self._stat_weight(gb, float(weight))
+
+    def stats_reset(self):
+        """Discard the statistics of every block of this rank; the next sample starts anew."""
+        for gb in sorted(self.block_ids):
+            self._stat_weight(gb, 0.0)
+
+    def stats_download(self, gb):
+        """The raw accumulators of block gb (AGX_FIELD_STAT_ACCUM): a flat array of
+        {planes, wall values, W, samples}, the cell planes, the wall rows -- what
+        stats_upload takes to go on with the average in another run."""
+        planes, wall, ncell, faces = self._stat_dims(gb)
+        out = np.empty(4 + planes * ncell + wall * faces)
+        self.api.check(self.api.field_download(self.ctx, self.block_ids[gb],
+                                               abi.FIELD["stat_accum"],
+                                               out.ctypes.data_as(abi.c_dp)), "stats_download")
+        self.__dict__.setdefault("_stat_book", {})[gb] = (float(out[2]), int(out[3]))
+        return out
+
+    def stats_upload(self, gb, payload):
+        a = np.ascontiguousarray(payload, dtype=np.float64)
+        planes, wall, ncell, faces = self._stat_dims(gb)
+        # (the header's two counts are the library's to judge; the length must fit them)
+        assert a.ndim == 1 and a.size >= 4 and \
+            a.size == 4 + int(a[0]) * ncell + int(a[1]) * faces, a.shape
+        self.api.check(self.api.field_upload(self.ctx, self.block_ids[gb],
+                                             abi.FIELD["stat_accum"],
+                                             a.ctypes.data_as(abi.c_dp)), "stats_upload")
+        self.__dict__.setdefault("_stat_book", {})[gb] = (float(a[2]), int(a[3]))
+
+    def stats_weight(self, gb):
+        """(sum of weights, samples) of block gb's statistics.  Every sample, reset, upload and
+        download of this Solver goes through the methods above, which keep the pair as the
+        library does (the same float64 additions; an upload or a download sets it from the
+        payload's header), so no plane moves.  A block this Solver has no record of is asked
+        with one download of its payload (2.4 GB at 256^3), which the library refuses by name
+        before the first sample."""
+        book = self.__dict__.setdefault("_stat_book", {})
+        if gb not in book:
+            self.stats_download(gb)
+        return book[gb]
+
+    def stats_pack(self, gb, names):
+        """Time statistics of block gb's cells (abi.STAT_OUT), shaped like output_pack:
+        [nvar, nk, nj, ni], dimensional."""
+        ni, nj, nk = self.case.blocks[gb].geom.n
+        ids = (C.c_int32 * len(names))(*[abi.STAT_OUT[n] for n in names])
+        out = np.empty((len(names), nk, nj, ni))
+        self.api.check(self.api.output_pack(self.ctx, self.block_ids[gb], len(names), ids,
+                                            out.ctypes.data_as(abi.c_dp)), "output_pack")
+        return out
+
+    def wall_stats_pack(self, gb, names):
+        """Time statistics of block gb's viscousWall faces (abi.WALL_STAT_OUT), shaped like
+        wall_pack: {name: [one array per wall surface]}, dimensional."""
+        surfs = self.wall_surfaces(gb)
+        total = sum(int(np.prod(s["shape"])) for s in surfs)
+        ids = (C.c_int32 * len(names))(*[abi.WALL_STAT_OUT[n] for n in names])
+        out = np.empty((len(names), max(total, 1)))
+        self.api.check(self.api.output_pack(self.ctx, self.block_ids[gb], len(names), ids,
+                                            out.ctypes.data_as(abi.c_dp)), "output_pack")
+        res = {}
+        for q, name in enumerate(names):
+            off, rows = 0, []
+            for s in surfs:
+                cnt = int(np.prod(s["shape"]))
+                rows.append(out[q, off:off + cnt].reshape(s["shape"]).copy())
+                off += cnt
+            res[name] = rows
+        return res
+
     def restart_pack(self, gb, which=0):
         """WriteRestart's payload of block gb: [nk, nj, ni, n_eq + 1], dimensional."""
         g = self.case.blocks[gb].geom
@@ -593,6 +699,28 @@ class MultigridSolver:
 
     def total_loads(self, tags=None, about=None, level=0):
         return self.levels[level].total_loads(tags, about)
+
+    # time statistics: those of the finest level
+    def stats_sample(self, weight=1.0):
+        return self.levels[0].stats_sample(weight)
+
+    def stats_reset(self):
+        return self.levels[0].stats_reset()
+
+    def stats_weight(self, gb):
+        return self.levels[0].stats_weight(gb)
+
+    def stats_pack(self, gb, names):
+        return self.levels[0].stats_pack(gb, names)
+
+    def wall_stats_pack(self, gb, names):
+        return self.levels[0].wall_stats_pack(gb, names)
+
+    def stats_download(self, gb):
+        return self.levels[0].stats_download(gb)
+
+    def stats_upload(self, gb, payload):
+        return self.levels[0].stats_upload(gb, payload)
 
     def _p(self, a, ctype):
         return a.ctypes.data_as(C.POINTER(ctype))

@@ -110,7 +110,29 @@ enum { AGX_FIELD_STATE = 0,      /* state_      nEq, with ghosts           */
        AGX_FIELD_CENTER = 15,    /* center_     3                               */
        AGX_FIELD_FAREA_I = 16, AGX_FIELD_FAREA_J = 17, AGX_FIELD_FAREA_K = 18, /* 4 */
        AGX_FIELD_WIDTH_I = 19, AGX_FIELD_WIDTH_J = 20, AGX_FIELD_WIDTH_K = 21, /* 1 */
-       AGX_FIELD_WALL_DIST = 22  /* wallDist_   1                               */
+       AGX_FIELD_WALL_DIST = 22, /* wallDist_   1                               */
+       /* running time statistics of the block ("time statistics" at AGX_STAT_BASE).
+        * STAT_SAMPLE: upload only, ONE double w.  w > 0 and finite: the block's current state
+        * enters its statistics with weight w (the accumulators are allocated on the first
+        * sample).  w == 0: the block's statistics are discarded and their memory freed; the
+        * next sample starts anew.  Negative or non-finite w, and a download, are refused by
+        * name.  A sample writes nothing the solver reads: it is a READ of the run ("reads
+        * between phases" at agx_field_download) and leaves the run bit-identical.  On a viscous
+        * block with a viscousWall surface it is a ghost-refilling read like the wall
+        * variables, refused between agx_phase_bc_faces and agx_phase_residual; on every other
+        * block it reads physical cells only and is legal at every position.
+        * STAT_ACCUM: download and upload, the block's raw (nondimensional) accumulators, for
+        * checkpointing an average:
+        *   4 doubles {cell planes P, wall values per face V, W (sum of weights), samples},
+        *   P planes [nk][nj][ni] (i fastest, no ghost cells): the means, then the co-moments C,
+        *   V rows of one value per wall face (the order of the wall payload),
+        * 4 + P ni nj nk + V faces doubles in all.  P = 18 (5 equations), 19
+        * (largeEddySimulation), 21 (7 equations); V = 18 on a viscous block with a viscousWall
+        * surface, else 0.  Upload replaces the block's statistics (allocating if need be) and
+        * is refused by name when P or V are not this library's and context's, or W or the
+        * sample count is negative or non-finite; download before the first sample is refused
+        * by name. */
+       AGX_FIELD_STAT_SAMPLE = 23, AGX_FIELD_STAT_ACCUM = 24
 };
 
 /* variables of a function file, WriteFunFile (output.cpp:235-407): formed and
@@ -250,6 +272,53 @@ enum { AGX_LOAD_BASE = 256, AGX_LOAD_AREA = AGX_LOAD_BASE,
        AGX_LOAD_PRESSURE_MOMENT_X, AGX_LOAD_PRESSURE_MOMENT_Y, AGX_LOAD_PRESSURE_MOMENT_Z,
        AGX_LOAD_VISCOUS_MOMENT_X, AGX_LOAD_VISCOUS_MOMENT_Y, AGX_LOAD_VISCOUS_MOMENT_Z,
        AGX_LOAD_END };
+
+/* time statistics: a fifth and a sixth range of agx_output_pack, with no counterpart in the
+ * reference.  An unsteady run (largeEddySimulation, SST-DES, bdf2 dual time stepping) is read
+ * from its time averages; the library keeps them on the device, so that a sample costs one
+ * streaming pass over the block instead of a download of its state.
+ * What is averaged.  Per physical cell the vector rho, u, v, w, p, T = p / (rho R), rho u,
+ * rho v, rho w; in contexts with an eddy viscosity (largeEddySimulation, the rans libraries)
+ * also that -- the last residual's, as AGX_OUT_TURB_VISCOSITY reads it; in the 7-equation
+ * libraries also k and omega.  Second moments: the six velocity co-moments and the variances
+ * of rho, p and T.  Per viscousWall face of a viscous context: the mean of each of the 14 wall
+ * variables (AGX_WALL_*), and the variances of the wall pressure and of the three shear
+ * components.  The Favre mean is the caller's division mean(rho u) / mean(rho); time-averaged
+ * integrated loads are the integrals of the mean face values.
+ * The recurrence (West 1979), per cell and per face, with the sample's weight w and the sum
+ * of weights W including it:
+ *   delta = x - mean;   mean += (w / W) delta;   C_ab += w (1 - w / W) delta_a delta_b
+ * and the covariance is C_ab / W.  Not sums of squares: E[x^2] - E[x]^2 loses every digit at
+ * the fluctuation levels an LES resolves.  Identical samples give the sample as the mean, bit
+ * for bit, and second moments of exactly 0; multiplying every weight by a power of two
+ * changes no bit.
+ * Timing.  A sample (agx_field_upload, AGX_FIELD_STAT_SAMPLE) takes the state the device
+ * holds when it is made; the wall variables are evaluated as agx_output_pack would at that
+ * moment (low-Re faces from the state now with the ghost cells the next residual would see,
+ * wall-law faces the stored wall data).  The time loop samples after mgSolution::Iterate has
+ * converged a time step.  agx_iterate never samples.
+ * Legality: see AGX_FIELD_STAT_SAMPLE.  Packing the statistics reads the accumulators only
+ * and is legal at every position.
+ * Determinism: no atomics, no reduction across cells; a cell's statistics are a function of
+ * its own samples, and two runs give the same bits.  Not a collective: a rank averages its
+ * own blocks, each block its own cells.
+ * AGX_STAT_BASE + n: one value per physical cell, out[v * ni*nj*nk + cell] like the cell
+ * range, dimensional (a mean with the factor of its variable, a second moment with the
+ * product of the two factors), n in the order
+ *   0 mean density; 1..3 mean vel_x/y/z; 4 mean pressure; 5 mean temperature;
+ *   6..8 mean mom_x/y/z (rho u_i); 9 mean turbulentViscosity; 10 mean tke; 11 mean sdr;
+ *   12..17 cov uu, uv, uw, vv, vw, ww; 18 var density; 19 var pressure; 20 var temperature.
+ * Refused by name: mean turbulentViscosity where the context has no eddy viscosity, mean tke
+ * and sdr in the 5-equation libraries.
+ * AGX_WSTAT_BASE + n: one value per wall face in the layout of the wall range,
+ *   n = w - AGX_WALL_YPLUS: the mean of wall variable w, for each of the 14;
+ *   14 var pressure; 15..17 var shearStress_x/y/z.
+ * Refused like the wall range: an inviscid context, a block without a viscousWall surface;
+ * mean tke and sdr in the 5-equation libraries.
+ * Both ranges refuse by name before the block's first sample; a call holds ids of one range,
+ * and at most as many as the range has. */
+enum { AGX_STAT_BASE = 512, AGX_STAT_END = 533 };
+enum { AGX_WSTAT_BASE = 576, AGX_WSTAT_END = 594 };
 
 /* what a halo exchange carries (gridLevel.cpp:299-313, utility.cpp:400-423) */
 enum { AGX_HALO_STATE = 0, AGX_HALO_UPDATE = 1,
@@ -502,6 +571,10 @@ int agx_phase_implicit_update(agx_ctx *ctx, int mm, double *l2, agx_linf *linf);
  * value per load surface of the block instead -- its viscousWall and slipWall surfaces in the
  * order agx_block_set_bcs got them -- variable by variable in the caller's order:
  * out[v * nsurf + surface], see the enum.
+ * Time statistics (no counterpart in output.cpp): with statistics ids (AGX_STAT_BASE + n) one
+ * value per physical cell in the layout of the cell variables, with wall statistics ids
+ * (AGX_WSTAT_BASE + n) one value per wall face in the layout of the wall variables; see the
+ * enums for what they refuse.
  * Refused: variables of two ranges in one call, an id in no range, a block without a
  * viscousWall surface, an inviscid context, wall-law surfaces before the first residual (the
  * three: wall variables), the four node variables named above, nvar beyond the number of ids

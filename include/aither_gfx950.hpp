@@ -97,6 +97,7 @@ class residual {
 class hotPath {
   AGX_CAT(AGX_SYMBOL_PREFIX, ctx) *ctx_ = nullptr;
   int numEqns_ = 5;
+  int numBlocks_ = 0;
 
   static void Check(int rc, const char *what) {
     if (rc != 0) {   // reference convention: report and stop
@@ -127,6 +128,7 @@ class hotPath {
   int AddBlock(const agx_block_geom &geom, const std::vector<agx_bc_surface> &surfs) {
     int id = -1;
     Check(AGX_SYM(block_create)(ctx_, &geom, &id), "hotPath::AddBlock");
+    if (id + 1 > numBlocks_) numBlocks_ = id + 1;
     Check(AGX_SYM(block_set_bcs)(ctx_, id, static_cast<int>(surfs.size()), surfs.data()),
           "hotPath::AddBlock (boundary conditions)");
     return id;
@@ -195,6 +197,40 @@ class hotPath {
     for (auto &v : ids) v += AGX_NODE_BASE;
     Check(AGX_SYM(output_pack)(ctx_, block, static_cast<int>(ids.size()), ids.data(), out),
           "hotPath::OutputPackNodes");
+  }
+  // Time statistics (no counterpart in the reference; see AGX_STAT_BASE in the C header):
+  // running means and second central moments per cell and per viscousWall face, kept on the
+  // device.  The time loop calls SampleStatistics after mgSolution::Iterate has converged a
+  // time step; the weight is usually the step's dt.  Every block AddBlock returned is sampled,
+  // one after the other: call it between time steps, where every block is legal (a block with
+  // viscousWall faces refuses between agx_phase_bc_faces and agx_phase_residual, and the
+  // blocks before it would have been sampled already)
+  void SampleStatistics(double weight) {
+    for (int b = 0; b < numBlocks_; ++b)
+      Check(AGX_SYM(field_upload)(ctx_, b, AGX_FIELD_STAT_SAMPLE, &weight),
+            "hotPath::SampleStatistics");
+  }
+  // discards the statistics of every block; the next sample starts anew
+  void ResetStatistics() { SampleStatistics(0.0); }
+  // the listed statistics of the block's cells (AGX_STAT_BASE + n), laid out like OutputPack's
+  // payload, and of its wall faces (AGX_WSTAT_BASE + n), laid out like WallPack's; dimensional
+  void Statistics(int block, const std::vector<int32_t> &ids, double *out) const {
+    Check(AGX_SYM(output_pack)(ctx_, block, static_cast<int>(ids.size()), ids.data(), out),
+          "hotPath::Statistics");
+  }
+  void WallStatistics(int block, const std::vector<int32_t> &ids, double *out) const {
+    Check(AGX_SYM(output_pack)(ctx_, block, static_cast<int>(ids.size()), ids.data(), out),
+          "hotPath::WallStatistics");
+  }
+  // the block's raw accumulators (AGX_FIELD_STAT_ACCUM: 4 header values, the cell planes, the
+  // wall rows; the caller sizes `payload` as the C header states) for a checkpoint, and back
+  void StatisticsPayload(int block, double *payload) const {
+    Check(AGX_SYM(field_download)(ctx_, block, AGX_FIELD_STAT_ACCUM, payload),
+          "hotPath::StatisticsPayload");
+  }
+  void SetStatisticsPayload(int block, const double *payload) {
+    Check(AGX_SYM(field_upload)(ctx_, block, AGX_FIELD_STAT_ACCUM, payload),
+          "hotPath::SetStatisticsPayload");
   }
   // WriteRestart (output.cpp:651-752): the block's payload, numEqns + 1 values per cell;
   // secondSolution: consVarsNm1 (multilevel time integration)
