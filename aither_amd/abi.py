@@ -93,6 +93,34 @@ WSTAT_BASE, WSTAT_END = 576, 594
 WALL_STAT_OUT = {"mean_" + _n: WSTAT_BASE + _v - 64 for _n, _v in WALL_OUT.items()}
 for _q, _n in enumerate(("pressure", "shearStress_x", "shearStress_y", "shearStress_z")):
     WALL_STAT_OUT["var_" + _n] = WSTAT_BASE + len(WALL_OUT) + _q
+# ... and of the cells collapsed along index directions (AGX_CSTAT_BASE + 32 * mask + n):
+# n in the order of STAT_OUT, then the bin's volume; mask bit 0 = i, bit 1 = j, bit 2 = k.
+# CSTAT_CHUNK: the collapsed (j, k) positions of a bin are pooled in chunks of this many.
+CSTAT_BASE, CSTAT_COUNT, CSTAT_CHUNK = 1024, 22, 64
+CSTAT_NAMES = tuple(STAT_OUT) + ("volume",)
+# the two means of each second moment
+STAT_PAIRS = {"cov_uu": ("mean_vel_x", "mean_vel_x"), "cov_uv": ("mean_vel_x", "mean_vel_y"),
+              "cov_uw": ("mean_vel_x", "mean_vel_z"), "cov_vv": ("mean_vel_y", "mean_vel_y"),
+              "cov_vw": ("mean_vel_y", "mean_vel_z"), "cov_ww": ("mean_vel_z", "mean_vel_z"),
+              "var_density": ("mean_density", "mean_density"),
+              "var_pressure": ("mean_pressure", "mean_pressure"),
+              "var_temperature": ("mean_temperature", "mean_temperature")}
+
+
+def cstat_mask(over):
+    """The mask of a string out of "i", "j", "k" (e.g. "ik" -> 5)."""
+    over = str(over)
+    if not over or any(c not in "ijk" for c in over) or len(set(over)) != len(over):
+        raise ValueError(f"collapsed directions {over!r}: a non-empty string out of 'i', 'j', "
+                         "'k', each at most once")
+    return sum(1 << "ijk".index(c) for c in over)
+
+
+def cstat_id(mask, name):
+    """The id of statistics variable `name` (CSTAT_NAMES) collapsed over `mask`."""
+    return CSTAT_BASE + 32 * int(mask) + CSTAT_NAMES.index(name)
+
+
 # cell planes of the accumulators: 9 means + extras (eddy viscosity; k, omega) + 9 second
 # moments; wall values per face
 STAT_SECOND = 9

@@ -153,6 +153,9 @@ struct Block {
   // with viscousWall faces, the sum of weights and the number of samples
   DevBuf<double> stat_cells, stat_wall;
   double stat_W = 0.0, stat_n = 0.0;
+  // the chunk records of a collapse (AGX_CSTAT_BASE): allocated by the first one, grown by a
+  // larger one, freed with the statistics
+  DevBuf<double> stat_part;
 };
 
 struct ConnSide {          // what side s receives / sends
@@ -303,6 +306,7 @@ static int halo_exchange_remote(agx_ctx* c, int what);
 static int stats_field_upload(agx_ctx* c, int id, int field, const double* in);
 static int stats_field_download(agx_ctx* c, int id, int field, double* out);
 static int stats_pack(agx_ctx* c, int id, bool wall, int nvar, const int32_t* vars, double* out);
+static int stats_collapse(agx_ctx* c, int id, int nvar, const int32_t* vars, double* out);
 #if AGX_FAST
 static int d2_prepare(agx_ctx* c, Block& blk, int write_x, int again, int norms);
 #endif
@@ -2651,7 +2655,7 @@ int agx_output_pack(agx_ctx* c, int id, int nvar, const int32_t* vars, double* o
   if (nvar < 1 || nvar > AGX_OUT_COUNT) return fail("agx_output_pack: nvar %d out of range", nvar);
   // cell variables, wall variables (WriteWallFun), node variables (WriteNodeFun) or integrated
   // wall loads, each range with its own bound on nvar
-  int n_wall = 0, n_node = 0, n_load = 0, n_stat = 0, n_wstat = 0;
+  int n_wall = 0, n_node = 0, n_load = 0, n_stat = 0, n_wstat = 0, n_cstat = 0;
   for (int v = 0; v < nvar; ++v) {
     const bool cell = vars[v] >= 0 && vars[v] < AGX_OUT_COUNT;
     const bool wall = vars[v] >= AGX_WALL_YPLUS && vars[v] < AGX_WALL_END;
@@ -2659,13 +2663,26 @@ int agx_output_pack(agx_ctx* c, int id, int nvar, const int32_t* vars, double* o
     const bool load = vars[v] >= AGX_LOAD_BASE && vars[v] < AGX_LOAD_END;
     const bool stat = vars[v] >= AGX_STAT_BASE && vars[v] < AGX_STAT_END;
     const bool wstat = vars[v] >= AGX_WSTAT_BASE && vars[v] < AGX_WSTAT_END;
-    if (!cell && !wall && !node && !load && !stat && !wstat)
+    const bool cstat = vars[v] >= AGX_CSTAT_BASE && vars[v] < AGX_CSTAT_END;
+    if (!cell && !wall && !node && !load && !stat && !wstat && !cstat)
       return fail("unknown output variable %d", vars[v]);
+    n_cstat += cstat;
     n_wall += wall;
     n_node += node;
     n_load += load;
     n_stat += stat;
     n_wstat += wstat;
+  }
+  // the statistics collapsed along index directions
+  if (n_cstat > 0) {
+    const char* other = n_wstat > 0 ? "wall statistics" : n_stat > 0 ? "statistics"
+                        : n_load > 0 ? "load" : n_node > 0 ? "node" : n_wall > 0 ? "wall"
+                        : n_cstat != nvar ? "cell" : nullptr;
+    if (other)
+      return fail("agx_output_pack: %s and collapsed statistics variables in one call (a call "
+                  "holds ids of one range)", other);
+    if (nvar > AGX_CSTAT_COUNT) return fail("agx_output_pack: nvar %d out of range", nvar);
+    return stats_collapse(c, id, nvar, vars, out);
   }
   // the two statistics ranges (cell statistics, wall statistics)
   if (n_stat > 0 || n_wstat > 0) {
@@ -2732,6 +2749,7 @@ long stat_pitch(const Block& b) { return (stat_ncell(b) + 1) & ~1L; }
 void stats_reset(Block& b) {
   b.stat_cells.reset();
   b.stat_wall.reset();
+  b.stat_part.reset();
   b.stat_W = b.stat_n = 0.0;
 }
 // zeroed accumulators (the first sample, or an upload into a block without)
@@ -2759,6 +2777,20 @@ bool stats_fit(const agx_ctx* c, const Block& b) {
 int stats_misfit(const char* who, int id) {
   return fail("%s: the wall surfaces of block %d changed since its statistics began; discard "
               "them first (AGX_FIELD_STAT_SAMPLE with w == 0)", who, id);
+}
+// the cell statistics a library or a context does not keep (n relative to AGX_STAT_BASE; var:
+// the id as the caller gave it)
+int stat_not_kept(bool refused, int var) {
+  return refused ? fail("agx_output_pack: statistics variable %d (mean tke, mean sdr) is not "
+                        "kept by the 5-equation libraries", var) : 0;
+}
+int stat_cell_refused(const agx_ctx* c, int n, int var) {
+  if (stat_not_kept(AGX_NEQ == 5 && (n == 10 || n == 11), var)) return 1;
+  if (n == 9 && stat_nx(c) == 0)
+    return fail("agx_output_pack: statistics variable %d (mean turbulentViscosity): this "
+                "context has no eddy viscosity (largeEddySimulation and the rans libraries "
+                "have)", var);
+  return 0;
 }
 int stats_sample(agx_ctx* c, int id, double w) {
   Block& b = c->blocks[id];
@@ -2870,14 +2902,9 @@ static int stats_pack(agx_ctx* c, int id, bool wall, int nvar, const int32_t* va
   for (int v = 0; v < nvar; ++v) {
     ids[v] = vars[v] - (wall ? AGX_WSTAT_BASE : AGX_STAT_BASE);
     const int wv = AGX_WALL_YPLUS + ids[v];
-    if (AGX_NEQ == 5 && (wall ? (wv == AGX_WALL_TKE || wv == AGX_WALL_SDR)
-                              : (ids[v] == 10 || ids[v] == 11)))
-      return fail("agx_output_pack: statistics variable %d (mean tke, mean sdr) is not kept by "
-                  "the 5-equation libraries", vars[v]);
-    if (!wall && ids[v] == 9 && stat_nx(c) == 0)
-      return fail("agx_output_pack: statistics variable %d (mean turbulentViscosity): this "
-                  "context has no eddy viscosity (largeEddySimulation and the rans libraries "
-                  "have)", vars[v]);
+    if (wall ? stat_not_kept(AGX_NEQ == 5 && (wv == AGX_WALL_TKE || wv == AGX_WALL_SDR), vars[v])
+             : stat_cell_refused(c, ids[v], vars[v]))
+      return 1;
   }
   if (!b.stat_cells)
     return fail("agx_output_pack: block %d has no statistics: no sample has been taken "
@@ -2895,6 +2922,66 @@ static int stats_pack(agx_ctx* c, int id, bool wall, int nvar, const int32_t* va
                        9 + stat_nx(c), b.stat_W, out_spec(c, b, nvar, ids), b.stat_cells.get(),
                        tmp);
   return copy_out(c, out, tmp, (size_t)nvar * n);
+}
+
+// the cell statistics of one block pooled over the collapsed index directions of a mask; the
+// ids are of AGX_CSTAT_BASE, of no other range, and at most AGX_CSTAT_COUNT
+static int stats_collapse(agx_ctx* c, int id, int nvar, const int32_t* vars, double* out) {
+  Block& b = c->blocks[id];
+  const int nm = 9 + stat_nx(c);
+  CstatSpec cs;
+  memset(&cs, 0, sizeof cs);
+  int32_t ids[AGX_OUT_COUNT];
+  for (int v = 0; v < nvar; ++v) {
+    const int mask = (vars[v] - AGX_CSTAT_BASE) / 32, n = (vars[v] - AGX_CSTAT_BASE) % 32;
+    if (mask < 1 || mask > 7)
+      return fail("agx_output_pack: collapsed statistics variable %d: mask %d (the collapsed "
+                  "directions are bit 0 = i, bit 1 = j, bit 2 = k: 1 ... 7)", vars[v], mask);
+    if (n >= AGX_CSTAT_COUNT)
+      return fail("agx_output_pack: collapsed statistics variable %d: n = %d (0 ... 20 are the "
+                  "variables of AGX_STAT_BASE, 21 is the volume)", vars[v], n);
+    if (v > 0 && mask != cs.mask)
+      return fail("agx_output_pack: collapsed statistics of masks %d and %d in one call (a call "
+                  "collapses one set of directions)", cs.mask, mask);
+    cs.mask = mask;
+    ids[v] = n;
+    if (stat_cell_refused(c, n, vars[v])) return 1;
+    // a mean carries its own plane, a second moment its plane and its two means
+    if (n < 12) cs.means |= 1u << n;
+    else if (n < CSTAT_VOLUME) {
+      cs.seconds |= 1u << (n - 12);
+      cs.means |= 1u << stat_second_a(n - 12) | 1u << stat_second_b(n - 12);
+    }
+  }
+  if (!b.stat_cells)
+    return fail("agx_output_pack: block %d has no statistics: no sample has been taken "
+                "(AGX_FIELD_STAT_SAMPLE)", id);
+  if (!stats_fit(c, b)) return stats_misfit("agx_output_pack", id);
+  const long ni = b.d.ni, nj = b.d.nj, nk = b.d.nk;
+  cs.pitch = stat_pitch(b);
+  cs.nbin = (cs.mask & 1 ? 1 : ni) * (cs.mask & 2 ? 1 : nj) * (cs.mask & 4 ? 1 : nk);
+  cs.steps = (cs.mask & 2 ? nj : 1) * (cs.mask & 4 ? nk : 1);
+  cs.nchunk = (cs.steps + CSTAT_CHUNK - 1) / CSTAT_CHUNK;
+  const size_t np = (size_t)cs.nchunk * cstat_nq(nm) * cs.nbin;
+  if (np > b.stat_part.size()) {
+    HIPCHK(hipStreamSynchronize(c->stream));     // (before the old one is freed)
+    if (b.stat_part.alloc(np) != hipSuccess)
+      return fail("agx_output_pack: no device memory for the chunk records of %zu doubles", np);
+  }
+  double* tmp = nullptr;
+  if (stage_buffer(c, (size_t)nvar * cs.nbin, &tmp)) return 1;
+  const long units = cs.nbin * cs.nchunk, threads = cs.mask & 1 ? units * 64 : units;
+  const dim3 grid((unsigned)((threads + 255) / 256));
+  by_int<0, 1, 3>(stat_nx(c), [&](auto nx) {
+    if constexpr ((AGX_NEQ == 7) == (decltype(nx)::value == 3))
+      hipLaunchKernelGGL(k_cstat_partial<decltype(nx)::value>, grid, dim3(256), 0, c->stream, b.d,
+                         cs, b.stat_cells.get(), b.stat_part.get());
+    return 0;
+  });
+  hipLaunchKernelGGL(k_cstat_join, dim3((unsigned)((cs.nbin + 63) / 64), (unsigned)nvar), dim3(64),
+                     0, c->stream, cs, nm, b.stat_W, out_spec(c, b, nvar, ids),
+                     b.stat_part.get(), tmp);
+  return copy_out(c, out, tmp, (size_t)nvar * cs.nbin);
 }
 
 int agx_restart_pack(agx_ctx* c, int id, int which, double* out) {

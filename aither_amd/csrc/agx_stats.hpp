@@ -203,6 +203,206 @@ k_stats_pack(long ncell, long pitch, int nm, double W, OutSpec sp, const double*
     out[(long)v * ncell + p] = stat_cell_value(id, acc[plane * pitch + p], W, sp);
   }
 }
+// ---- the statistics collapsed along index directions (AGX_CSTAT_BASE) --------------------------
+// A bin is one position of the directions that remain; its cells are pooled with their volumes
+// by the same one-pass recurrence, in space:
+//     V += v;  r = v / V;  cf = v (1 - r);  delta = m - M
+//     M += r delta;   T_ab += r (C_ab - T_ab);   D_ab += (cf delta_a) delta_b
+// and two partial bins join by the pairwise form (cstat_join).  cov_ab = T_ab / W + D_ab / V is
+// the co-moment about the space-time mean.  Cells with bit-identical m and C give M = m,
+// T = C and D = 0 exactly, whatever their volumes.
+// Shape of the sum (fixed by the extents and the mask alone; no atomics): the collapsed j and
+// k positions of a bin are its MARCH, k outer, j inner, cut into chunks of CSTAT_CHUNK steps.
+// i kept: a thread per (chunk, bin) takes one cell per step, neighbouring threads neighbouring
+// i.  i collapsed: a wave per (chunk, bin); per step lane l takes the row's cells l, l + 64, ...,
+// and after the chunk the 64 lane partials join by a butterfly, the lower lane first.  Each
+// (chunk, bin) leaves a record of CSTAT_NQ(NM) values in part[(chunk * NQ + q) * nbin + bin]:
+// V, M[NM], T[9], D[9]; k_cstat_join joins a bin's records in ascending chunk order, one
+// thread per (bin, requested id), and makes the value dimensional.  Every quantity is a
+// function of the volumes and of its own planes, so a subset of ids returns the same bits.
+constexpr int CSTAT_CHUNK = 64;
+constexpr int CSTAT_VOLUME = 21;       // id of the bin's volume, after the 21 of AGX_STAT_BASE
+__host__ __device__ constexpr int cstat_nq(int nm) { return 1 + nm + 2 * STAT_NSECOND; }
+// the two means of a second moment (uu uv uw vv vw ww, rho rho, p p, T T)
+__host__ __device__ constexpr int stat_second_a(int n) {
+  constexpr int A[STAT_NSECOND] = {1, 1, 1, 2, 2, 3, 0, 4, 5};
+  return A[n];
+}
+__host__ __device__ constexpr int stat_second_b(int n) {
+  constexpr int B[STAT_NSECOND] = {1, 2, 3, 2, 3, 3, 0, 4, 5};
+  return B[n];
+}
+struct CstatSpec {
+  int mask;                // collapsed directions, bit 0 = i, 1 = j, 2 = k
+  unsigned means, seconds; // the planes to pool: bit n = mean n / second moment n
+  long pitch;              // of the accumulator planes
+  long nbin, nchunk, steps;
+};
+// r of a join or a step: V2 / (V1 + V2); two empty partials (lanes beyond a short row) join
+// as the identity
+__device__ __forceinline__ double cstat_ratio(double v2, double vsum) {
+  return vsum == 0.0 ? 0.0 : v2 / vsum;
+}
+template <int NM>
+struct CstatPartial {
+  double V, M[NM], T[STAT_NSECOND], D[STAT_NSECOND];
+};
+template <int NM>
+__device__ __forceinline__ void cstat_join(CstatPartial<NM>& a, const CstatPartial<NM>& b,
+                                           unsigned means, unsigned seconds) {
+#pragma clang fp contract(off)
+  const double V = a.V + b.V, r = cstat_ratio(b.V, V), cf = a.V * r;
+  double d[NM];
+#pragma unroll
+  for (int n = 0; n < NM; ++n)
+    if (means >> n & 1) {
+      d[n] = b.M[n] - a.M[n];
+      a.M[n] = a.M[n] + r * d[n];
+    }
+#pragma unroll
+  for (int n = 0; n < STAT_NSECOND; ++n)
+    if (seconds >> n & 1) {
+      a.T[n] = a.T[n] + r * (b.T[n] - a.T[n]);
+      a.D[n] = a.D[n] + b.D[n] + (cf * d[stat_second_a(n)]) * d[stat_second_b(n)];
+    }
+  a.V = V;
+}
+template <int NX>
+__global__ void __launch_bounds__(256)
+k_cstat_partial(BlockDev b, CstatSpec cs, const double* __restrict__ acc,
+                double* __restrict__ part) {
+  constexpr int NM = 9 + NX, NQ = cstat_nq(NM);
+  const bool over_i = cs.mask & 1;
+  const long t = (long)blockIdx.x * blockDim.x + threadIdx.x;
+  const int lane = threadIdx.x & 63;
+  const long unit = over_i ? t >> 6 : t;       // (uniform over a wave where i is collapsed)
+  if (unit >= cs.nbin * cs.nchunk) return;
+  const long bin = unit % cs.nbin, chunk = unit / cs.nbin;
+  // the bin's position in the directions that remain, 0 in the collapsed ones
+  const int ni_rem = over_i ? 1 : b.ni, nj_rem = cs.mask & 2 ? 1 : b.nj;
+  const int i0 = (int)(bin % ni_rem);
+  const long rest = bin / ni_rem;
+  const int j0 = (int)(rest % nj_rem), k0 = (int)(rest / nj_rem);
+  const int cj = cs.mask & 2 ? b.nj : 1;
+  const long s0 = chunk * CSTAT_CHUNK;
+  const long s1 = s0 + CSTAT_CHUNK < cs.steps ? s0 + CSTAT_CHUNK : cs.steps;
+  int js = (int)(s0 % cj), ks = (int)(s0 / cj);
+  CstatPartial<NM> p;
+  p.V = 0.0;
+#pragma unroll
+  for (int n = 0; n < NM; ++n) p.M[n] = 0.0;
+#pragma unroll
+  for (int n = 0; n < STAT_NSECOND; ++n) p.T[n] = p.D[n] = 0.0;
+  const int i_first = over_i ? lane : i0, i_step = over_i ? 64 : b.ni;
+  for (long s = s0; s < s1; ++s) {
+    const int j = j0 + js, k = k0 + ks;
+    const long row = ((long)k * b.nj + j) * b.ni;
+    for (int i = i_first; i < b.ni; i += i_step) {
+      const double v = b.vol[b.idx(i, j, k)];
+      const double* a = acc + row + i;
+      double m[NM], c[STAT_NSECOND];
+#pragma unroll
+      for (int n = 0; n < NM; ++n)
+        if (cs.means >> n & 1) m[n] = a[n * cs.pitch];
+#pragma unroll
+      for (int n = 0; n < STAT_NSECOND; ++n)
+        if (cs.seconds >> n & 1) c[n] = a[(NM + n) * cs.pitch];
+      {
+        // (no contraction, as in k_stats_cells: identical cells must leave delta = 0)
+#pragma clang fp contract(off)
+        p.V = p.V + v;
+        const double r = cstat_ratio(v, p.V), cf = v * (1.0 - r);
+        double d[NM];
+#pragma unroll
+        for (int n = 0; n < NM; ++n)
+          if (cs.means >> n & 1) {
+            d[n] = m[n] - p.M[n];
+            p.M[n] = p.M[n] + r * d[n];
+          }
+#pragma unroll
+        for (int n = 0; n < STAT_NSECOND; ++n)
+          if (cs.seconds >> n & 1) {
+            p.T[n] = p.T[n] + r * (c[n] - p.T[n]);
+            p.D[n] = p.D[n] + (cf * d[stat_second_a(n)]) * d[stat_second_b(n)];
+          }
+      }
+    }
+    if (++js == cj) { js = 0; ++ks; }
+  }
+  if (over_i) {
+    // the 64 lane partials of the wave: 6 steps, both lanes of a pair forming join(lower,
+    // upper), so that every lane ends with the same bits
+    for (int w = 1; w < 64; w <<= 1) {
+      CstatPartial<NM> o;
+      o.V = __shfl_xor(p.V, w);
+#pragma unroll
+      for (int n = 0; n < NM; ++n)
+        if (cs.means >> n & 1) o.M[n] = __shfl_xor(p.M[n], w);
+#pragma unroll
+      for (int n = 0; n < STAT_NSECOND; ++n)
+        if (cs.seconds >> n & 1) {
+          o.T[n] = __shfl_xor(p.T[n], w);
+          o.D[n] = __shfl_xor(p.D[n], w);
+        }
+      if (lane & w) {
+        cstat_join<NM>(o, p, cs.means, cs.seconds);
+        p = o;
+      } else {
+        cstat_join<NM>(p, o, cs.means, cs.seconds);
+      }
+    }
+    if (lane != 0) return;
+  }
+  double* rec = part + chunk * NQ * cs.nbin + bin;
+  rec[0] = p.V;
+#pragma unroll
+  for (int n = 0; n < NM; ++n)
+    if (cs.means >> n & 1) rec[(1 + n) * cs.nbin] = p.M[n];
+#pragma unroll
+  for (int n = 0; n < STAT_NSECOND; ++n)
+    if (cs.seconds >> n & 1) {
+      rec[(1 + NM + n) * cs.nbin] = p.T[n];
+      rec[(1 + NM + STAT_NSECOND + n) * cs.nbin] = p.D[n];
+    }
+}
+// One thread per (bin, requested id): the bin's chunk records joined in ascending order,
+// cov = T / W + D / V, then the factors of stat_cell_value; the volume times l_ref^3.
+__global__ void __launch_bounds__(64)
+k_cstat_join(CstatSpec cs, int nm, double W, OutSpec sp, const double* __restrict__ part,
+             double* __restrict__ out) {
+  const long bin = (long)blockIdx.x * blockDim.x + threadIdx.x;
+  if (bin >= cs.nbin) return;
+  const int id = sp.var[blockIdx.y], nq = cstat_nq(nm);
+  const bool second = id >= 12 && id < CSTAT_VOLUME, mean = id < 12;
+  const int sn = second ? id - 12 : 0;
+  const int qa = 1 + (second ? stat_second_a(sn) : mean ? id : 0);
+  const int qb = 1 + (second ? stat_second_b(sn) : mean ? id : 0);
+  double V = 0.0, Ma = 0.0, Mb = 0.0, T = 0.0, D = 0.0;
+  for (long ch = 0; ch < cs.nchunk; ++ch) {
+#pragma clang fp contract(off)
+    const double* rec = part + ch * nq * cs.nbin + bin;
+    const double V2 = rec[0], Vs = V + V2, r = cstat_ratio(V2, Vs);
+    if (id != CSTAT_VOLUME) {
+      const double da = rec[qa * cs.nbin] - Ma, db = rec[qb * cs.nbin] - Mb;
+      Ma = Ma + r * da;
+      Mb = Mb + r * db;
+      if (second) {
+        T = T + r * (rec[(1 + nm + sn) * cs.nbin] - T);
+        D = D + rec[(1 + nm + STAT_NSECOND + sn) * cs.nbin] + ((V * r) * da) * db;
+      }
+    }
+    V = Vs;
+  }
+  double val;
+  {
+#pragma clang fp contract(off)
+    if (id == CSTAT_VOLUME) val = V * (sp.l_ref * sp.l_ref * sp.l_ref);
+    else if (mean) val = stat_cell_value(id, Ma, W, sp);
+    else val = stat_cell_value(id, T / W + D / V, 1.0, sp);
+  }
+  out[(long)blockIdx.y * cs.nbin + bin] = val;
+}
+
 // ... and of the wall faces (ids relative to AGX_WSTAT_BASE): the factors of k_wall_pack
 __device__ __forceinline__ double stat_wall_factor(int v, const GasDev& g, const OutSpec& sp) {
   const double rR = sp.rho_ref, aR = sp.a_ref, lR = sp.l_ref, tR = sp.t_ref, muR = sp.mu_ref;

@@ -20,6 +20,36 @@ from .case import geometry as _geo
 EPS = 1.0e-30  # macros.hpp.in:20
 
 
+def pool_bins(parts):
+    """Join collapsed statistics (Solver.stats_collapse) of blocks that share the remaining
+    directions, or of ranks: parts is a list of (volume, means, covs) with volume an array over
+    the bins, means {name: array} and covs {key: array} of that shape; a key is a pair
+    (a, b) of names in means or a second moment of abi.STAT_PAIRS ("cov_uv", ...).  Joined in
+    list order by the pairwise form, r = V2 / (V1 + V2), delta = M2 - M1:
+        M = M1 + r delta;  cov = cov1 + r (cov2 - cov1) + (V1 r / V) delta_a delta_b
+    in numpy float64.  Parts with bit-identical means and covs return them bit for bit.
+    Returns (volume, means, covs)."""
+    vol, means, covs = parts[0]
+    vol = np.array(vol, dtype=np.float64)
+    means = {n: np.array(m, dtype=np.float64) for n, m in means.items()}
+    covs = {k: np.array(c, dtype=np.float64) for k, c in covs.items()}
+    for vol2, means2, covs2 in parts[1:]:
+        vol2 = np.asarray(vol2, dtype=np.float64)
+        total = vol + vol2
+        some = total != 0.0
+        r = np.where(some, vol2 / np.where(some, total, 1.0), 0.0)
+        cf = np.where(some, vol * r / np.where(some, total, 1.0), 0.0)
+        d = {n: np.asarray(means2[n], dtype=np.float64) - means[n] for n in means}
+        for k in covs:
+            a, b = k if isinstance(k, tuple) else abi.STAT_PAIRS[k]
+            covs[k] = covs[k] + r * (np.asarray(covs2[k], dtype=np.float64) - covs[k]) \
+                + cf * (d[a] * d[b])
+        for n in means:
+            means[n] = means[n] + r * d[n]
+        vol = total
+    return vol, means, covs
+
+
 class DistExchange:
     """An agx_exchange (include/aither_gfx950.h) on torch.distributed
     point-to-point with HOST buffers: what an MPI adapter would pass
@@ -426,6 +456,21 @@ class Solver:
                                             out.ctypes.data_as(abi.c_dp)), "output_pack")
         return out
 
+    def stats_collapse(self, gb, names, over):
+        """Time statistics of block gb's cells (abi.STAT_OUT and "volume") pooled, volume
+        weighted, over the index directions of `over` -- a string out of "i", "j", "k", e.g.
+        "ik" -- by the library (AGX_CSTAT_BASE): [nvar, *remaining extents in (k, j, i) order],
+        dimensional; over="ijk" gives [nvar].  A mean is the pooled mean, a second moment the
+        co-moment about the space-time mean of the bin.  pool_bins joins blocks and ranks."""
+        mask = abi.cstat_mask(over)
+        ni, nj, nk = self.case.blocks[gb].geom.n
+        rest = tuple(n for bit, n in ((4, nk), (2, nj), (1, ni)) if not mask & bit)
+        ids = (C.c_int32 * len(names))(*[abi.cstat_id(mask, n) for n in names])
+        out = np.empty((len(names),) + rest)
+        self.api.check(self.api.output_pack(self.ctx, self.block_ids[gb], len(names), ids,
+                                            out.ctypes.data_as(abi.c_dp)), "output_pack")
+        return out
+
     def wall_stats_pack(self, gb, names):
         """Time statistics of block gb's viscousWall faces (abi.WALL_STAT_OUT), shaped like
         wall_pack: {name: [one array per wall surface]}, dimensional."""
@@ -712,6 +757,9 @@ class MultigridSolver:
 
     def stats_pack(self, gb, names):
         return self.levels[0].stats_pack(gb, names)
+
+    def stats_collapse(self, gb, names, over):
+        return self.levels[0].stats_collapse(gb, names, over)
 
     def wall_stats_pack(self, gb, names):
         return self.levels[0].wall_stats_pack(gb, names)

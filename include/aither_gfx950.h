@@ -320,6 +320,47 @@ enum { AGX_LOAD_BASE = 256, AGX_LOAD_AREA = AGX_LOAD_BASE,
 enum { AGX_STAT_BASE = 512, AGX_STAT_END = 533 };
 enum { AGX_WSTAT_BASE = 576, AGX_WSTAT_END = 594 };
 
+/* the cell statistics collapsed along homogeneous index directions: a seventh range of
+ * agx_output_pack.  A channel is read as profiles over y, a flat plate as fields over (x, y):
+ * the time statistics pooled over the block's homogeneous directions, a few kilobytes where
+ * the 21 planes of AGX_STAT_BASE are gigabytes.
+ * id = AGX_CSTAT_BASE + 32 * mask + n.  mask: the collapsed directions, bit 0 = i, bit 1 = j,
+ * bit 2 = k, 1 ... 7.  A BIN is one position of the directions that remain (lines, planes, or
+ * with mask 7 the whole block).  With the volume v_c, the time means m_c, the time co-moments
+ * C_c of the bin's physical cells c and the sum of weights W:
+ *   V = sum v_c;   M = sum v_c m_c / V
+ *   cov_ab = sum v_c [ C_c,ab / W + (m_c,a - M_a)(m_c,b - M_b) ] / V
+ * cov_ab is the co-moment about the space-time mean of the bin (the law of total covariance).
+ * n = 0 ... 20: the variables of AGX_STAT_BASE in its order, a mean as the pooled mean M, a
+ * second moment as the pooled cov_ab; n = 21: the bin's volume V l_ref^3.
+ * The recurrence.  A bin is formed by the weighted one-pass recurrence of the time statistics,
+ * in space, cell by cell:
+ *   V += v;  r = v / V;  cf = v (1 - r);  delta = m - M
+ *   M += r delta;   T_ab += r (C_ab - T_ab);   D_ab += (cf delta_a) delta_b
+ * and two partial bins join by the pairwise form, r = V2 / (V1 + V2), delta = M2 - M1:
+ *   M = M1 + r delta;  T = T1 + r (T2 - T1);  D = D1 + D2 + ((V1 r) delta_a) delta_b
+ * The value is cov = T / W + D / V with the dimensional factors of AGX_STAT_BASE.  No sums of
+ * squares and no second pass.  Cells with bit-identical m and C give M = m and cov = C / W bit
+ * for bit -- what AGX_STAT_BASE returns for a cell of the bin -- whatever their volumes.
+ * Layout: out[v * nbin + bin], variable by variable in the caller's order; nbin is the product
+ * of the remaining extents, the bins ordered over the remaining directions as k, then j, then
+ * i, i fastest; mask 7 gives one bin.  Dimensional, like the cell range.
+ * Refused by name, with nothing written: a call before the block's first sample; mask 0 or a
+ * mask above 7; n above 21; ids of two masks in one call; these ids with ids of another range
+ * in one call; more than AGX_CSTAT_COUNT ids (repeated ids are allowed); mean
+ * turbulentViscosity, tke and sdr wherever AGX_STAT_BASE refuses them.
+ * Timing and legality.  Reads the accumulators and the volume plane only: legal at every
+ * position, and the run stays bit-identical.  Only the planes of the requested ids are read (a
+ * second moment reads its two means).  Not a collective: a rank gets the bins of its own
+ * block; blocks that share the remaining directions, and ranks, are joined by the caller with
+ * the pairwise form from (V, M, cov): cov = cov1 + r (cov2 - cov1) + (V1 r / V) delta_a delta_b.
+ * Determinism.  No floating-point atomics, and a shape of the recurrence and of the joins
+ * fixed by the block's extents and the mask alone (the collapsed j and k positions in chunks
+ * of 64, k outer; a collapsed row by 64 strided lanes joined by a butterfly; the chunks added
+ * in ascending order): two calls, and any subset, order or repetition of ids, return the same
+ * bits. */
+enum { AGX_CSTAT_BASE = 1024, AGX_CSTAT_COUNT = 22, AGX_CSTAT_END = 2048 };
+
 /* what a halo exchange carries (gridLevel.cpp:299-313, utility.cpp:400-423) */
 enum { AGX_HALO_STATE = 0, AGX_HALO_UPDATE = 1,
        /* velocityGrad_ of the cells across connection surfaces, swapped after the
@@ -573,8 +614,9 @@ int agx_phase_implicit_update(agx_ctx *ctx, int mm, double *l2, agx_linf *linf);
  * out[v * nsurf + surface], see the enum.
  * Time statistics (no counterpart in output.cpp): with statistics ids (AGX_STAT_BASE + n) one
  * value per physical cell in the layout of the cell variables, with wall statistics ids
- * (AGX_WSTAT_BASE + n) one value per wall face in the layout of the wall variables; see the
- * enums for what they refuse.
+ * (AGX_WSTAT_BASE + n) one value per wall face in the layout of the wall variables; with
+ * collapsed statistics ids (AGX_CSTAT_BASE + 32 * mask + n) one value per bin of the
+ * directions that remain, out[v * nbin + bin]; see the enums for what they refuse.
  * Refused: variables of two ranges in one call, an id in no range, a block without a
  * viscousWall surface, an inviscid context, wall-law surfaces before the first residual (the
  * three: wall variables), the four node variables named above, nvar beyond the number of ids

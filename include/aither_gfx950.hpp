@@ -222,6 +222,19 @@ class hotPath {
     Check(AGX_SYM(output_pack)(ctx_, block, static_cast<int>(ids.size()), ids.data(), out),
           "hotPath::WallStatistics");
   }
+  // the id of statistics variable n (0 ... 20 in the order of AGX_STAT_BASE, 21 the bin's
+  // volume) collapsed along the index directions of mask (bit 0 = i, 1 = j, 2 = k)
+  static int32_t CollapsedStatisticId(int mask, int n) { return AGX_CSTAT_BASE + 32 * mask + n; }
+  // the listed statistics (n as above) of the block's cells pooled, volume weighted, over the
+  // directions of mask (AGX_CSTAT_BASE): out[v * nbin + bin], the bins over the remaining
+  // directions, i fastest; dimensional.  Reads the accumulators and the volumes only
+  void CollapsedStatistics(int block, int mask, const std::vector<int32_t> &ids,
+                           double *out) const {
+    std::vector<int32_t> full(ids);
+    for (auto &v : full) v = CollapsedStatisticId(mask, v);
+    Check(AGX_SYM(output_pack)(ctx_, block, static_cast<int>(full.size()), full.data(), out),
+          "hotPath::CollapsedStatistics");
+  }
   // the block's raw accumulators (AGX_FIELD_STAT_ACCUM: 4 header values, the cell planes, the
   // wall rows; the caller sizes `payload` as the C header states) for a checkpoint, and back
   void StatisticsPayload(int block, double *payload) const {
