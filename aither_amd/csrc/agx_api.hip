@@ -280,6 +280,9 @@ struct agx_ctx : agx::Switches {
   // behind the norm read-back the host waits for, so that the GPU does not idle
   // while the host turns the iteration around
   bool in_iterate = false, ghosts_prefilled = false;
+  // the transport's swap has failed (halo_exchange_remote): agx_iterate ends the call there
+  // wherever the exchange was posted from -- the update's eager ghost fill included
+  bool swap_failed = false;
   // the caller's own agx_phase_bc_faces has run and the agx_phase_residual that reads its
   // ghost cells has not: the output paths that refill the ghost cells are refused
   bool ghost_fill_open = false;
@@ -3979,8 +3982,13 @@ static int halo_exchange_remote(agx_ctx* c, int what) {
                             c->stream));
     HIPCHK(hipStreamSynchronize(c->stream));
   }
-  if (c->ex.swap(c->ex.user, (int)c->slabs.size(), c->slabs.data(), c->stream))
+  // (a transport that fails says why itself -- the RCCL one does -- or leaves the text empty:
+  // what an earlier failure left in it is not this swap's)
+  g_err[0] = '\0';
+  if (c->ex.swap(c->ex.user, (int)c->slabs.size(), c->slabs.data(), c->stream)) {
+    c->swap_failed = true;
     return g_err[0] ? 1 : fail("the exchange's swap operation failed");
+  }
   if (c->ex.host_buffers)
     for (auto& r : c->remote)
       HIPCHK(hipMemcpyAsync(r.recv.get(), r.hrecv.get(), sizeof(double) * r.count, hipMemcpyHostToDevice,
@@ -4070,6 +4078,7 @@ int reduce_over_ranks(agx_ctx* c, double* l2, agx_linf* linf, double* matrix_res
   mine.k = linf->k; mine.eqn = linf->eqn;
   mine.status = status;
   Rec* all = c->rec_host.get() + 1;
+  if (!status) g_err[0] = '\0';      // (a failing all-gather names itself, see the swap)
   if (c->ex.host_buffers) {
     if (c->ex.allgather(c->ex.user, &mine, all, (int64_t)sizeof(Rec), c->stream))
       return g_err[0] ? 1 : fail("the exchange's allgather operation failed");
@@ -4120,13 +4129,30 @@ int agx_iterate(agx_ctx* c, int mm, double cfl, double* l2, agx_linf* linf,
   // leave the other ranks waiting in a collective: from the first failure on the compute
   // phases are skipped, the exchanges and the final all-gather are still reached, and the
   // status word of the norm record fails the call on every rank.
+  // The count: a rank that fails posts exactly the exchanges a healthy rank posts in the same
+  // call -- its peers are healthy ranks.  The last of them is the state exchange of the eager
+  // ghost fill, which the update queues BEFORE the device's error word is read
+  // (check_device_error, behind the one host synchronisation): a failure the device found
+  // (spin limit, singular block, thermally perfect energy, boundary variant) surfaces with
+  // that exchange already posted, a failure before the update (a refused phase) without it.
+  // So the fill is made up for at the end only where this call has not queued it
+  // (!ghosts_prefilled), and the ghost cells then count as filled for the next call as they do
+  // on the healthy ranks.  An exchange that itself fails ends the call wherever it was posted
+  // from, the update's fill included (swap_failed).
   int st = 0;
   char first_err[sizeof g_err] = "";
   const bool collective = c->have_ex && c->ex.nranks > 1;
+  c->swap_failed = false;
   auto phase = [&](int r) {
     if (r && !st) { st = r; memcpy(first_err, g_err, sizeof g_err); }
   };
-#define AGX_PHASE(call) do { if (!st) phase(call); } while (0)
+#define AGX_PHASE(call)                                             \
+  do {                                                              \
+    if (!st) {                                                      \
+      phase(call);                                                  \
+      if (c->swap_failed) return st;   /* (the update's eager fill) */ \
+    }                                                               \
+  } while (0)
   // an exchange runs even after a local failure when other ranks take part in it; a
   // failure of the exchange itself cannot be hidden from the peers and ends the call
 #define AGX_XCHG(what)                                              \
@@ -4183,8 +4209,15 @@ int agx_iterate(agx_ctx* c, int mm, double cfl, double* l2, agx_linf* linf,
   }
 #undef AGX_PHASE
 #undef AGX_XCHG
-  // the update queues the next call's ghost fill -- an exchange -- behind its norms
-  if (st && collective && c->eager_ghosts) (void)fill_ghosts(c);
+  // the update queues the next call's ghost fill -- an exchange -- behind its norms; a call
+  // that failed before its update posts it here, one that failed in it has posted it
+  if (st && collective && c->eager_ghosts && !c->ghosts_prefilled) {
+    if (fill_ghosts(c)) {
+      if (c->swap_failed) { memcpy(g_err, first_err, sizeof g_err); return st; }
+    } else {
+      ghosts_filled_ahead(c);
+    }
+  }
   if (st) memcpy(g_err, first_err, sizeof g_err);
   if (c->have_ex) return reduce_over_ranks(c, l2, linf, matrix_resid, l2_in, linf_in, st);
   return st;

@@ -55,15 +55,29 @@ class DistExchange:
     point-to-point with HOST buffers: what an MPI adapter would pass
     (MPI_Sendrecv / MPI_Allgather), here over gloo for the multi-process tests.
     The production transport is the library's own RCCL one
-    (agx_rccl_exchange_create)."""
+    (agx_rccl_exchange_create).
+
+    A ctypes callback that raises would print the exception and return 0 -- a transport that
+    timed out would look like a completed exchange.  So both callbacks return 1 on an
+    exception and keep it in `pending`; Solver raises it with the failed call."""
 
     def __init__(self, world, group=None):
         import torch
         import torch.distributed as dist
         self.torch, self.dist, self.world, self.group = torch, dist, world, group
-        self._swap = abi.SWAP_FN(self.swap)
-        self._allgather = abi.ALLGATHER_FN(self.allgather)
+        self.pending = None
+        self._swap = abi.SWAP_FN(self._guard(self.swap))
+        self._allgather = abi.ALLGATHER_FN(self._guard(self.allgather))
         self.struct = abi.Exchange(None, self._swap, self._allgather, world, 1)
+
+    def _guard(self, fn):
+        def guarded(*args):
+            try:
+                return fn(*args)
+            except Exception as exc:
+                self.pending = exc
+                return 1
+        return guarded
 
     def _view(self, ptr, n, dtype):
         ct = C.c_double if dtype == np.float64 else C.c_uint8
@@ -577,10 +591,24 @@ class Solver:
         l2 = np.zeros(n_eq)
         linf = abi.Linf()
         mres = C.c_double(0.0)
-        self.api.check(self.api.iterate(
+        self._check(self.api.iterate(
             self.ctx, mm, cfl, l2.ctypes.data_as(abi.c_dp), C.byref(linf),
             C.byref(mres)), "iterate")
         return l2, linf, mres.value
+
+    def _check(self, rc, what):
+        """api.check for a call that runs the exchange: an exception one of its callbacks
+        raised (kept in exchange.pending; the library saw a failed operation) is the cause of
+        the RuntimeError and named in its text."""
+        exc = getattr(self._exchange, "pending", None)
+        if exc is not None:
+            self._exchange.pending = None
+        try:
+            self.api.check(rc, what)
+        except RuntimeError as err:
+            if exc is None:
+                raise
+            raise RuntimeError(f"{err} [the exchange raised {exc!r}]") from exc
 
     def normalized(self, l2sq, nn, mm):
         """PrintResiduals (output.cpp:1028-1087) for the single-species case."""

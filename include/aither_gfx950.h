@@ -795,6 +795,13 @@ typedef struct agx_exchange {
    * in rank order */
   int (*allgather)(void *user, const void *send, void *recv, int64_t bytes,
                    void *hip_stream);
+  /* Both return 0, or non-zero for an operation that did not complete (a time-out
+   * included: a callback must never report an exchange it gave up on as done).
+   * A failing operation ends the agx_iterate call where it is -- nothing is posted
+   * after it, the peers cannot be helped -- with "the exchange's swap / allgather
+   * operation failed", or, after an earlier failure of this rank's own, that one's
+   * text.  A rank that fails on its own posts what a healthy rank posts, in the
+   * failing call and after it, and every rank's call returns non-zero. */
   int32_t nranks;
   int32_t host_buffers;
 } agx_exchange;

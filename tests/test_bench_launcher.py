@@ -49,9 +49,17 @@ def test_world_size_mismatch_is_an_error():
 
 
 def test_failing_rank_fails_the_command():
-    # an unknown workload makes every rank exit non-zero; the parent must relay that
-    r = _run(["--gpus", "2", "--backend", "gloo", "--workload", "nope", "--rendezvous-only"])
+    """The ranks are launched and fail there: --size 0 passes the parent's argument parser
+    and divides by zero in each rank's rank_local_chain_case (the thin neighbour's thickness
+    over n).  The launcher relays the children's failure -- a non-zero return code, the
+    child's traceback on stderr."""
+    r = _run(["--gpus", "2", "--backend", "gloo", "--size", "0", "--workload", "rk4",
+              "--rendezvous-only"], timeout=300)
     assert r.returncode != 0
+    assert "ZeroDivisionError" in r.stderr and "rank_local_chain_case" in r.stderr, \
+        r.stderr[-2000:]
+    # (the parent itself refuses nothing here: its own refusals never reach a rank)
+    assert "usage:" not in r.stderr
 
 
 def test_dump_outputs_writes_state_and_norms(oracle, tmp_path, monkeypatch):

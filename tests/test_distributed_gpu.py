@@ -340,3 +340,79 @@ def test_dplur_interior_boundary_split(oracle, solver, div):
     _check_components(case, ref, split[0][1], {**split[0][0], **split[1][0]})
     _check_records(case, ref, [split[0][2], split[1][2]], True)
     ref.close()
+
+
+# ---- a rank that fails: every rank returns the failure, none waits in a collective -------
+def _failing_rank_worker(rank, port, name, q):
+    from datetime import timedelta
+    os.environ["MASTER_ADDR"] = "127.0.0.1"
+    os.environ["MASTER_PORT"] = str(port)
+    # (a bound on every gloo operation: an unmatched one raises into the exchange's callback
+    # instead of waiting for ever)
+    dist.init_process_group("gloo", rank=rank, world_size=2, timeout=timedelta(seconds=60))
+    import failure_decks as fd
+    lib, case = fd.deck(name, [0, 1])
+    if rank == 1:      # the trigger is this rank's alone
+        if name == "tp":
+            case.deck.cfl_start = case.deck.cfl_max = fd.TP_CFL_TRIGGER
+        else:
+            os.environ["AGX_SPIN_LIMIT"] = "1"      # (read when the context is created)
+    sol = Solver(lib, case, rank=rank, exchange=DistExchange(2))
+    at, msg = None, None
+    for nn in range(fd.WALK):
+        try:
+            sol.step(nn)
+        except RuntimeError as err:
+            at, msg = nn, str(err)
+            break
+    q.put((rank, at, msg))
+    dist.barrier()
+    sol.close()
+    dist.destroy_process_group()
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("name", ["kp", "tp"])
+def test_failing_rank_fails_both_ranks_and_both_return(oracle, name):
+    """Two ranks on cuda:0 over gloo, rank 1 alone with a failure (the LU-SGS sweep's spin
+    limit; a thermally perfect explicit step that numpy says takes a cell below the heat of
+    formation): both ranks fail the same call -- rank 1 with its own cause, rank 0 told that
+    rank 1 failed -- and both go on to a barrier and exit.  A failing rank that posted an
+    exchange more than its peer would end in the transport's timeout instead."""
+    import queue
+    import re
+    import time
+    import failure_decks as fd
+    if name == "tp":
+        _, case = fd.deck("tp")
+        low = fd.energy_margin(oracle, case, fd.TP_CFL_TRIGGER)
+        ok = fd.energy_margin(oracle, case, fd.TP_CFL)
+        assert low[1] < 0.0 < ok[0], (low, ok)
+    ctx = mp.get_context("spawn")
+    q = ctx.Queue()
+    with socket.socket() as s:
+        s.bind(("127.0.0.1", 0))
+        port = s.getsockname()[1]
+    procs = [ctx.Process(target=_failing_rank_worker, args=(r, port, name, q)) for r in range(2)]
+    for p in procs:
+        p.start()
+    try:
+        res, deadline = {}, time.monotonic() + 240
+        while len(res) < 2 and time.monotonic() < deadline:
+            try:
+                rank, at, msg = q.get(timeout=1.0)
+                res[rank] = (at, msg)
+            except queue.Empty:      # (a worker that died will not report: do not wait for it)
+                if any(p.exitcode not in (None, 0) for p in procs):
+                    break
+        assert sorted(res) == [0, 1], (res, [p.exitcode for p in procs])
+        for p in procs:
+            p.join(timeout=90)
+        assert [p.exitcode for p in procs] == [0, 0]
+    finally:
+        for p in procs:
+            if p.is_alive():
+                p.terminate()
+    assert res[0][0] is not None and res[0][0] == res[1][0], res
+    assert (fd.ENERGY_MATCH if name == "tp" else fd.SPIN_MATCH) in res[1][1], res[1]
+    assert re.search(r"rank 1 failed \(status", res[0][1]), res[0]

@@ -843,9 +843,11 @@ def test_plane_sweep_forms_agree_bitwise(agx_rans):
 @pytest.mark.gpu
 def test_pipelined_sweep_spin_limit_error_path_and_recovery(agx_rans):
     """k_lusgs_pipe: a k-plane that polls longer than AGX_SPIN_LIMIT for the plane below
-    raises the error flag, every workgroup leaves, agx_iterate returns the error; the SAME
-    context then sets its pipeline up afresh -- with a sane limit a fresh context gives the
-    states of the launch-per-hyperplane form (wallLaw: two blocks, BLU-SGS)."""
+    raises the error flag, every workgroup leaves, agx_iterate returns the error; that context
+    is closed, and with a sane limit FRESH contexts give the states of the
+    launch-per-hyperplane form (wallLaw: two blocks, BLU-SGS).  The same context used again
+    after its failure (the pipeline set up afresh, `pipe_nblocks = 0`):
+    tests/test_failure_protocol_gpu.py::test_spin_limit_then_the_same_context_recovers."""
     with switches(AGX_SPIN_LIMIT="1"):
         s = Solver(agx_rans, golden_case("wallLaw"))
     with pytest.raises(RuntimeError, match="spin limit"):
