@@ -80,6 +80,18 @@ for _n, _base in (("pressureMoment", 11), ("viscousMoment", 14)):
     for _q, _c in enumerate("xyz"):
         LOAD_OUT[f"{_n}_{_c}"] = LOAD_BASE + _base + _q
 LOAD_MOMENTS = tuple(_n for _n in LOAD_OUT if "Moment" in _n)
+# boundary fluxes (AGX_FLUX_*): one value per flux surface, positive out of the block; and the
+# block balance (AGX_BUDGET_*): one value per id.  EQUATIONS: the library's equations in order.
+EQUATIONS = ("mass", "mom_x", "mom_y", "mom_z", "energy", "tke", "sdr")
+FLUX_BASE, FLUX_END, BUDGET_BASE, BUDGET_END = 384, 399, 448, 463
+FLUX_OUT = {"area": FLUX_BASE}
+BUDGET_OUT = {"volume": BUDGET_BASE}
+for _q, _c in enumerate(EQUATIONS):
+    FLUX_OUT[f"inviscid_{_c}"] = FLUX_BASE + 1 + _q
+    BUDGET_OUT[f"total_{_c}"] = BUDGET_BASE + 1 + _q
+for _q, _c in enumerate(EQUATIONS):
+    FLUX_OUT[f"viscous_{_c}"] = FLUX_BASE + 8 + _q
+    BUDGET_OUT[f"residual_{_c}"] = BUDGET_BASE + 8 + _q
 # time statistics of the cells (AGX_STAT_BASE + n): means, velocity co-moments, variances
 STAT_BASE, STAT_END = 512, 533
 STAT_OUT = {_n: STAT_BASE + _q for _q, _n in enumerate(

@@ -9,6 +9,7 @@
 #include "agx_geometry.hpp"
 #include "agx_start.hpp"
 #include "agx_stats.hpp"
+#include "agx_flux.hpp"
 #include "agx_mem.hpp"
 #include "agx_switches.hpp"
 #include <rccl/rccl.h>
@@ -148,6 +149,15 @@ struct Block {
   DevBuf<LoadSurfDev> load_tab_dev;
   long load_faces = 0, load_chunks = 0;
   DevBuf<double> load_partial, load_fcen;
+  // flux surfaces (agx_flux.hpp): every surface in the order given but the connections to
+  // other ranks -- which the connections decide, so the table is made by the first flux call
+  // after the last agx_block_set_bcs / agx_conn_create -- their chunks and the chunk records
+  // of a call; the chunk records of the block balance
+  std::vector<FluxSurfDev> flux_tab;
+  DevBuf<FluxSurfDev> flux_tab_dev;
+  bool flux_tab_built = false;
+  long flux_chunks = 0;
+  DevBuf<double> flux_partial, budget_partial;
   // time statistics (agx_stats.hpp): the cell accumulator planes (null before the first
   // sample: a context that never samples allocates nothing), the wall rows of a viscous block
   // with viscousWall faces, the sum of weights and the number of samples
@@ -276,6 +286,8 @@ struct agx_ctx : agx::Switches {
   std::map<std::array<int, 6>, TilePlan> tile_plans;
   bool have_time_n = false;  // agx_store_time_n has run (nonreflecting BCs read consVarsN)
   bool have_wall_data = false;   // a residual's viscous ghost fill has stored the wall-law data
+  bool have_residual = false;    // the residual planes hold a residual (agx_phase_residual, or
+                                 // an upload of AGX_FIELD_RESIDUAL): AGX_BUDGET_RESIDUAL
   // agx_iterate fills the ghost cells for the NEXT call right after the update,
   // behind the norm read-back the host waits for, so that the GPU does not idle
   // while the host turns the iteration around
@@ -1985,6 +1997,7 @@ int agx_block_set_bcs(agx_ctx* c, int id, int n, const agx_bc_surface* s) {
   if (id < 0 || id >= (int)c->blocks.size()) return fail("bad block id %d", id);
   Block& b = c->blocks[id];
   b.sweep_graph.drop();                      // (they hold the old BlockDev)
+  b.flux_tab_built = false;
   b.surf_host.assign(s, s + n);
   // (a view in b.d follows its owner only once the owner holds the new memory: a failing
   // call leaves none dangling)
@@ -2121,6 +2134,7 @@ int agx_block_set_bcs(agx_ctx* c, int id, int n, const agx_bc_surface* s) {
 int agx_conn_create(agx_ctx* c, const agx_connection* cc, int* conn_id) {
   c->conns.emplace_back();
   c->conns.back().c = *cc;
+  for (auto& b : c->blocks) b.flux_tab_built = false;   // (remote connections leave the table)
   *conn_id = (int)c->conns.size() - 1;
   return 0;
 }
@@ -2451,7 +2465,9 @@ static int d2_x_copy(agx_ctx* c, Block& b, int to_d2) {
 // The viscous-wall fill stays in the ghost cells, so between the caller's agx_phase_bc_faces
 // and the agx_phase_residual that follows it -- whose inviscid fluxes would read it -- the
 // call is refused (include/aither_gfx950.h "reads between phases").
-static int ghosts_for_output(agx_ctx* c, const char* who) {
+// (in its two halves for the boundary fluxes, which read the ghost cells of both fills: the
+// inviscid flux of a residual sees a viscousWall as a slip wall)
+static int ghosts_for_output_inviscid(agx_ctx* c, const char* who) {
   if (c->ghost_fill_open)
     return fail("%s: gradients, node and wall variables refill the ghost cells, which are "
                 "being filled for the coming residual (agx_phase_bc_faces was called, "
@@ -2462,12 +2478,18 @@ static int ghosts_for_output(agx_ctx* c, const char* who) {
     if (agx_halo_swap_local(c, AGX_HALO_STATE)) return 1;
     if (bc_edges(c)) return 1;
   }
+  return 0;
+}
+static int ghosts_for_output_viscous(agx_ctx* c) {
   if (c->cfg.is_viscous) {
     if (bc_pass(c, true, 2)) return 1;     // (2: the stored wall-law data stay the last residual's)
     if (bc_pass(c, false, 1)) return 1;
   }
   ghost_fill_gone(c);   // (the next iteration starts from its own inviscid fill)
   return 0;
+}
+static int ghosts_for_output(agx_ctx* c, const char* who) {
+  return ghosts_for_output_inviscid(c, who) || ghosts_for_output_viscous(c);
 }
 
 int agx_field_download(agx_ctx* c, int id, int field, double* out) {
@@ -2612,6 +2634,143 @@ int wall_loads(agx_ctx* c, int id, int nvar, const int32_t* vars, double* out) {
                      b.load_chunks, 1.0 / c->gas.scaling, b.load_partial.get(), tmp);
   return copy_out(c, out, tmp, (size_t)nvar * nsurf);
 }
+// Does surface s of block id belong to a connection whose partner is on another rank?  (The
+// ranges of a connection are cell ranges along d1 = d3 + 1 and d2 = d3 + 2, dirs_of.)
+bool surface_is_remote(const agx_ctx* c, int id, const agx_bc_surface& s) {
+  if (s.bc_type != AGX_BC_INTERBLOCK && s.bc_type != AGX_BC_PERIODIC) return false;
+  const int st = surface_type(s);
+  int d1, d2, d3;
+  dirs_of(st, d1, d2, d3);
+  const int lo[3] = {s.imin, s.jmin, s.kmin}, hi[3] = {s.imax, s.jmax, s.kmax};
+  for (const auto& k : c->conns) {
+    const int m = my_side(c, k);
+    if (m < 0 || k.c.local_block[m] != id || k.c.boundary[m] != st) continue;
+    if (k.c.d1_start[m] < hi[d1] && k.c.d1_end[m] > lo[d1] && k.c.d2_start[m] < hi[d2] &&
+        k.c.d2_end[m] > lo[d2])
+      return true;
+  }
+  return false;
+}
+// the table of the flux surfaces of a block (agx_flux.hpp), from its surfaces and the
+// connections as they are now
+int flux_table(agx_ctx* c, int id) {
+  Block& b = c->blocks[id];
+  if (b.flux_tab_built) return 0;
+  b.flux_tab.clear();
+  b.flux_chunks = 0;
+  const int nn[3] = {b.d.ni, b.d.nj, b.d.nk};
+  for (size_t q = 0; q < b.surf_host.size(); ++q) {
+    const agx_bc_surface& s = b.surf_host[q];
+    if (surface_is_remote(c, id, s)) continue;
+    FluxSurfDev w;
+    const int lo[3] = {s.imin, s.jmin, s.kmin}, hi[3] = {s.imax, s.jmax, s.kmax};
+    w.side = surface_type(s);
+    const int d3 = (w.side - 1) / 2;
+    for (int d = 0; d < 3; ++d) {
+      w.lo[d] = lo[d];
+      w.n[d] = d == d3 ? 1 : hi[d] - lo[d];
+      // (the kernel indexes the planes from these: they must lie on the block)
+      if (lo[d] < 0 || hi[d] > nn[d] || w.n[d] < 1 ||
+          (d == d3 && (lo[d] != (w.side % 2 == 1 ? 0 : nn[d]) || hi[d] != lo[d])))
+        return fail("agx_output_pack: surface %d does not lie on a side of block %d", (int)q, id);
+    }
+    w.chunk0 = b.flux_chunks;
+    b.flux_chunks += ((long)w.n[0] * w.n[1] * w.n[2] + FLUX_CHUNK - 1) / FLUX_CHUNK;
+    b.flux_tab.push_back(w);
+  }
+  HIPCHK(hipStreamSynchronize(c->stream));     // (before the old table and records are freed)
+  HIPCHK(b.flux_tab_dev.upload(b.flux_tab));
+  b.flux_partial.reset();
+  if (b.flux_chunks > 0) HIPCHK(b.flux_partial.alloc((size_t)b.flux_chunks * FLUX_NQ));
+  b.flux_tab_built = true;
+  return 0;
+}
+// equations 5 and 6 (rho k, rho omega) of the flux and budget ranges in a 5-equation library
+int flux_eq_refused(const char* range, int q, int var) {
+  return AGX_NEQ == 5 && q > 0 && (q - 1) % FLUX_NE >= AGX_NEQ
+             ? fail("agx_output_pack: %s variable %d (tke, sdr) is not kept by the 5-equation "
+                    "libraries", range, var)
+             : 0;
+}
+// The fluxes through the flux surfaces of one block (the ids are flux ids, nvar is in their
+// range): k_surface_flux's chunk records, then k_surface_flux_sum
+int surface_fluxes(agx_ctx* c, int id, int nvar, const int32_t* vars, double* out) {
+  Block& b = c->blocks[id];
+  if (!c->finalized) return fail("agx_setup_finalize has not been called");
+  for (int v = 0; v < nvar; ++v)
+    if (flux_eq_refused("flux", vars[v] - AGX_FLUX_BASE, vars[v])) return 1;
+  if (flux_table(c, id)) return 1;
+  if (b.flux_tab.empty())
+    return fail("agx_output_pack: block %d has no flux surface (every surface it has is a "
+                "connection to another rank)", id);
+  const bool viscous = c->cfg.is_viscous != 0;
+  if (viscous && b.d.wallv && !c->have_wall_data)
+    return fail("agx_output_pack: the wall-law surfaces hold no wall data before the first "
+                "residual");
+  const int halo = c->cfg.recon == AGX_RECON_CONSTANT ? 1 : c->cfg.recon == AGX_RECON_MUSCL ? 2 : 3;
+  if (halo > b.d.ng)
+    return fail("agx_output_pack: flux variables: the reconstruction reaches %d cells across a "
+                "face, the blocks have %d ghost layers", halo, b.d.ng);
+  const int nsurf = (int)b.flux_tab.size();
+  double* tmp = nullptr;
+  if (stage_buffer(c, (size_t)nvar * nsurf, &tmp)) return 1;
+  // viscous or not, a boundary face's flux reads the ghost cells, those the next residual
+  // would see: its inviscid fill for the inviscid flux (a viscousWall is a slip wall there),
+  // then its viscous-wall fill for the viscous one
+  if (ghosts_for_output_inviscid(c, "agx_output_pack")) return 1;
+  const dim3 grid((unsigned)b.flux_chunks), tb(FLUX_CHUNK);
+  // (reconstruction, limiter, flux) as launch_inv instantiates the gather-form residual
+  by_int<AGX_RECON_CONSTANT, AGX_RECON_MUSCL, AGX_RECON_WENO, AGX_RECON_WENOZ>(
+      c->cfg.recon, [&](auto recon) {
+        constexpr int RECON = decltype(recon)::value;
+        auto launch = [&](auto lim) {
+          by_int<AGX_FLUX_ROE, AGX_FLUX_AUSM>(c->cfg.inviscid_flux, [&](auto flux) {
+            hipLaunchKernelGGL(
+                (k_surface_flux<RECON, decltype(lim)::value, decltype(flux)::value>), grid, tb,
+                0, c->stream, b.d, c->gas, c->sp.kappa, b.flux_tab_dev.get(), nsurf,
+                b.flux_partial.get());
+          });
+        };
+        if constexpr (RECON == AGX_RECON_MUSCL)
+          by_int<AGX_LIMITER_VANALBADA, AGX_LIMITER_MINMOD, AGX_LIMITER_NONE>(c->cfg.limiter,
+                                                                               launch);
+        else
+          launch(std::integral_constant<int, AGX_LIMITER_NONE>{});
+      });
+  if (ghosts_for_output_viscous(c)) return 1;
+  if (viscous) {
+    const int fourth = (c->cfg.viscous_recon == AGX_VISC_RECON_CENTRAL_4TH ? 1 : 0) |
+                       (c->sp.les ? 2 : 0);
+    hipLaunchKernelGGL(k_surface_flux_visc, grid, tb, 0, c->stream, b.d, c->gas,
+                       b.flux_tab_dev.get(), nsurf, fourth, b.flux_partial.get());
+  }
+  hipLaunchKernelGGL(k_surface_flux_sum, dim3((unsigned)((nvar * nsurf + 63) / 64)), dim3(64), 0,
+                     c->stream, out_spec(c, b, nvar, vars), b.flux_tab_dev.get(), nsurf,
+                     b.flux_chunks, viscous ? 1 : 0, b.flux_partial.get(), tmp);
+  return copy_out(c, out, tmp, (size_t)nvar * nsurf);
+}
+// The balance of one block (the ids are budget ids, nvar is in their range): physical cells
+// only, legal at every position
+int block_budget(agx_ctx* c, int id, int nvar, const int32_t* vars, double* out) {
+  Block& b = c->blocks[id];
+  for (int v = 0; v < nvar; ++v) {
+    if (flux_eq_refused("budget", vars[v] - AGX_BUDGET_BASE, vars[v])) return 1;
+    if (vars[v] >= AGX_BUDGET_RESIDUAL && !c->have_residual)
+      return fail("agx_output_pack: budget variable %d is a sum of the residual, and no residual "
+                  "has been formed yet (agx_phase_residual, agx_iterate)", vars[v]);
+  }
+  const long rows = (long)b.d.nj * b.d.nk;
+  const long nchunk = (rows + BUDGET_CHUNK - 1) / BUDGET_CHUNK;
+  if (!b.budget_partial) HIPCHK(b.budget_partial.alloc((size_t)nchunk * FLUX_NQ));
+  double* tmp = nullptr;
+  if (stage_buffer(c, (size_t)nvar, &tmp)) return 1;
+  hipLaunchKernelGGL(k_block_budget, dim3((unsigned)((nchunk * 64 + 255) / 256)), dim3(256), 0,
+                     c->stream, b.d, c->gas, nchunk, c->have_residual ? 1 : 0,
+                     b.budget_partial.get());
+  hipLaunchKernelGGL(k_block_budget_sum, dim3(1), dim3(64), 0, c->stream,
+                     out_spec(c, b, nvar, vars), nchunk, b.budget_partial.get(), tmp);
+  return copy_out(c, out, tmp, (size_t)nvar);
+}
 // WriteFunFile's payload of one block, or (node) WriteNodeFun's: one value per physical cell
 // or per node; vars: cell ids
 int point_pack(agx_ctx* c, int id, bool node, int nvar, const int32_t* vars, double* out) {
@@ -2659,7 +2818,13 @@ int agx_output_pack(agx_ctx* c, int id, int nvar, const int32_t* vars, double* o
   // cell variables, wall variables (WriteWallFun), node variables (WriteNodeFun) or integrated
   // wall loads, each range with its own bound on nvar
   int n_wall = 0, n_node = 0, n_load = 0, n_stat = 0, n_wstat = 0, n_cstat = 0;
+  int n_flux = 0, n_budget = 0;
   for (int v = 0; v < nvar; ++v) {
+    const bool flux = vars[v] >= AGX_FLUX_BASE && vars[v] < AGX_FLUX_END;
+    const bool budget = vars[v] >= AGX_BUDGET_BASE && vars[v] < AGX_BUDGET_END;
+    n_flux += flux;
+    n_budget += budget;
+    if (flux || budget) continue;
     const bool cell = vars[v] >= 0 && vars[v] < AGX_OUT_COUNT;
     const bool wall = vars[v] >= AGX_WALL_YPLUS && vars[v] < AGX_WALL_END;
     const bool node = vars[v] >= AGX_NODE_BASE && vars[v] < AGX_NODE_END;
@@ -2675,6 +2840,21 @@ int agx_output_pack(agx_ctx* c, int id, int nvar, const int32_t* vars, double* o
     n_load += load;
     n_stat += stat;
     n_wstat += wstat;
+  }
+  // the boundary fluxes and the block balance (agx_flux.hpp)
+  if (n_flux > 0 || n_budget > 0) {
+    const bool is_flux = n_flux > 0;
+    const int mine = is_flux ? n_flux : n_budget;
+    const char* other = is_flux && n_budget > 0 ? "budget"
+                        : n_cstat > 0 ? "collapsed statistics" : n_wstat > 0 ? "wall statistics"
+                        : n_stat > 0 ? "statistics" : n_load > 0 ? "load" : n_node > 0 ? "node"
+                        : n_wall > 0 ? "wall" : mine != nvar ? "cell" : nullptr;
+    if (other)
+      return fail("agx_output_pack: %s and %s variables in one call (a call holds ids of one "
+                  "range)", other, is_flux ? "flux" : "budget");
+    if (nvar > AGX_FLUX_END - AGX_FLUX_BASE)
+      return fail("agx_output_pack: nvar %d out of range", nvar);
+    return is_flux ? surface_fluxes(c, id, nvar, vars, out) : block_budget(c, id, nvar, vars, out);
   }
   // the statistics collapsed along index directions
   if (n_cstat > 0) {
@@ -3200,6 +3380,7 @@ int agx_field_upload(agx_ctx* c, int id, int field, const double* in) {
   const int g = gh ? b.d.ng : 0;
   if (upload_aos(c, b, in, p, nc, b.d.ni + 2 * g, b.d.nj + 2 * g, b.d.nk + 2 * g, g)) return 1;
   if (field == AGX_FIELD_UPDATE) x_uploaded(b);
+  if (field == AGX_FIELD_RESIDUAL) c->have_residual = true;
   if (field == AGX_FIELD_UPDATE && b.d.d2.base) return d2_x_copy(c, b, 1);
   return 0;
 }
@@ -3603,6 +3784,7 @@ int agx_phase_residual(agx_ctx* c, int mm, double cfl) {
   }
   HIPCHK(hipGetLastError());
   c->fused_pending = fuse;
+  c->have_residual = true;
   if (c->cfg.is_viscous) {
     {
       Timer t(c, G_BC);

@@ -50,6 +50,28 @@ def pool_bins(parts):
     return vol, means, covs
 
 
+def pool_fluxes(parts, tags=None, bc_types=None):
+    """Add the boundary fluxes of blocks, or of ranks: parts is a list of
+    (Solver.flux_surfaces(gb), Solver.surface_fluxes(gb)), one per block, of any ranks.
+    Returns {name: float}, every surface that passes the filters added in list order (block,
+    then surface) in float64.  tags / bc_types: only surfaces whose BC tag / BC type is listed.
+    Without filters the two sides of every connection both of whose blocks are in `parts`
+    cancel (the inviscid values to rounding, the viscous ones up to the faces on the rim of
+    the patch, which each block evaluates with its own edge ghost cells), and what is left is
+    the flux through the outer boundary.  Right after a residual the pooled net flux of an
+    equation is the sum of the blocks' residual sums (Solver.block_budget) in any case."""
+    total = {}
+    for surfs, vals in parts:
+        for q, s in enumerate(surfs):
+            if tags is not None and s["tag"] not in tags:
+                continue
+            if bc_types is not None and s["bc_type"] not in bc_types:
+                continue
+            for n, v in vals.items():
+                total[n] = total.get(n, 0.0) + float(v[q])
+    return total
+
+
 class DistExchange:
     """An agx_exchange (include/aither_gfx950.h) on torch.distributed
     point-to-point with HOST buffers: what an MPI adapter would pass
@@ -382,6 +404,92 @@ class Solver:
                     for n in names:
                         total[n] += float(got[n][q])
         return total
+
+    # -- boundary fluxes and the block balance ----------------------------------------------
+    def _remote_surface(self, gb, s):
+        """Is surface s of block gb (part of) a connection whose partner is on another rank?"""
+        if s.bc_type not in ("interblock", "periodic"):
+            return False
+        side = s.surface_type()
+        d3 = (side - 1) // 2
+        d1, d2 = (d3 + 1) % 3, (d3 + 2) % 3
+        lo, hi = (s.imin, s.jmin, s.kmin), (s.imax, s.jmax, s.kmax)
+        for conn in self.case.connections:
+            if conn.rank[0] == conn.rank[1]:
+                continue
+            for m in range(2):
+                if conn.rank[m] == self.rank and conn.block[m] == gb and \
+                        conn.boundary[m] == side and conn.d1s[m] < hi[d1] and \
+                        conn.d1e[m] > lo[d1] and conn.d2s[m] < hi[d2] and conn.d2e[m] > lo[d2]:
+                    return True
+        return False
+
+    def flux_surfaces(self, gb):
+        """The flux surfaces of block gb in the order of the flux payload: every surface the
+        library got, in that order, of every BC type -- local interblock / periodic connections
+        included, connections to other ranks left out (their ghost cells are current only
+        between exchanges).  Per surface its side (surface type 1..6), BC type, tag, index
+        range and the shape (nk, nj, ni) of its faces."""
+        out = []
+        for s in self.case.blocks[gb].surfaces:
+            if self._remote_surface(gb, s):
+                continue
+            side = s.surface_type()
+            d = (side - 1) // 2
+            n = [s.imax - s.imin, s.jmax - s.jmin, s.kmax - s.kmin]
+            n[d] = 1
+            out.append(dict(side=side, tag=s.tag, bc_type=s.bc_type,
+                            range=(s.imin, s.imax, s.jmin, s.jmax, s.kmin, s.kmax),
+                            shape=(n[2], n[1], n[0])))
+        return out
+
+    def flux_names(self, out=None):
+        """The names of abi.FLUX_OUT (or of `out`, e.g. abi.BUDGET_OUT) this library gives: the
+        5-equation libraries refuse the tke and sdr ids."""
+        out = abi.FLUX_OUT if out is None else out
+        drop = () if self.cfg.n_eq == 7 else ("_tke", "_sdr")
+        return [n for n in out if not n.endswith(drop)]
+
+    def surface_fluxes(self, gb, names=None):
+        """What crosses each flux surface of block gb (abi.FLUX_OUT), summed by the library
+        from the face fluxes the residual pass takes: {name: ndarray[nsurf]}, SI, positive
+        out of the block; inviscid_e + viscous_e is the net outward flux of equation e."""
+        names = list(self.flux_names() if names is None else names)
+        nsurf = len(self.flux_surfaces(gb))
+        ids = (C.c_int32 * len(names))(*[abi.FLUX_OUT[n] for n in names])
+        out = np.empty((len(names), max(nsurf, 1)))
+        self.api.check(self.api.output_pack(self.ctx, self.block_ids[gb], len(names), ids,
+                                            out.ctypes.data_as(abi.c_dp)), "output_pack")
+        return {n: out[q, :nsurf].copy() for q, n in enumerate(names)}
+
+    def block_budget(self, gb, names=None):
+        """The balance of block gb (abi.BUDGET_OUT) over its physical cells: {name: float}, SI
+        -- the volume, the conserved totals of the state now and the sums of the residual as
+        the last residual pass left it."""
+        names = list(self.flux_names(abi.BUDGET_OUT) if names is None else names)
+        ids = (C.c_int32 * len(names))(*[abi.BUDGET_OUT[n] for n in names])
+        out = np.empty(len(names))
+        self.api.check(self.api.output_pack(self.ctx, self.block_ids[gb], len(names), ids,
+                                            out.ctypes.data_as(abi.c_dp)), "output_pack")
+        return {n: float(out[q]) for q, n in enumerate(names)}
+
+    def flux_balance(self, gb):
+        """{equation: (residual sum, flux sum)} of block gb: the sum of the residual over the
+        physical cells against the net outward flux through all flux surfaces, added in
+        surface order.  Equal to rounding right after a residual wherever the equation has no
+        source term and the rank holds all of the block's surfaces; after an update the
+        residual belongs to the state before it."""
+        eqs = abi.EQUATIONS[:self.cfg.n_eq]
+        flux = self.surface_fluxes(gb, [f"{kind}_{e}" for e in eqs
+                                        for kind in ("inviscid", "viscous")])
+        resid = self.block_budget(gb, [f"residual_{e}" for e in eqs])
+        out = {}
+        for e in eqs:
+            total = 0.0
+            for a, b in zip(flux[f"inviscid_{e}"], flux[f"viscous_{e}"]):
+                total += float(a) + float(b)
+            out[e] = (resid[f"residual_{e}"], total)
+        return out
 
     # -- time statistics, kept by the library on the device -----------------------------
     def _stat_dims(self, gb):
@@ -772,6 +880,15 @@ class MultigridSolver:
 
     def total_loads(self, tags=None, about=None, level=0):
         return self.levels[level].total_loads(tags, about)
+
+    def flux_surfaces(self, gb, level=0):
+        return self.levels[level].flux_surfaces(gb)
+
+    def surface_fluxes(self, gb, names=None, level=0):
+        return self.levels[level].surface_fluxes(gb, names)
+
+    def block_budget(self, gb, names=None, level=0):
+        return self.levels[level].block_budget(gb, names)
 
     # time statistics: those of the finest level
     def stats_sample(self, weight=1.0):

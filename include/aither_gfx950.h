@@ -273,6 +273,90 @@ enum { AGX_LOAD_BASE = 256, AGX_LOAD_AREA = AGX_LOAD_BASE,
        AGX_LOAD_VISCOUS_MOMENT_X, AGX_LOAD_VISCOUS_MOMENT_Y, AGX_LOAD_VISCOUS_MOMENT_Z,
        AGX_LOAD_END };
 
+/* boundary fluxes: one more range of agx_output_pack, with no counterpart in the reference.
+ * What the scheme lets through the boundary of a block -- mass flow, momentum flux, energy
+ * flux [, the fluxes of rho k and rho omega] per inlet, outlet, far field, wall and block
+ * connection.  One value per FLUX SURFACE of the block, dimensional (SI): out[v * nsurf + s].
+ * The flux surfaces are every surface agx_block_set_bcs got, in that order, of every BC type,
+ * local interblock / periodic connections included; connections whose partner lies on another
+ * rank are left out of the list (their ghost cells are current only between the caller's
+ * exchanges).  Sums over the faces of the surface, |A| the face's area, F the flux per unit
+ * area in the direction of increasing index, e the equation (mass, mom_x, mom_y, mom_z,
+ * energy, tke, sdr):
+ *   AGX_FLUX_AREA            sum |A|
+ *   AGX_FLUX_INVISCID + e    sum sigma F_inv,e |A|
+ *   AGX_FLUX_VISCOUS + e     - sum sigma F_visc,e |A|
+ * Orientation: sigma = +1 on upper sides (surface types 2, 4, 6), -1 on lower sides (1, 3,
+ * 5): a positive value LEAVES THE BLOCK.  The viscous flux enters the residual with the
+ * opposite sign of the inviscid one (procBlock.cpp:447-463 against :1392-1430), hence the
+ * minus: inviscid + viscous is the net outward flux of equation e, and summed over all
+ * surfaces of a block it is the sum of the block's residual (AGX_BUDGET_RESIDUAL + e)
+ * wherever the equation has no source term.  The inviscid values of the two sides of a local
+ * connection cancel; the viscous values cancel except for the faces on the rim of the patch,
+ * which each block evaluates with its own edge ghost cells, as its residual does.
+ * Face values are exactly what the residual pass takes at the face: the configured
+ * reconstruction (constant, MUSCL with the configured limiter, WENO, WENO-Z) with the ghost
+ * cells as its stencil, the configured inviscid flux (Roe, AUSMPW+), the viscous flux of the
+ * viscous pass (central / centralFourth face values, the face's WALE eddy viscosity in
+ * largeEddySimulation contexts, the k and omega diffusion in the rans libraries, the stored
+ * wall data at wall-law faces).  An inviscid context returns 0 for the viscous ids.
+ * Factors: the nondimensional sum times the factor of the conserved variable (what
+ * agx_restart_pack gives consVarsNm1) times a_ref l_ref^2 -- the area times l_ref^2:
+ *   mass     rho_ref a_ref l_ref^2                    [kg/s]
+ *   mom_x/y/z  rho_ref a_ref^2 l_ref^2                [N]
+ *   energy   rho_ref a_ref^3 l_ref^2                  [W]
+ *   tke      rho_ref a_ref^3 l_ref^2
+ *   sdr      rho_ref^2 a_ref^3 l_ref^2 / mu_ref
+ * (for e < 6 the factor of AGX_OUT_RESID + e; resid_sdr of the cell range carries the
+ * reference file's a_ref^4.  The viscous energy value of a viscousWall at rest is the
+ * nondimensional sum of AGX_LOAD_HEAT, which carries the wall file's mu_ref t_ref / l_ref
+ * instead; the viscous momentum values are AGX_LOAD_VISCOUS_FORCE_X/Y/Z as they are.)
+ * The 5-equation libraries refuse e = 5, 6 by name.
+ * Timing and legality.  A ghost-refilling read in viscous and inviscid contexts alike (the
+ * inviscid flux of a boundary face reads the ghost cells too): the ghost cells, edges
+ * included, are those the next residual would see; refused from the caller's
+ * agx_phase_bc_faces to the agx_phase_residual that follows it ("reads between phases" at
+ * agx_field_download), legal elsewhere, and the run stays bit-identical.  Wall-law faces:
+ * refused before the first residual, like the wall variables.  Not a collective.
+ * Determinism: no floating-point atomics, a shape fixed by the surfaces alone (chunks of 256
+ * faces that never span two surfaces, added in ascending order), all 15 sums formed on every
+ * call: two calls, and any subset, order or repetition of ids, return the same bits.
+ * Refused by name: ids of another range in the same call; more than 15 ids; a block all of
+ * whose surfaces are connections to other ranks; a call before agx_setup_finalize. */
+enum { AGX_FLUX_BASE = 384, AGX_FLUX_AREA = AGX_FLUX_BASE,
+       AGX_FLUX_INVISCID = AGX_FLUX_BASE + 1,      /* + e, e = 0 ... 6 */
+       AGX_FLUX_VISCOUS = AGX_FLUX_BASE + 8,       /* + e */
+       AGX_FLUX_END = AGX_FLUX_BASE + 15 };
+
+/* block balance: one value per id, out[v], dimensional, over the PHYSICAL cells of the block:
+ *   AGX_BUDGET_VOLUME          sum V                                     times l_ref^3
+ *   AGX_BUDGET_TOTAL + e       sum U_e V, the conserved variables of the state now (mass,
+ *                              momentum, total energy, rho k, rho omega): the factor of the
+ *                              conserved variable times l_ref^3
+ *   AGX_BUDGET_RESIDUAL + e    sum residual_e, the residual planes as the last residual pass
+ *                              left them, with the factor of AGX_FLUX_INVISCID + e
+ * so that BUDGET_RESIDUAL_e = sum over the flux surfaces of (FLUX_INVISCID_e + FLUX_VISCOUS_e)
+ * holds as delivered, to rounding, for e < 5 on a rank that holds all of the block's
+ * surfaces.  In the rans libraries the k and omega residuals contain the source terms: no
+ * balance is claimed for e = 5, 6.  On a coarse multigrid level the ids return what the
+ * level's planes hold (the forcing term is not in the fluxes): no balance is claimed.
+ * Timing.  Physical cells only: legal at every position, and the run stays bit-identical.
+ * Every path keeps the residual in its planes (the fused explicit stage kernel stores it
+ * beside the new state, the diagonal-ordered LU-SGS path reads it from them), so the sums are
+ * never stale; but after agx_iterate, or an update phase, the residual belongs to the state
+ * BEFORE the update while the fluxes and the totals belong to the state now.  The balance is
+ * exact right after agx_phase_residual.
+ * Determinism: the rows (j, k) of the block in chunks of 64, k outer; a row by 64 strided
+ * lanes added by shuffles; the chunks added in ascending order.  A shape fixed by the extents
+ * alone, no atomics, all 15 sums formed on every call.
+ * Refused by name: the residual sums before the first residual (agx_phase_residual,
+ * agx_iterate, or an upload of AGX_FIELD_RESIDUAL); e = 5, 6 in the 5-equation libraries;
+ * ids of another range in the same call; more than 15 ids. */
+enum { AGX_BUDGET_BASE = 448, AGX_BUDGET_VOLUME = AGX_BUDGET_BASE,
+       AGX_BUDGET_TOTAL = AGX_BUDGET_BASE + 1,     /* + e, e = 0 ... 6 */
+       AGX_BUDGET_RESIDUAL = AGX_BUDGET_BASE + 8,  /* + e */
+       AGX_BUDGET_END = AGX_BUDGET_BASE + 15 };
+
 /* time statistics: a fifth and a sixth range of agx_output_pack, with no counterpart in the
  * reference.  An unsteady run (largeEddySimulation, SST-DES, bdf2 dual time stepping) is read
  * from its time averages; the library keeps them on the device, so that a sample costs one
@@ -548,7 +632,9 @@ int agx_state_upload(agx_ctx *ctx, int block_id, const double *state_aos);
  * then the viscous-wall fill, which stays): the gradient fields (AGX_FIELD_VEL_GRAD ..
  * AGX_FIELD_PRESS_GRAD), and of agx_output_pack the gradient variables, every node variable
  * and every wall variable, and on a viscous context every load variable (AGX_LOAD_*; an
- * inviscid context reads physical cells only there).  From the caller's agx_phase_bc_faces up to the
+ * inviscid context reads physical cells only there), and in every context every flux variable
+ * (AGX_FLUX_*; the budget variables AGX_BUDGET_* read physical cells only and are legal
+ * everywhere).  From the caller's agx_phase_bc_faces up to the
  * agx_phase_residual that follows it the ghost cells are being filled for that residual, and
  * these calls are REFUSED with a message; they are legal from agx_phase_residual to the next
  * agx_phase_bc_faces, and between agx_iterate calls (agx_iterate's own fill does not count). */
@@ -612,6 +698,11 @@ int agx_phase_implicit_update(agx_ctx *ctx, int mm, double *l2, agx_linf *linf);
  * value per load surface of the block instead -- its viscousWall and slipWall surfaces in the
  * order agx_block_set_bcs got them -- variable by variable in the caller's order:
  * out[v * nsurf + surface], see the enum.
+ * Boundary fluxes and the block balance (no counterpart in output.cpp): with flux variables
+ * (AGX_FLUX_*) one value per flux surface of the block -- every surface agx_block_set_bcs
+ * got, in that order, but the connections to other ranks -- out[v * nsurf + surface]; with
+ * budget variables (AGX_BUDGET_*) one value per id, out[v]; see the enums for what they
+ * refuse.
  * Time statistics (no counterpart in output.cpp): with statistics ids (AGX_STAT_BASE + n) one
  * value per physical cell in the layout of the cell variables, with wall statistics ids
  * (AGX_WSTAT_BASE + n) one value per wall face in the layout of the wall variables; with

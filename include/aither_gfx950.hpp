@@ -187,6 +187,24 @@ class hotPath {
     Check(AGX_SYM(output_pack)(ctx_, block, static_cast<int>(vars.size()), vars.data(), out),
           "hotPath::SurfaceLoads");
   }
+  // No counterpart in output.cpp: what crosses the block's flux surfaces -- every surface
+  // SetBCs got, in that order, of every BC type, but the connections to other ranks -- summed
+  // on the device from the face fluxes the residual pass takes: the listed variables
+  // (AGX_FLUX_AREA, AGX_FLUX_INVISCID + e, AGX_FLUX_VISCOUS + e), variable by variable, one
+  // value per surface, SI, positive out of the block; `out` holds vars.size() * (flux surfaces)
+  // values.  A ghost-refilling read: refused between agx_phase_bc_faces and agx_phase_residual
+  void SurfaceFluxes(int block, const std::vector<int32_t> &vars, double *out) const {
+    Check(AGX_SYM(output_pack)(ctx_, block, static_cast<int>(vars.size()), vars.data(), out),
+          "hotPath::SurfaceFluxes");
+  }
+  // ... and the block's balance over its physical cells (AGX_BUDGET_VOLUME, AGX_BUDGET_TOTAL +
+  // e, AGX_BUDGET_RESIDUAL + e), one value per id; legal at every position.  Right after a
+  // residual, BUDGET_RESIDUAL_e is the sum over the surfaces of FLUX_INVISCID_e +
+  // FLUX_VISCOUS_e (e < 5); after an update the residual belongs to the state before it
+  void BlockBudget(int block, const std::vector<int32_t> &vars, double *out) const {
+    Check(AGX_SYM(output_pack)(ctx_, block, static_cast<int>(vars.size()), vars.data(), out),
+          "hotPath::BlockBudget");
+  }
   // WriteNodeFun (output.cpp:452-469): the block's payload of the nodal function file -- the
   // listed variables by their cell ids (AGX_OUT_*; AGX_NODE_BASE is added here), converted to
   // the (nk+1)(nj+1)(ni+1) nodes on the device (procBlock::CellToNode), variable by variable,
