@@ -6,6 +6,8 @@ oracle used by the tests (prefix "ora_", same signatures).
 """
 import ctypes as C
 
+import numpy as np
+
 RECON = {"constant": 0, "muscl": 1, "weno": 2, "wenoZ": 3}
 LIMITER = {"none": 0, "vanAlbada": 1, "minmod": 2}
 FLUX = {"roe": 0, "ausm": 1}
@@ -33,10 +35,17 @@ FIELD = {"state": 0, "residual": 1, "dt": 2, "spec_radius": 3, "cons_n": 4,
 # names: `name in FIELD`, FIELD.get(name), len and iteration do NOT (tests/probe.py holds the
 # iterated set to the block-shaped fields); ask STAT_FIELD for those.
 STAT_FIELD = {"stat_sample": 23, "stat_accum": 24}
+# time series at chosen cells and wall faces (AGX_FIELD_SERIES_*): the plan, one sample (upload
+# only), the recorded rows, the nearest-cell search.  Payloads of their own layout like the two
+# above, and resolved the same way: FIELD["series_plan"] works, iteration does not see them.
+SERIES_FIELD = {"series_plan": 25, "series_sample": 26, "series_rows": 27, "series_locate": 28}
+SERIES_KIND = {"cells": 0, "wall": 1}
 
 
 class _Fields(dict):
     def __missing__(self, name):
+        if name in SERIES_FIELD:
+            return SERIES_FIELD[name]
         return STAT_FIELD[name]
 
 
@@ -131,6 +140,56 @@ def cstat_mask(over):
 def cstat_id(mask, name):
     """The id of statistics variable `name` (CSTAT_NAMES) collapsed over `mask`."""
     return CSTAT_BASE + 32 * int(mask) + CSTAT_NAMES.index(name)
+
+
+def series_plan(names, points, capacity, kind="cells"):
+    """The payload of AGX_FIELD_SERIES_PLAN: {kind, P, V, capacity, V ids, P points} as
+    float64.  kind "cells": names of OUT, points[P, 3] = (i, j, k) of physical cells; kind
+    "wall": names of WALL_OUT, points[P] = indices into the block's wall payload.  No points:
+    the payload that discards the block's plan."""
+    table = OUT if SERIES_KIND[kind] == 0 else WALL_OUT
+    per = 3 if SERIES_KIND[kind] == 0 else 1
+    pts = np.asarray(points, dtype=np.float64).reshape(-1, per)
+    ids = [float(table[n]) for n in names]
+    head = [float(SERIES_KIND[kind]), float(len(pts)), float(len(ids)), float(capacity)]
+    return np.concatenate([np.array(head + ids, dtype=np.float64), pts.ravel()])
+
+
+def series_plan_parse(payload):
+    """The inverse of series_plan: (names, points, capacity, kind) of a plan payload, points
+    as an integer array [P, 3] (cells) or [P] (wall)."""
+    a = np.asarray(payload, dtype=np.float64)
+    kind = {v: k for k, v in SERIES_KIND.items()}[int(a[0])]
+    npts, nvar, capacity = int(a[1]), int(a[2]), int(a[3])
+    table = {v: k for k, v in (OUT if kind == "cells" else WALL_OUT).items()}
+    names = [table[int(v)] for v in a[4:4 + nvar]]
+    pts = a[4 + nvar:].astype(np.int64)
+    pts = pts.reshape(npts, 3) if kind == "cells" else pts.reshape(npts)
+    return names, pts, capacity, kind
+
+
+def series_rows_size(npts, nvar, capacity):
+    """Doubles of the buffer a download of AGX_FIELD_SERIES_ROWS fills at most."""
+    return 4 + capacity * (1 + nvar * npts)
+
+
+def series_rows_split(payload):
+    """A payload of AGX_FIELD_SERIES_ROWS, {P, V, rows, capacity} and rows x {t, V P values},
+    into (t[rows], values[rows, V, P]), oldest row first."""
+    a = np.asarray(payload, dtype=np.float64)
+    npts, nvar, rows = int(a[0]), int(a[1]), int(a[2])
+    body = a[4:4 + rows * (1 + nvar * npts)].reshape(rows, 1 + nvar * npts)
+    return body[:, 0].copy(), body[:, 1:].reshape(rows, nvar, npts).copy()
+
+
+def series_rows_join(t, values, capacity):
+    """The inverse of series_rows_split: the payload of t[rows] and values[rows, V, P]."""
+    v = np.asarray(values, dtype=np.float64)
+    rows, nvar, npts = v.shape
+    body = np.concatenate([np.asarray(t, dtype=np.float64).reshape(rows, 1),
+                           v.reshape(rows, nvar * npts)], axis=1)
+    return np.concatenate([np.array([npts, nvar, rows, capacity], dtype=np.float64),
+                           body.ravel()])
 
 
 # cell planes of the accumulators: 9 means + extras (eddy viscosity; k, omega) + 9 second

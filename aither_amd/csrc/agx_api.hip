@@ -9,6 +9,8 @@
 #include "agx_geometry.hpp"
 #include "agx_start.hpp"
 #include "agx_stats.hpp"
+#include "agx_series.hpp"
+#include "agx_series_ring.hpp"
 #include "agx_flux.hpp"
 #include "agx_mem.hpp"
 #include "agx_switches.hpp"
@@ -166,6 +168,24 @@ struct Block {
   // the chunk records of a collapse (AGX_CSTAT_BASE): allocated by the first one, grown by a
   // larger one, freed with the statistics
   DevBuf<double> stat_part;
+  // time series (agx_series.hpp): the plan as uploaded (empty: no plan), its ids and points,
+  // the ring of rows on the device and the rows' time stamps on the host; wall_epoch counts
+  // the agx_block_set_bcs calls (a wall plan is of the wall payload it was uploaded for)
+  struct Series {
+    std::vector<double> payload;
+    int kind = 0, V = 0;
+    long P = 0, wall_epoch = 0;
+    bool grads = false;
+    int32_t var[AGX_OUT_COUNT] = {};
+    DevBuf<long> pts;
+    DevBuf<double> rows;
+    SeriesRing ring;
+    std::vector<double> t;
+  } series;
+  long wall_epoch = 0;
+  // the result of the last AGX_FIELD_SERIES_LOCATE upload, 4 doubles per point
+  DevBuf<double> locate_out;
+  long locate_n = 0;
 };
 
 struct ConnSide {          // what side s receives / sends
@@ -322,6 +342,8 @@ static int stats_field_upload(agx_ctx* c, int id, int field, const double* in);
 static int stats_field_download(agx_ctx* c, int id, int field, double* out);
 static int stats_pack(agx_ctx* c, int id, bool wall, int nvar, const int32_t* vars, double* out);
 static int stats_collapse(agx_ctx* c, int id, int nvar, const int32_t* vars, double* out);
+static int series_field_upload(agx_ctx* c, int id, int field, const double* in);
+static int series_field_download(agx_ctx* c, int id, int field, double* out);
 #if AGX_FAST
 static int d2_prepare(agx_ctx* c, Block& blk, int write_x, int again, int norms);
 #endif
@@ -2079,6 +2101,7 @@ int agx_block_set_bcs(agx_ctx* c, int id, int n, const agx_bc_surface* s) {
   b.wall_tab_dev.reset();
   b.wall_tab.clear();
   b.wall_faces = 0;
+  ++b.wall_epoch;
   for (int q = 0; q < n; ++q) {
     if (s[q].bc_type != AGX_BC_VISCOUSWALL) continue;
     WallSurfDev w;
@@ -2497,6 +2520,8 @@ int agx_field_download(agx_ctx* c, int id, int field, double* out) {
   if (id < 0 || id >= (int)c->blocks.size()) return fail("bad block id %d", id);
   if (field == AGX_FIELD_STAT_SAMPLE || field == AGX_FIELD_STAT_ACCUM)
     return stats_field_download(c, id, field, out);
+  if (field >= AGX_FIELD_SERIES_PLAN && field <= AGX_FIELD_SERIES_LOCATE)
+    return series_field_download(c, id, field, out);
   Block& b = c->blocks[id];
   // (the D2 arrays hold x with the writer's tag in its two lowest mantissa bits: while the
   // planes are current -- an upload or a multigrid transfer wrote them last -- they are the
@@ -3167,6 +3192,233 @@ static int stats_collapse(agx_ctx* c, int id, int nvar, const int32_t* vars, dou
   return copy_out(c, out, tmp, (size_t)nvar * cs.nbin);
 }
 
+// ---- time series (agx_series.hpp; include/aither_gfx950.h at AGX_FIELD_SERIES_PLAN) ----------
+namespace {
+// entry `at` of a payload as an integer in [lo, hi]; refuses by name, saying which entry
+int series_entry(const char* field, const double* in, long at, const char* what, double lo,
+                 double hi, long* out) {
+  const double x = in[at];
+  if (!std::isfinite(x) || x != std::floor(x) || x < lo || x > hi)
+    return fail("agx_field_upload: %s: entry %ld (%s) is %g: an integer from %.0f to %.0f is "
+                "expected", field, at, what, x, lo, hi);
+  *out = (long)x;
+  return 0;
+}
+constexpr double SERIES_MAX_COUNT = 16777216.0;     // points of a plan or a locate, rows of a ring
+// ids of a plan that this library does not keep (the 5-equation libraries: the rans variables)
+int series_id_refused(const agx_ctx* c, const Block& b, int id, int kind, int var) {
+  if (kind == 0) {
+    const bool rans = var == AGX_OUT_TKE || var == AGX_OUT_SDR || var == AGX_OUT_F1 ||
+                      var == AGX_OUT_F2 || (var >= AGX_OUT_TKEGRAD && var < AGX_OUT_RESID) ||
+                      var >= AGX_OUT_RESID + 5;
+    if (AGX_NEQ == 5 && rans)
+      return fail("agx_field_upload: AGX_FIELD_SERIES_PLAN: variable %d (tke, sdr, f1, f2, "
+                  "their gradients and residuals) is not kept by the 5-equation libraries", var);
+    if (var == AGX_OUT_VISCOSITY && !c->sp.viscous)
+      return fail("viscosity_ is only kept for viscous runs (procBlock.cpp:6171)");
+    return 0;
+  }
+  if (AGX_NEQ == 5 && (var == AGX_WALL_TKE || var == AGX_WALL_SDR))
+    return fail("agx_field_upload: AGX_FIELD_SERIES_PLAN: wall variable %d (tke, sdr) is not "
+                "kept by the 5-equation libraries", var);
+  if (!c->cfg.is_viscous)
+    return fail("agx_field_upload: AGX_FIELD_SERIES_PLAN: wall variables need a viscous context "
+                "(an inviscid run keeps no wallData_)");
+  if (b.wall_tab.empty())
+    return fail("agx_field_upload: AGX_FIELD_SERIES_PLAN: block %d has no viscousWall surface",
+                id);
+  return 0;
+}
+int series_no_plan(const char* call, const char* field, int id) {
+  return fail("%s: %s: block %d has no plan (upload AGX_FIELD_SERIES_PLAN first)", call, field,
+              id);
+}
+int series_plan_upload(agx_ctx* c, int id, const double* in) {
+  static const char F[] = "AGX_FIELD_SERIES_PLAN";
+  Block& b = c->blocks[id];
+  long kind, P, V, cap;
+  if (series_entry(F, in, 0, "kind: 0 cells, 1 wall faces", 0, 1, &kind)) return 1;
+  if (series_entry(F, in, 1, "P, the points", 0, SERIES_MAX_COUNT, &P)) return 1;
+  if (P == 0) {
+    HIPCHK(hipStreamSynchronize(c->stream));     // (before the rows are freed)
+    b.series = Block::Series();
+    return 0;
+  }
+  if (series_entry(F, in, 2, "V, the variables", 1, AGX_OUT_COUNT, &V)) return 1;
+  if (series_entry(F, in, 3, "capacity, the rows of the record", 1, SERIES_MAX_COUNT, &cap))
+    return 1;
+  Block::Series s;
+  s.kind = (int)kind; s.V = (int)V; s.P = P; s.wall_epoch = b.wall_epoch;
+  for (long v = 0; v < V; ++v) {
+    long var;
+    if (series_entry(F, in, 4 + v, "a variable id", 0, 2147483647.0, &var)) return 1;
+    if (kind == 0 ? var >= AGX_OUT_COUNT : var < AGX_WALL_YPLUS || var >= AGX_WALL_END)
+      return fail("agx_field_upload: %s: entry %ld: unknown output variable %ld (a plan of "
+                  "kind %ld holds %s)", F, 4 + v, var, kind,
+                  kind == 0 ? "cell ids < AGX_OUT_COUNT" : "wall ids AGX_WALL_*");
+    if (series_id_refused(c, b, id, (int)kind, (int)var)) return 1;
+    s.var[v] = (int32_t)var;
+    s.grads = s.grads || (kind == 0 && var >= AGX_OUT_VELGRAD && var < AGX_OUT_RESID);
+  }
+  const int per = kind == 0 ? 3 : 1;
+  std::vector<long> pts((size_t)P);
+  const int nn[3] = {b.d.ni, b.d.nj, b.d.nk};
+  for (long p = 0; p < P; ++p) {
+    if (kind == 0) {
+      long ijk[3];
+      for (int d = 0; d < 3; ++d)
+        if (series_entry(F, in, 4 + V + 3 * p + d, d == 0 ? "i of a cell" : d == 1 ? "j of a cell"
+                         : "k of a cell", 0, nn[d] - 1, &ijk[d])) return 1;
+      pts[p] = (ijk[2] * b.d.nj + ijk[1]) * b.d.ni + ijk[0];
+    } else if (series_entry(F, in, 4 + V + p, "a face of the wall payload", 0,
+                            (double)(b.wall_faces - 1), &pts[p])) {
+      return 1;
+    }
+  }
+  const size_t nrow = (size_t)V * P;
+  if (s.pts.upload(pts) != hipSuccess || s.rows.alloc((size_t)cap * nrow) != hipSuccess)
+    return fail("agx_field_upload: %s: no device memory for %ld rows of %zu doubles", F, cap,
+                nrow);
+  s.payload.assign(in, in + 4 + V + per * P);
+  s.ring.reset(cap);
+  s.t.assign((size_t)cap, 0.0);
+  HIPCHK(hipStreamSynchronize(c->stream));       // (before the old rows are freed)
+  b.series = std::move(s);
+  return 0;
+}
+int series_sample(agx_ctx* c, int id, double t) {
+  static const char F[] = "AGX_FIELD_SERIES_SAMPLE";
+  Block& b = c->blocks[id];
+  Block::Series& s = b.series;
+  if (s.payload.empty()) return series_no_plan("agx_field_upload", F, id);
+  if (!std::isfinite(t)) return fail("agx_field_upload: %s: the time %g is not finite", F, t);
+  if (s.ring.full())
+    return fail("agx_field_upload: %s: the record of block %d is full (%ld rows, its capacity): "
+                "collect the rows first (download AGX_FIELD_SERIES_ROWS, then upload the number "
+                "of rows to drop); nothing is overwritten", F, id, s.ring.count);
+  const bool wall = s.kind == 1;
+  if (wall) {
+    if (s.wall_epoch != b.wall_epoch)
+      return fail("agx_field_upload: %s: the wall surfaces of block %d changed since its plan was "
+                  "uploaded; upload the plan again (AGX_FIELD_SERIES_PLAN)", F, id);
+    if (b.d.wallv && !c->have_wall_data)
+      return fail("agx_field_upload: %s: the wall-law surfaces hold no wall data before the first "
+                  "residual", F);
+  }
+  // gradients and wall faces are evaluated with the ghost cells the next residual would see
+  if ((wall || s.grads) && ghosts_for_output(c, "agx_field_upload")) return 1;
+  double* row = s.rows.get() + (size_t)s.ring.next() * s.V * s.P;
+  const dim3 grid((unsigned)((s.P * s.V + 255) / 256));
+  const OutSpec sp = out_spec(c, b, s.V, s.var);
+  if (wall) {
+    const int fourth = (c->cfg.viscous_recon == AGX_VISC_RECON_CENTRAL_4TH ? 1 : 0) |
+                       (c->sp.les ? 2 : 0);
+    hipLaunchKernelGGL(k_series_wall, grid, dim3(256), 0, c->stream, b.d, c->gas, sp,
+                       b.wall_tab_dev.get(), (int)b.wall_tab.size(), fourth, s.pts.get(), s.P,
+                       row);
+  } else {
+    hipLaunchKernelGGL(k_series_cells, grid, dim3(256), 0, c->stream, b.d, c->gas, sp,
+                       s.pts.get(), s.P, row);
+  }
+  HIPCHK(hipGetLastError());
+  s.t[(size_t)s.ring.next()] = t;
+  s.ring.push();
+  return 0;
+}
+int series_drop(agx_ctx* c, int id, double n) {
+  static const char F[] = "AGX_FIELD_SERIES_ROWS";
+  Block::Series& s = c->blocks[id].series;
+  if (s.payload.empty()) return series_no_plan("agx_field_upload", F, id);
+  if (!std::isfinite(n) || n != std::floor(n) || n < 0.0 || n > (double)s.ring.count)
+    return fail("agx_field_upload: %s: cannot drop %g rows: the record of block %d holds %ld "
+                "(an integer from 0 to that)", F, n, id, s.ring.count);
+  s.ring.drop((long)n);
+  return 0;
+}
+int series_locate(agx_ctx* c, int id, const double* in) {
+  static const char F[] = "AGX_FIELD_SERIES_LOCATE";
+  Block& b = c->blocks[id];
+  long P;
+  if (series_entry(F, in, 0, "P, the points", 1, SERIES_MAX_COUNT, &P)) return 1;
+  for (long n = 0; n < 3 * P; ++n)
+    if (!(std::fabs(in[1 + n]) <= 1e150))
+      return fail("agx_field_upload: %s: entry %ld (coordinate %ld of point %ld) is %g: a finite "
+                  "value of at most 1e150 in magnitude is expected", F, 1 + n, n % 3, n / 3,
+                  in[1 + n]);
+  double* dp = nullptr;
+  if (stage_buffer(c, (size_t)3 * P, &dp)) return 1;
+  if ((size_t)4 * P > b.locate_out.size()) {
+    HIPCHK(hipStreamSynchronize(c->stream));     // (before the old one is freed)
+    b.locate_n = 0;
+    if (b.locate_out.alloc((size_t)4 * P) != hipSuccess)
+      return fail("agx_field_upload: %s: no device memory for the result of %ld points", F, P);
+  }
+  HIPCHK(hipMemcpyAsync(dp, in + 1, sizeof(double) * 3 * P, hipMemcpyHostToDevice, c->stream));
+  constexpr int PPW = SERIES_LOCATE_PPW;
+  hipLaunchKernelGGL(k_series_locate<PPW>, dim3((unsigned)((P + PPW - 1) / PPW)), dim3(256), 0,
+                     c->stream, b.d, P, dp, b.locate_out.get());
+  HIPCHK(hipGetLastError());
+  HIPCHK(hipStreamSynchronize(c->stream));       // (the caller's points have been read)
+  b.locate_n = P;
+  return 0;
+}
+}  // namespace
+
+static int series_field_upload(agx_ctx* c, int id, int field, const double* in) {
+  if (flush_consn(c)) return 1;
+  if (id < 0 || id >= (int)c->blocks.size()) return fail("bad block id %d", id);
+  if (!in) return fail("agx_field_upload: null pointer");
+  if (!c->finalized) return fail("agx_setup_finalize has not been called");
+  switch (field) {
+    case AGX_FIELD_SERIES_PLAN: return series_plan_upload(c, id, in);
+    case AGX_FIELD_SERIES_SAMPLE: return series_sample(c, id, in[0]);
+    case AGX_FIELD_SERIES_ROWS: return series_drop(c, id, in[0]);
+  }
+  return series_locate(c, id, in);
+}
+
+static int series_field_download(agx_ctx* c, int id, int field, double* out) {
+  Block& b = c->blocks[id];
+  const Block::Series& s = b.series;
+  if (field == AGX_FIELD_SERIES_SAMPLE)
+    return fail("agx_field_download: AGX_FIELD_SERIES_SAMPLE is upload only (a sample's time); "
+                "AGX_FIELD_SERIES_ROWS holds the record");
+  if (field == AGX_FIELD_SERIES_LOCATE) {
+    if (b.locate_n == 0)
+      return fail("agx_field_download: AGX_FIELD_SERIES_LOCATE: block %d has located no points "
+                  "yet (upload the points first)", id);
+    return copy_out(c, out, b.locate_out.get(), (size_t)4 * b.locate_n);
+  }
+  if (s.payload.empty())
+    return series_no_plan("agx_field_download", field == AGX_FIELD_SERIES_PLAN
+                          ? "AGX_FIELD_SERIES_PLAN" : "AGX_FIELD_SERIES_ROWS", id);
+  if (field == AGX_FIELD_SERIES_PLAN) {
+    std::copy(s.payload.begin(), s.payload.end(), out);
+    return 0;
+  }
+  const size_t nrow = (size_t)s.V * s.P;
+  out[0] = (double)s.P; out[1] = s.V; out[2] = (double)s.ring.count;
+  out[3] = (double)s.ring.capacity;
+  // oldest first: the run from the head to the end of the ring, then the run that wrapped
+  long n[2];
+  s.ring.runs(&n[0], &n[1]);
+  const long first[2] = {s.ring.head, 0};
+  double* dst = out + 4;
+  for (int r = 0; r < 2; ++r) {
+    if (n[r] == 0) continue;
+    HIPCHK(hipMemcpy2DAsync(dst + 1, sizeof(double) * (nrow + 1),
+                            s.rows.get() + (size_t)first[r] * nrow, sizeof(double) * nrow,
+                            sizeof(double) * nrow, (size_t)n[r], hipMemcpyDeviceToHost,
+                            c->stream));
+    dst += (size_t)n[r] * (nrow + 1);
+  }
+  HIPCHK(hipGetLastError());
+  HIPCHK(hipStreamSynchronize(c->stream));
+  for (long r = 0; r < s.ring.count; ++r)
+    out[4 + (size_t)r * (nrow + 1)] = s.t[(size_t)s.ring.slot(r)];
+  return 0;
+}
+
 int agx_restart_pack(agx_ctx* c, int id, int which, double* out) {
   if (flush_consn(c)) return 1;
   if (id < 0 || id >= (int)c->blocks.size()) return fail("bad block id %d", id);
@@ -3368,6 +3620,9 @@ int agx_field_upload(agx_ctx* c, int id, int field, const double* in) {
   // and leaves every flag as a read would)
   if (field == AGX_FIELD_STAT_SAMPLE || field == AGX_FIELD_STAT_ACCUM)
     return stats_field_upload(c, id, field, in);
+  // (nor do the time-series fields: a sample is a read, a plan and a locate own their memory)
+  if (field >= AGX_FIELD_SERIES_PLAN && field <= AGX_FIELD_SERIES_LOCATE)
+    return series_field_upload(c, id, field, in);
   field_written_by_caller(c);
   if (flush_consn(c)) return 1;
   if (id < 0 || id >= (int)c->blocks.size()) return fail("bad block id %d", id);

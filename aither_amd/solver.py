@@ -72,6 +72,36 @@ def pool_fluxes(parts, tags=None, bc_types=None):
     return total
 
 
+def pool_series(parts, records=None):
+    """Join located points (Solver.series_locate) of blocks, or of ranks: parts is a list of
+    [P, 5] arrays (gb, i, j, k, d2) for the same P points.  Per point the entry with the
+    smallest d2 is kept, the lowest gb among equal ones, in the caller's order of points.
+    Returns [P, 5].
+    records: the sampled rows to go with it -- a list (one entry per rank) of
+    {gb: (t, values)} of Solver.series_rows for blocks planned by
+    Solver.series_plan_located(where, ...) with the joined `where`; then the return is
+    (where, t[rows], values[rows, V, P]) with the points back in the caller's order.  Every
+    record must hold the same rows (the ranks sample in step)."""
+    where = np.array(parts[0], dtype=np.float64)
+    for part in parts[1:]:
+        part = np.asarray(part, dtype=np.float64)
+        take = (part[:, 4] < where[:, 4]) | ((part[:, 4] == where[:, 4]) &
+                                             (part[:, 0] < where[:, 0]))
+        where[take] = part[take]
+    if records is None:
+        return where
+    t = values = None
+    for rank_records in records:
+        for gb, (tb, vb) in rank_records.items():
+            at = np.flatnonzero(where[:, 0] == gb)
+            if values is None:
+                t = np.array(tb, dtype=np.float64)
+                values = np.full((vb.shape[0], vb.shape[1], len(where)), np.nan)
+            assert np.array_equal(t, tb), "the records of the blocks hold different rows"
+            values[:, :, at] = vb
+    return where, t, values
+
+
 class DistExchange:
     """An agx_exchange (include/aither_gfx950.h) on torch.distributed
     point-to-point with HOST buffers: what an MPI adapter would pass
@@ -612,6 +642,99 @@ class Solver:
             res[name] = rows
         return res
 
+    # -- time series at chosen cells and wall faces, recorded on the device ----------------
+    def _series_up(self, gb, field, payload, what):
+        a = np.ascontiguousarray(payload, dtype=np.float64)
+        self.api.check(self.api.field_upload(self.ctx, self.block_ids[gb], abi.FIELD[field],
+                                             a.ctypes.data_as(abi.c_dp)), what)
+
+    def _series_down(self, gb, field, size, what):
+        out = np.empty(size)
+        self.api.check(self.api.field_download(self.ctx, self.block_ids[gb], abi.FIELD[field],
+                                               out.ctypes.data_as(abi.c_dp)), what)
+        return out
+
+    def series_plan(self, gb, names, points, capacity, kind="cells"):
+        """Plan the time series of block gb (AGX_FIELD_SERIES_PLAN): the variables `names`
+        (abi.OUT for kind "cells", abi.WALL_OUT for kind "wall") at `points` -- [P, 3] cells
+        (i, j, k), or [P] indices into the wall payload in the order of wall_pack's rows
+        concatenated over wall_surfaces(gb).  Replaces the block's plan, discards its rows and
+        allocates a ring of `capacity` rows on the device; no points discards the plan."""
+        payload = abi.series_plan(names, points, capacity, kind)
+        self._series_up(gb, "series_plan", payload, "series_plan")
+        book = self.__dict__.setdefault("_series_book", {})
+        if int(payload[1]) == 0:
+            book.pop(gb, None)
+        else:
+            # [P, V, capacity, rows]: what sizes a collect, kept as the library keeps it
+            book[gb] = [int(payload[1]), len(names), int(capacity), 0]
+
+    def series_sample(self, t):
+        """Append one row -- t and the planned variables at the planned points, exactly what
+        output_pack / wall_pack hold there now -- to the record of every block of this rank
+        that has a plan, in ascending gb (AGX_FIELD_SERIES_SAMPLE).  One kernel per block on
+        the context's stream: no synchronisation, no copy, no allocation.  A full record
+        refuses: collect (series_rows) and drop (series_drop) first.
+        Block by block, not all or nothing: a plan with gradient names and every wall plan
+        refuse between phase_bc_faces and phase_residual, a plan of plain cell variables
+        samples there, so a call that raises has sampled the blocks before the refusing one.
+        Call it between time steps, where every plan is legal."""
+        one = np.array([float(t)])
+        for gb in sorted(self.__dict__.get("_series_book", {})):
+            self._series_up(gb, "series_sample", one, "series_sample")
+            self._series_book[gb][3] += 1
+
+    def series_rows(self, gb):
+        """The record of block gb, oldest row first: (t[rows], values[rows, V, P]), dimensional
+        (AGX_FIELD_SERIES_ROWS; synchronises, leaves the record as it is)."""
+        npts, nvar, cap, _ = self.__dict__.get("_series_book", {}).get(gb, (0, 0, 0, 0))
+        out = self._series_down(gb, "series_rows", abi.series_rows_size(npts, nvar, cap),
+                                "series_rows")
+        return abi.series_rows_split(out)
+
+    def series_drop(self, gb, n=None):
+        """Drop the oldest n rows of block gb's record (all of them by default), making room
+        for as many samples: the record is a ring and never reallocates."""
+        entry = self.__dict__.get("_series_book", {}).get(gb)
+        if n is None:
+            n = entry[3] if entry else 0
+        self._series_up(gb, "series_rows", np.array([float(n)]), "series_drop")
+        if entry:
+            entry[3] -= int(n)
+
+    def series_clear(self):
+        """Discard the plan and the record of every block of this rank."""
+        for gb in sorted(self.__dict__.get("_series_book", {})):
+            self.series_plan(gb, [], [], 1)
+
+    def series_locate(self, points):
+        """For each of points[P, 3] (in the units of the "center" field) the physical cell of
+        this rank's blocks whose centre is nearest, searched on the device
+        (AGX_FIELD_SERIES_LOCATE, every block of the rank): [P, 5] = (gb, i, j, k, d2).  Among
+        equally near cells of a block the lowest (k nj + j) ni + i wins, among blocks at equal
+        d2 the lowest gb.  pool_series joins the results of ranks."""
+        pts = np.ascontiguousarray(points, dtype=np.float64).reshape(-1, 3)
+        payload = np.concatenate([[float(len(pts))], pts.ravel()])
+        parts = []
+        for gb in sorted(self.block_ids):
+            self._series_up(gb, "series_locate", payload, "series_locate")
+            got = self._series_down(gb, "series_locate", 4 * len(pts), "series_locate")
+            parts.append(np.column_stack([np.full(len(pts), float(gb)), got.reshape(-1, 4)]))
+        return pool_series(parts)
+
+    def series_plan_located(self, where, names, capacity):
+        """Plan every block of this rank for the points of `where` ([P, 5] of series_locate or
+        pool_series) that lie in it.  Returns {gb: indices into `where` of its points}, the
+        order of the block's points in its rows."""
+        where = np.asarray(where)
+        mine = {}
+        for gb in sorted(self.block_ids):
+            at = np.flatnonzero(where[:, 0] == gb)
+            if at.size:
+                self.series_plan(gb, names, where[at, 1:4], capacity)
+                mine[gb] = at
+        return mine
+
     def restart_pack(self, gb, which=0):
         """WriteRestart's payload of block gb: [nk, nj, ni, n_eq + 1], dimensional."""
         g = self.case.blocks[gb].geom
@@ -914,6 +1037,28 @@ class MultigridSolver:
 
     def stats_upload(self, gb, payload):
         return self.levels[0].stats_upload(gb, payload)
+
+    # time series: those of the finest level
+    def series_plan(self, gb, names, points, capacity, kind="cells"):
+        return self.levels[0].series_plan(gb, names, points, capacity, kind)
+
+    def series_sample(self, t):
+        return self.levels[0].series_sample(t)
+
+    def series_rows(self, gb):
+        return self.levels[0].series_rows(gb)
+
+    def series_drop(self, gb, n=None):
+        return self.levels[0].series_drop(gb, n)
+
+    def series_clear(self):
+        return self.levels[0].series_clear()
+
+    def series_locate(self, points):
+        return self.levels[0].series_locate(points)
+
+    def series_plan_located(self, where, names, capacity):
+        return self.levels[0].series_plan_located(where, names, capacity)
 
     def _p(self, a, ctype):
         return a.ctypes.data_as(C.POINTER(ctype))

@@ -132,7 +132,59 @@ enum { AGX_FIELD_STATE = 0,      /* state_      nEq, with ghosts           */
         * is refused by name when P or V are not this library's and context's, or W or the
         * sample count is negative or non-finite; download before the first sample is refused
         * by name. */
-       AGX_FIELD_STAT_SAMPLE = 23, AGX_FIELD_STAT_ACCUM = 24
+       AGX_FIELD_STAT_SAMPLE = 23, AGX_FIELD_STAT_ACCUM = 24,
+       /* time series at chosen points of the block, recorded on the device: the signals of an
+        * unsteady run (spectra, two-point correlations, shedding frequencies) beside its
+        * averages.  All payloads are arrays of doubles; counts, ids and indices are integral
+        * doubles, and a payload with a non-integral, negative, non-finite or out-of-range entry
+        * is refused by name, the message saying which entry.  After agx_setup_finalize.
+        * SERIES_PLAN: upload and download, the block's plan:
+        *   {kind, P, V, capacity, V variable ids, P points}
+        *   kind 0, cells: ids < AGX_OUT_COUNT; a point is three values i, j, k of a physical
+        *     cell (4 + V + 3 P doubles);
+        *   kind 1, wall faces: ids AGX_WALL_*; a point is one index into the block's wall
+        *     payload, in the order agx_output_pack hands the wall variables out
+        *     (4 + V + P doubles).
+        * A plan holds one kind, as an agx_output_pack call holds one range.  An upload replaces
+        * the block's plan, discards its rows and allocates capacity x V x P doubles on the
+        * device; P == 0 discards the plan and frees the memory (V, capacity and what follows
+        * are not read).  Refused by name: unknown ids; tke, sdr, f1, f2, their gradients and
+        * residuals, and the wall's tke and sdr in the 5-equation libraries; viscosity in an
+        * inviscid context; wall ids without a viscous context or on a block without a
+        * viscousWall surface; V < 1, V > AGX_OUT_COUNT; capacity < 1.  A refused upload leaves
+        * the plan and the rows as they were.  A download returns the payload as uploaded and is
+        * refused by name when the block has no plan.
+        * SERIES_SAMPLE: upload only, ONE finite double t.  Appends one row to the block's
+        * record: t and the V x P values, variable-major [v * P + p], dimensional -- exactly
+        * what agx_output_pack with the plan's ids would deliver at those points at that moment.
+        * The call enqueues one kernel on the context's stream and returns: it does not
+        * synchronise the stream, copies nothing to the host and allocates nothing.  A sample
+        * is a READ of the run and leaves it bit-identical; its legality is that of the
+        * agx_output_pack call with the same ids ("reads between phases" at
+        * agx_field_download): a cell plan without gradient ids reads physical cells only and
+        * is legal at every position; a cell plan with gradient ids and every wall plan refill
+        * the ghost cells and are refused between agx_phase_bc_faces and agx_phase_residual;
+        * a wall plan on wall-law surfaces is refused before the first residual.  Refused by
+        * name as well: a full record (rows == capacity: collect the rows first -- nothing is
+        * ever overwritten); a block without a plan; a wall plan whose block's surfaces were
+        * set again (agx_block_set_bcs) since the plan's upload; a non-finite t; a download.
+        * SERIES_ROWS: download {P, V, rows, capacity}, then `rows` rows of 1 + V P doubles
+        * {t, values}, oldest first; the caller's buffer holds 4 + capacity (1 + V P) doubles.
+        * The download synchronises and leaves the record as it is.  Upload of ONE double n,
+        * 0 <= n <= rows: the oldest n rows are dropped.  The record is a ring: a long run
+        * samples, collects and drops for ever in the memory of the plan's upload, the rows
+        * recorded after a drop wrapping around.  Both are refused by name without a plan.
+        * SERIES_LOCATE: upload {P, P triples x, y, z} (P >= 1, every coordinate finite and
+        * at most 1e150 in magnitude) in the units of AGX_FIELD_CENTER: the library finds on
+        * the device, for each point, the PHYSICAL cell of this block whose centre is nearest.
+        * Download: P x {i, j, k, d2} of the last upload, refused by name before one.  Tie rule:
+        * among cells at equal squared distance the lowest linear index (k nj + j) ni + i
+        * wins.  d2 is dx dx + dy dy + dz dz of centre - point; the compiler may contract the
+        * sum, so cells whose distances differ by a few units of 2^-53 relative are not decided
+        * the way an uncontracted sum would (as agx_state_from_cloud).  Exhaustive, points x
+        * cells.  Locate touches neither the plan nor the record. */
+       AGX_FIELD_SERIES_PLAN = 25, AGX_FIELD_SERIES_SAMPLE = 26, AGX_FIELD_SERIES_ROWS = 27,
+       AGX_FIELD_SERIES_LOCATE = 28
 };
 
 /* variables of a function file, WriteFunFile (output.cpp:235-407): formed and

@@ -98,6 +98,7 @@ class hotPath {
   AGX_CAT(AGX_SYMBOL_PREFIX, ctx) *ctx_ = nullptr;
   int numEqns_ = 5;
   int numBlocks_ = 0;
+  std::vector<bool> seriesPlanned_;   // blocks with a time-series plan (SetSeriesPlan)
 
   static void Check(int rc, const char *what) {
     if (rc != 0) {   // reference convention: report and stop
@@ -262,6 +263,48 @@ class hotPath {
   void SetStatisticsPayload(int block, const double *payload) {
     Check(AGX_SYM(field_upload)(ctx_, block, AGX_FIELD_STAT_ACCUM, payload),
           "hotPath::SetStatisticsPayload");
+  }
+  // Time series (no counterpart in the reference; see AGX_FIELD_SERIES_PLAN in the C header):
+  // chosen variables at chosen cells or wall faces, one row per sample, recorded on the
+  // device.  SetSeriesPlan once per block ({kind, P, V, capacity, ids, points} as doubles);
+  // the time loop calls SampleSeries after mgSolution::Iterate has converged a time step --
+  // one kernel per planned block, no synchronisation, no copy -- and every `capacity` steps
+  // at the latest SeriesRows (which synchronises) and DropSeriesRows.  Like SampleStatistics
+  // it goes block by block: call it between time steps, where every plan is legal.
+  void SetSeriesPlan(int block, const double *plan) {
+    Check(AGX_SYM(field_upload)(ctx_, block, AGX_FIELD_SERIES_PLAN, plan),
+          "hotPath::SetSeriesPlan");
+    if (block >= static_cast<int>(seriesPlanned_.size())) seriesPlanned_.resize(block + 1, false);
+    seriesPlanned_[block] = plan[1] != 0.0;
+  }
+  void SampleSeries(double t) {
+    for (int b = 0; b < static_cast<int>(seriesPlanned_.size()); ++b)
+      if (seriesPlanned_[b])
+        Check(AGX_SYM(field_upload)(ctx_, b, AGX_FIELD_SERIES_SAMPLE, &t),
+              "hotPath::SampleSeries");
+  }
+  // {P, V, rows, capacity}, then the rows {t, V P values} oldest first; `rows` holds
+  // 4 + capacity (1 + V P) doubles
+  void SeriesRows(int block, double *rows) const {
+    Check(AGX_SYM(field_download)(ctx_, block, AGX_FIELD_SERIES_ROWS, rows),
+          "hotPath::SeriesRows");
+  }
+  void DropSeriesRows(int block, int64_t n) {
+    const double count = static_cast<double>(n);
+    Check(AGX_SYM(field_upload)(ctx_, block, AGX_FIELD_SERIES_ROWS, &count),
+          "hotPath::DropSeriesRows");
+  }
+  // the physical cell of the block nearest to each of numPts points (x, y, z in the units of
+  // center_): where[numPts][4] = i, j, k, squared distance; the lowest linear cell index among
+  // equally near ones
+  void LocateCells(int block, int64_t numPts, const double *points, double *where) {
+    std::vector<double> payload(1 + 3 * static_cast<size_t>(numPts));
+    payload[0] = static_cast<double>(numPts);
+    std::copy(points, points + 3 * numPts, payload.begin() + 1);
+    Check(AGX_SYM(field_upload)(ctx_, block, AGX_FIELD_SERIES_LOCATE, payload.data()),
+          "hotPath::LocateCells");
+    Check(AGX_SYM(field_download)(ctx_, block, AGX_FIELD_SERIES_LOCATE, where),
+          "hotPath::LocateCells");
   }
   // WriteRestart (output.cpp:651-752): the block's payload, numEqns + 1 values per cell;
   // secondSolution: consVarsNm1 (multilevel time integration)
