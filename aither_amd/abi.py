@@ -40,12 +40,20 @@ STAT_FIELD = {"stat_sample": 23, "stat_accum": 24}
 # above, and resolved the same way: FIELD["series_plan"] works, iteration does not see them.
 SERIES_FIELD = {"series_plan": 25, "series_sample": 26, "series_rows": 27, "series_locate": 28}
 SERIES_KIND = {"cells": 0, "wall": 1}
+# spectra along a homogeneous direction (AGX_FIELD_SPECTRA_*): the plan, one sample (upload of
+# a weight), the raw accumulators, the dimensional values.  Resolved like the series ids.
+SPECTRA_FIELD = {"spectra_plan": 29, "spectra_sample": 30, "spectra_accum": 31,
+                 "spectra_values": 32}
+SPECTRA_NAMES = ("density", "vel_x", "vel_y", "vel_z", "pressure", "temperature")
+SPECTRA_MAX_N = 1024
 
 
 class _Fields(dict):
     def __missing__(self, name):
         if name in SERIES_FIELD:
             return SERIES_FIELD[name]
+        if name in SPECTRA_FIELD:
+            return SPECTRA_FIELD[name]
         return STAT_FIELD[name]
 
 
@@ -190,6 +198,55 @@ def series_rows_join(t, values, capacity):
                            v.reshape(rows, nvar * npts)], axis=1)
     return np.concatenate([np.array([npts, nvar, rows, capacity], dtype=np.float64),
                            body.ravel()])
+
+
+def spectra_plan(names, pairs=(), along="i", over=""):
+    """The payload of AGX_FIELD_SPECTRA_PLAN: {along, over mask, nvar, npair, nvar ids of OUT,
+    npair pairs} as float64.  names out of SPECTRA_NAMES; a pair is two of the names, or two
+    indices into them.  No names: the payload that frees the block's spectra."""
+    names = list(names)
+    flat = []
+    for a, b in pairs:
+        flat += [float(names.index(x)) if isinstance(x, str) else float(x) for x in (a, b)]
+    head = [float("ijk".index(along)), float(cstat_mask(over)) if over else 0.0,
+            float(len(names)), float(len(flat) // 2)]
+    return np.array(head + [float(OUT[n]) for n in names] + flat, dtype=np.float64)
+
+
+def spectra_plan_parse(payload):
+    """The inverse of spectra_plan: (names, pairs as index pairs, along, over)."""
+    a = np.asarray(payload, dtype=np.float64)
+    nvar, npair = int(a[2]), int(a[3])
+    table = {v: k for k, v in OUT.items()}
+    names = [table[int(v)] for v in a[4:4 + nvar]]
+    pairs = [(int(x), int(y)) for x, y in a[4 + nvar:4 + nvar + 2 * npair].reshape(npair, 2)]
+    over = "".join(d for bit, d in enumerate("ijk") if int(a[1]) >> bit & 1)
+    return names, pairs, "ijk"[int(a[0])], over
+
+
+def spectra_shape(extents, along, over):
+    """(remaining extents in (k, j, i) order, nmode) of a plan on a block of extents
+    (ni, nj, nk)."""
+    a = "ijk".index(along)
+    rest = tuple(extents[d] for d in (2, 1, 0) if d != a and "ijk"[d] not in over)
+    return rest, extents[a] // 2 + 1
+
+
+def spectra_accum_size(nvar, npair, nbin, nmode):
+    """Doubles of an AGX_FIELD_SPECTRA_ACCUM payload."""
+    return 8 + nvar + 2 * npair + (nvar + npair) * nbin * nmode
+
+
+def spectra_accum_split(payload):
+    """An AGX_FIELD_SPECTRA_ACCUM payload into (plan payload, W, samples, S[nspec, nbin,
+    nmode]), S raw (nondimensional)."""
+    a = np.asarray(payload, dtype=np.float64)
+    nvar, npair = int(a[2]), int(a[3])
+    np_ = 4 + nvar + 2 * npair
+    nbin, nmode = int(a[np_ + 2]), int(a[np_ + 3])
+    body = a[np_ + 4:np_ + 4 + (nvar + npair) * nbin * nmode]
+    return a[:np_].copy(), float(a[np_]), float(a[np_ + 1]), \
+        body.reshape(nvar + npair, nbin, nmode).copy()
 
 
 # cell planes of the accumulators: 9 means + extras (eddy viscosity; k, omega) + 9 second

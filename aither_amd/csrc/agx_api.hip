@@ -11,6 +11,7 @@
 #include "agx_stats.hpp"
 #include "agx_series.hpp"
 #include "agx_series_ring.hpp"
+#include "agx_spectra.hpp"
 #include "agx_flux.hpp"
 #include "agx_mem.hpp"
 #include "agx_switches.hpp"
@@ -183,6 +184,16 @@ struct Block {
     std::vector<double> t;
   } series;
   long wall_epoch = 0;
+  // spectra (agx_spectra.hpp): the plan as uploaded (empty: no plan), its shape, the twiddle
+  // table, the lines of each record, the records of a sample and the accumulators S
+  // [spectrum][bin][mode], nondimensional; W and the sample count are the host's
+  struct Spectra {
+    std::vector<double> payload;
+    SpectraDev dev;
+    double factor[SPECTRA_MAX_VAR + SPECTRA_MAX_PAIR] = {};
+    DevBuf<double> tw, lines, part, S;
+    double W = 0.0, samples = 0.0;
+  } spectra;
   // the result of the last AGX_FIELD_SERIES_LOCATE upload, 4 doubles per point
   DevBuf<double> locate_out;
   long locate_n = 0;
@@ -344,6 +355,8 @@ static int stats_pack(agx_ctx* c, int id, bool wall, int nvar, const int32_t* va
 static int stats_collapse(agx_ctx* c, int id, int nvar, const int32_t* vars, double* out);
 static int series_field_upload(agx_ctx* c, int id, int field, const double* in);
 static int series_field_download(agx_ctx* c, int id, int field, double* out);
+static int spectra_field_upload(agx_ctx* c, int id, int field, const double* in);
+static int spectra_field_download(agx_ctx* c, int id, int field, double* out);
 #if AGX_FAST
 static int d2_prepare(agx_ctx* c, Block& blk, int write_x, int again, int norms);
 #endif
@@ -2522,6 +2535,8 @@ int agx_field_download(agx_ctx* c, int id, int field, double* out) {
     return stats_field_download(c, id, field, out);
   if (field >= AGX_FIELD_SERIES_PLAN && field <= AGX_FIELD_SERIES_LOCATE)
     return series_field_download(c, id, field, out);
+  if (field >= AGX_FIELD_SPECTRA_PLAN && field <= AGX_FIELD_SPECTRA_VALUES)
+    return spectra_field_download(c, id, field, out);
   Block& b = c->blocks[id];
   // (the D2 arrays hold x with the writer's tag in its two lowest mantissa bits: while the
   // planes are current -- an upload or a multigrid transfer wrote them last -- they are the
@@ -3419,6 +3434,205 @@ static int series_field_download(agx_ctx* c, int id, int field, double* out) {
   return 0;
 }
 
+// ---- spectra (agx_spectra.hpp; include/aither_gfx950.h at AGX_FIELD_SPECTRA_PLAN) ------------
+namespace {
+int spectra_no_plan(const char* call, const char* field, int id) {
+  return fail("%s: %s: block %d has no plan (upload AGX_FIELD_SPECTRA_PLAN first)", call, field,
+              id);
+}
+// doubles of a plan payload; the header of an accumulator payload follows it
+size_t spectra_plan_size(const SpectraShape& s) { return 4 + (size_t)s.nvar + 2 * (size_t)s.npair; }
+int spectra_plan_upload(agx_ctx* c, int id, const double* in) {
+  static const char F[] = "AGX_FIELD_SPECTRA_PLAN";
+  Block& b = c->blocks[id];
+  long along, over, nvar, npair;
+  if (series_entry(F, in, 2, "nvar, the variables", 0, 2147483647.0, &nvar)) return 1;
+  if (nvar == 0) {
+    HIPCHK(hipStreamSynchronize(c->stream));     // (before the memory is freed)
+    b.spectra = Block::Spectra();
+    return 0;
+  }
+  if (nvar > SPECTRA_MAX_VAR)
+    return fail("agx_field_upload: %s: nvar = %ld: a plan holds at most %d variables", F, nvar,
+                SPECTRA_MAX_VAR);
+  if (series_entry(F, in, 0, "along: 0 i, 1 j, 2 k", 0, 2, &along)) return 1;
+  if (series_entry(F, in, 1, "over, the mask of the pooled directions", 0, 7, &over)) return 1;
+  if (series_entry(F, in, 3, "npair, the pairs", 0, SPECTRA_MAX_PAIR, &npair)) return 1;
+  if (over >> along & 1)
+    return fail("agx_field_upload: %s: over (mask %ld) contains along (%ld): a direction is "
+                "transformed or pooled, not both", F, over, along);
+  Block::Spectra sp;
+  SpectraDev& d = sp.dev;
+  memset(&d, 0, sizeof d);
+  const agx_gas& a = c->cfg.gas;
+  const double fac[6] = {a.rho_ref, a.a_ref, a.a_ref, a.a_ref, a.rho_ref * a.a_ref * a.a_ref,
+                         a.t_ref};
+  static const int OUT_ID[6] = {AGX_OUT_DENSITY, AGX_OUT_VEL_X, AGX_OUT_VEL_Y, AGX_OUT_VEL_Z,
+                                AGX_OUT_PRESSURE, AGX_OUT_TEMPERATURE};
+  for (long v = 0; v < nvar; ++v) {
+    long var;
+    if (series_entry(F, in, 4 + v, "a variable id", 0, 2147483647.0, &var)) return 1;
+    int code = -1;
+    for (int n = 0; n < 6; ++n)
+      if (var == OUT_ID[n]) code = n;
+    if (code < 0)
+      return fail("agx_field_upload: %s: entry %ld: variable %ld is not one of density, vel_x, "
+                  "vel_y, vel_z, pressure, temperature", F, 4 + v, var);
+    for (long u = 0; u < v; ++u)
+      if (d.var[u] == code)
+        return fail("agx_field_upload: %s: entry %ld: variable %ld is repeated", F, 4 + v, var);
+    d.var[v] = code;
+    sp.factor[v] = fac[code] * fac[code];
+  }
+  for (int n = 0; n < SPECTRA_MAX_PAIR; ++n) d.pair_spec[n] = -1;
+  for (long p = 0; p < npair; ++p) {
+    long ab[2];
+    for (int e = 0; e < 2; ++e)
+      if (series_entry(F, in, 4 + nvar + 2 * p + e, "a variable of a pair, an index into the "
+                       "plan's variables", 0, (double)(nvar - 1), &ab[e])) return 1;
+    if (ab[0] == ab[1])
+      return fail("agx_field_upload: %s: pair %ld is (%ld, %ld): the auto-spectrum of a variable "
+                  "is kept already", F, p, ab[0], ab[1]);
+    const int lo = (int)(ab[0] < ab[1] ? ab[0] : ab[1]), hi = (int)(ab[0] < ab[1] ? ab[1] : ab[0]);
+    int& slot = d.pair_spec[spectra_pair_index(lo, hi)];
+    if (slot >= 0)
+      return fail("agx_field_upload: %s: pair %ld, (%ld, %ld), is repeated (in this or in the "
+                  "other order)", F, p, ab[0], ab[1]);
+    slot = (int)(nvar + p);
+    sp.factor[nvar + p] = fac[d.var[ab[0]]] * fac[d.var[ab[1]]];
+  }
+  const int ext[3] = {b.d.ni, b.d.nj, b.d.nk};
+  if (ext[along] < 2)
+    return fail("agx_field_upload: %s: block %d has N = %d cells along direction %ld: a spectrum "
+                "needs N >= 2", F, id, ext[along], along);
+  if (!spectra_shape(ext, (int)along, (int)over, (int)nvar, (int)npair, &d.s))
+    return fail("agx_field_upload: %s: block %d has N = %d cells along direction %ld: the line "
+                "kernel holds lines of at most AGX_SPECTRA_MAX_N = %d cells", F, id, ext[along],
+                along, SPECTRA_MAX_N);
+  const SpectraShape& s = d.s;
+  std::vector<double> tw(2 * (size_t)s.n), lines((size_t)s.nrec);
+  for (int q = 0; q < s.n; ++q) {
+    const long double ang = 2.0L * 3.14159265358979323846264338327950288L * q / s.n;
+    tw[2 * q] = (double)cosl(ang);
+    tw[2 * q + 1] = (double)sinl(ang);
+  }
+  for (long r = 0; r < s.nrec; ++r) lines[r] = (double)spectra_record_lines(s, r);
+  const size_t nval = (size_t)spectra_values(s);
+  if (sp.tw.upload(tw) != hipSuccess || sp.lines.upload(lines) != hipSuccess ||
+      sp.part.alloc((size_t)s.nrec * nval) != hipSuccess || sp.S.alloc(nval) != hipSuccess)
+    return fail("agx_field_upload: %s: no device memory for %ld records of %zu doubles", F,
+                s.nrec, nval);
+  HIPCHK(hipMemsetAsync(sp.S.get(), 0, sizeof(double) * nval, c->stream));
+  sp.payload.assign(in, in + spectra_plan_size(s));
+  HIPCHK(hipStreamSynchronize(c->stream));       // (before the old memory is freed)
+  b.spectra = std::move(sp);
+  return 0;
+}
+int spectra_sample(agx_ctx* c, int id, double w) {
+  static const char F[] = "AGX_FIELD_SPECTRA_SAMPLE";
+  Block& b = c->blocks[id];
+  Block::Spectra& sp = b.spectra;
+  if (sp.payload.empty()) return spectra_no_plan("agx_field_upload", F, id);
+  if (!std::isfinite(w) || w < 0.0)
+    return fail("agx_field_upload: %s: the weight %g is negative or not finite (w > 0 samples, "
+                "w == 0 resets the block's spectra)", F, w);
+  const SpectraShape& s = sp.dev.s;
+  const long nval = spectra_values(s);
+  if (w == 0.0) {
+    HIPCHK(hipMemsetAsync(sp.S.get(), 0, sizeof(double) * nval, c->stream));
+    sp.W = sp.samples = 0.0;
+    return 0;
+  }
+  const double W = sp.W + w, r = w / W;
+  const dim3 grid((unsigned)(s.nchunk * s.nfix));
+  const bool small = spectra_lds_doubles(s.n, s.nvar, s.tl) <= SPECTRA_LDS_SMALL;
+  by_int<1, 2, 3, 4, 5, 6>(s.nvar, [&](auto nv) {
+    constexpr int NV = decltype(nv)::value;
+    if (small)
+      hipLaunchKernelGGL((k_spectra_lines<NV, SPECTRA_LDS_SMALL>), grid, dim3(256), 0, c->stream,
+                         b.d, c->gas, sp.dev, sp.tw.get(), sp.part.get());
+    else
+      hipLaunchKernelGGL((k_spectra_lines<NV, SPECTRA_LDS_DOUBLES>), grid, dim3(256), 0,
+                         c->stream, b.d, c->gas, sp.dev, sp.tw.get(), sp.part.get());
+    return 0;
+  });
+  hipLaunchKernelGGL(k_spectra_join, dim3((unsigned)((nval + 255) / 256)), dim3(256), 0, c->stream,
+                     nval, s.nrec, sp.lines.get(), sp.part.get(), r, sp.S.get());
+  HIPCHK(hipGetLastError());
+  sp.W = W;
+  sp.samples += 1.0;
+  return 0;
+}
+int spectra_accum_upload(agx_ctx* c, int id, const double* in) {
+  static const char F[] = "AGX_FIELD_SPECTRA_ACCUM";
+  Block::Spectra& sp = c->blocks[id].spectra;
+  if (sp.payload.empty()) return spectra_no_plan("agx_field_upload", F, id);
+  const SpectraShape& s = sp.dev.s;
+  const size_t np = spectra_plan_size(s);
+  for (size_t n = 0; n < np; ++n)
+    if (!(in[n] == sp.payload[n]))
+      return fail("agx_field_upload: %s: entry %zu of the payload's plan is %g, the plan of block "
+                  "%d holds %g: an average is carried on under the plan it was taken with", F, n,
+                  in[n], id, sp.payload[n]);
+  const double* h = in + np;
+  if (h[2] != (double)s.nbin || h[3] != (double)s.nmode)
+    return fail("agx_field_upload: %s: the payload holds %g bins of %g modes, the plan of block "
+                "%d gives %ld of %d", F, h[2], h[3], id, s.nbin, s.nmode);
+  if (!std::isfinite(h[0]) || h[0] < 0.0 || !std::isfinite(h[1]) || h[1] < 0.0)
+    return fail("agx_field_upload: %s: the sum of weights %g or the sample count %g is negative "
+                "or not finite", F, h[0], h[1]);
+  HIPCHK(hipMemcpyAsync(sp.S.get(), h + 4, sizeof(double) * spectra_values(s),
+                        hipMemcpyHostToDevice, c->stream));
+  HIPCHK(hipStreamSynchronize(c->stream));
+  sp.W = h[0];
+  sp.samples = h[1];
+  return 0;
+}
+}  // namespace
+
+static int spectra_field_upload(agx_ctx* c, int id, int field, const double* in) {
+  if (flush_consn(c)) return 1;
+  if (id < 0 || id >= (int)c->blocks.size()) return fail("bad block id %d", id);
+  if (!in) return fail("agx_field_upload: null pointer");
+  if (!c->finalized) return fail("agx_setup_finalize has not been called");
+  switch (field) {
+    case AGX_FIELD_SPECTRA_PLAN: return spectra_plan_upload(c, id, in);
+    case AGX_FIELD_SPECTRA_SAMPLE: return spectra_sample(c, id, in[0]);
+    case AGX_FIELD_SPECTRA_ACCUM: return spectra_accum_upload(c, id, in);
+  }
+  if (c->blocks[id].spectra.payload.empty())
+    return spectra_no_plan("agx_field_upload", "AGX_FIELD_SPECTRA_VALUES", id);
+  return fail("agx_field_upload: AGX_FIELD_SPECTRA_VALUES is download only (the dimensional "
+              "spectra); AGX_FIELD_SPECTRA_ACCUM carries an average on");
+}
+
+static int spectra_field_download(agx_ctx* c, int id, int field, double* out) {
+  if (!out) return fail("agx_field_download: null pointer");
+  const Block::Spectra& sp = c->blocks[id].spectra;
+  if (field == AGX_FIELD_SPECTRA_PLAN || field == AGX_FIELD_SPECTRA_SAMPLE)
+    return fail("agx_field_download: %s is upload only; AGX_FIELD_SPECTRA_ACCUM holds the plan "
+                "and the accumulators", field == AGX_FIELD_SPECTRA_PLAN
+                ? "AGX_FIELD_SPECTRA_PLAN" : "AGX_FIELD_SPECTRA_SAMPLE");
+  const bool raw = field == AGX_FIELD_SPECTRA_ACCUM;
+  if (sp.payload.empty())
+    return spectra_no_plan("agx_field_download", raw ? "AGX_FIELD_SPECTRA_ACCUM"
+                           : "AGX_FIELD_SPECTRA_VALUES", id);
+  const SpectraShape& s = sp.dev.s;
+  const size_t nval = (size_t)spectra_values(s);
+  if (raw) {
+    out = std::copy(sp.payload.begin(), sp.payload.end(), out);
+    out[0] = sp.W; out[1] = sp.samples; out[2] = (double)s.nbin; out[3] = s.nmode;
+    return copy_out(c, out + 4, sp.S.get(), nval);
+  }
+  if (copy_out(c, out, sp.S.get(), nval)) return 1;
+  // dimensional: the product of the two variables' output factors, as k_stats_pack's second
+  // moments
+  const size_t per = (size_t)s.nbin * s.nmode;
+  for (int n = 0; n < s.nvar + s.npair; ++n)
+    for (size_t e = 0; e < per; ++e) out[n * per + e] = out[n * per + e] * sp.factor[n];
+  return 0;
+}
+
 int agx_restart_pack(agx_ctx* c, int id, int which, double* out) {
   if (flush_consn(c)) return 1;
   if (id < 0 || id >= (int)c->blocks.size()) return fail("bad block id %d", id);
@@ -3623,6 +3837,9 @@ int agx_field_upload(agx_ctx* c, int id, int field, const double* in) {
   // (nor do the time-series fields: a sample is a read, a plan and a locate own their memory)
   if (field >= AGX_FIELD_SERIES_PLAN && field <= AGX_FIELD_SERIES_LOCATE)
     return series_field_upload(c, id, field, in);
+  // (nor do the spectra: a sample is a read, a plan and an upload of S own their memory)
+  if (field >= AGX_FIELD_SPECTRA_PLAN && field <= AGX_FIELD_SPECTRA_VALUES)
+    return spectra_field_upload(c, id, field, in);
   field_written_by_caller(c);
   if (flush_consn(c)) return 1;
   if (id < 0 || id >= (int)c->blocks.size()) return fail("bad block id %d", id);

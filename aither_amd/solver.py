@@ -102,6 +102,38 @@ def pool_series(parts, records=None):
     return where, t, values
 
 
+def pool_spectra(parts):
+    """Join the spectra (Solver.spectra) of blocks, or of ranks, that share N and the bins:
+    parts is a list of (values, W, lines) -- values[nspec, ..., nmode], the sum of weights and
+    the lines of a bin (the product of the block's pooled extents).  A part weighs lines x W;
+    joined in list order by the pairwise form of pool_bins, r = g2 / (g1 + g2):
+        S = S1 + r (S2 - S1)
+    in numpy float64, so parts with bit-identical values return them bit for bit.  Lines are
+    never lengthened: a spectrum stays that of a block's own N.  Returns (values, weight)."""
+    values, W, lines = parts[0]
+    values = np.array(values, dtype=np.float64)
+    weight = float(lines) * float(W)
+    for v2, W2, lines2 in parts[1:]:
+        g2 = float(lines2) * float(W2)
+        total = weight + g2
+        r = g2 / total if total != 0.0 else 0.0
+        values = values + r * (np.asarray(v2, dtype=np.float64) - values)
+        weight = total
+    return values, weight
+
+
+def correlation(spectrum, n):
+    """The circular two-point correlation of a one-sided spectrum (Solver.spectra, last axis
+    the modes 0 ... n // 2 of lines of n cells): R(r) = sum_m S_m cos(2 pi m r / n) for
+    r = 0 ... n - 1, last axis r.  R(0) is the mean of x_a x_b (Parseval); entry m = 0 carries
+    the product of the means, so R is the correlation of the values, not of the fluctuations
+    (drop S_0 for those).  Host numpy; the twiddle index m r mod n is formed in integers."""
+    s = np.asarray(spectrum, dtype=np.float64)
+    m = np.arange(s.shape[-1])
+    q = np.outer(m, np.arange(n)) % n
+    return s @ np.cos(2.0 * np.pi * q / n)
+
+
 class DistExchange:
     """An agx_exchange (include/aither_gfx950.h) on torch.distributed
     point-to-point with HOST buffers: what an MPI adapter would pass
@@ -208,6 +240,7 @@ class Solver:
         either, iterate() handles connections to other ranks and returns the
         globally reduced norms."""
         self.api, self.case, self.rank = api, case, rank
+        self._spectra_book = {}      # gb -> the plan the library holds (spectra_plan)
         self.ctx = C.c_void_p()
         api.check(api.ctx_create(device, rank, C.byref(self.ctx)), "ctx_create")
         if stream is not None:
@@ -735,6 +768,79 @@ class Solver:
                 mine[gb] = at
         return mine
 
+    # -- spectra along homogeneous directions, accumulated on the device ----------------------
+    def spectra_plan(self, gb, names, pairs=(), along="i", over=""):
+        """Plan the spectra of block gb (AGX_FIELD_SPECTRA_PLAN): the auto-spectra of `names`
+        (out of abi.SPECTRA_NAMES, at most 6) and the co-spectra of `pairs` (two names, or two
+        indices into names) along index direction `along`, the lines pooled with equal weights
+        over the directions of `over` (a string out of the other two).  Replaces the block's
+        plan, discards its accumulators and allocates; no names frees everything."""
+        payload = abi.spectra_plan(names, pairs, along, over)
+        self._series_up(gb, "spectra_plan", payload, "spectra_plan")
+        book = self._spectra_book
+        if not len(names):
+            book.pop(gb, None)
+            return
+        ni, nj, nk = self.case.blocks[gb].geom.n
+        rest, nmode = abi.spectra_shape((ni, nj, nk), along, over)
+        lines = int(np.prod([(ni, nj, nk)["ijk".index(d)] for d in over] or [1]))
+        book[gb] = {"payload": payload, "rest": rest, "nmode": nmode, "lines": lines,
+                    "n": (ni, nj, nk)["ijk".index(along)]}
+
+    def spectra_sample(self, weight=1.0):
+        """One sample of the state the device holds now into the spectra of every block of this
+        rank that has a plan, in ascending gb (AGX_FIELD_SPECTRA_SAMPLE): two kernels per block
+        on the context's stream, no synchronisation, no copy, no allocation.  Reads physical
+        cells only: legal at every position of the phase API."""
+        one = np.array([float(weight)])
+        for gb in sorted(self._spectra_book):
+            self._series_up(gb, "spectra_sample", one, "spectra_sample")
+
+    def spectra_reset(self):
+        """Discard the accumulated spectra of every planned block; the plans stay."""
+        self.spectra_sample(0.0)
+
+    def spectra_clear(self):
+        """Discard the plan and the spectra of every block of this rank."""
+        for gb in sorted(self._spectra_book):
+            self.spectra_plan(gb, [])
+
+    def _spectra_entry(self, gb):
+        entry = self._spectra_book.get(gb)
+        # (a block without a plan: the library refuses by name; one double is enough)
+        return entry or {"payload": np.zeros(4), "rest": (), "nmode": 1, "lines": 1, "n": 2}
+
+    def spectra_download(self, gb):
+        """The raw payload of block gb's spectra (AGX_FIELD_SPECTRA_ACCUM): the plan,
+        {W, samples, nbin, nmode} and the nondimensional S; abi.spectra_accum_split reads it."""
+        e = self._spectra_entry(gb)
+        nvar, npair = int(e["payload"][2]), int(e["payload"][3])
+        nbin = int(np.prod(e["rest"] or (1,)))
+        return self._series_down(gb, "spectra_accum",
+                                 abi.spectra_accum_size(nvar, npair, nbin, e["nmode"]),
+                                 "spectra_download")
+
+    def spectra_upload(self, gb, payload):
+        """Carry an average on: the payload of spectra_download into block gb, which must hold
+        the same plan (refused by name otherwise)."""
+        self._series_up(gb, "spectra_accum", payload, "spectra_upload")
+
+    def spectra(self, gb):
+        """The spectra of block gb (AGX_FIELD_SPECTRA_VALUES), dimensional:
+        (values[nspec, *remaining extents in (k, j, i) order, nmode], W, samples); the spectra
+        are the variables in plan order, then the pairs."""
+        e = self._spectra_entry(gb)
+        nspec = int(e["payload"][2]) + int(e["payload"][3])
+        nbin = int(np.prod(e["rest"] or (1,)))
+        out = self._series_down(gb, "spectra_values", max(nspec * nbin * e["nmode"], 1),
+                                "spectra")
+        _, W, samples, _ = abi.spectra_accum_split(self.spectra_download(gb))
+        return out.reshape((nspec,) + tuple(e["rest"]) + (e["nmode"],)), W, samples
+
+    def spectra_lines(self, gb):
+        """Lines of a bin of block gb's plan (what pool_spectra weighs a part by, with W)."""
+        return self._spectra_entry(gb)["lines"]
+
     def restart_pack(self, gb, which=0):
         """WriteRestart's payload of block gb: [nk, nj, ni, n_eq + 1], dimensional."""
         g = self.case.blocks[gb].geom
@@ -1059,6 +1165,31 @@ class MultigridSolver:
 
     def series_plan_located(self, where, names, capacity):
         return self.levels[0].series_plan_located(where, names, capacity)
+
+    # spectra: those of the finest level
+    def spectra_plan(self, gb, names, pairs=(), along="i", over=""):
+        return self.levels[0].spectra_plan(gb, names, pairs, along, over)
+
+    def spectra_sample(self, weight=1.0):
+        return self.levels[0].spectra_sample(weight)
+
+    def spectra(self, gb):
+        return self.levels[0].spectra(gb)
+
+    def spectra_download(self, gb):
+        return self.levels[0].spectra_download(gb)
+
+    def spectra_upload(self, gb, payload):
+        return self.levels[0].spectra_upload(gb, payload)
+
+    def spectra_reset(self):
+        return self.levels[0].spectra_reset()
+
+    def spectra_clear(self):
+        return self.levels[0].spectra_clear()
+
+    def spectra_lines(self, gb):
+        return self.levels[0].spectra_lines(gb)
 
     def _p(self, a, ctype):
         return a.ctypes.data_as(C.POINTER(ctype))

@@ -184,8 +184,55 @@ enum { AGX_FIELD_STATE = 0,      /* state_      nEq, with ghosts           */
         * the way an uncontracted sum would (as agx_state_from_cloud).  Exhaustive, points x
         * cells.  Locate touches neither the plan nor the record. */
        AGX_FIELD_SERIES_PLAN = 25, AGX_FIELD_SERIES_SAMPLE = 26, AGX_FIELD_SERIES_ROWS = 27,
-       AGX_FIELD_SERIES_LOCATE = 28
+       AGX_FIELD_SERIES_LOCATE = 28,
+       /* wavenumber spectra along a homogeneous index direction of the block, accumulated on
+        * the device: E_uu(k), the co-spectrum of uv, and with them the two-point correlations
+        * of an unsteady run.  Payloads are arrays of doubles, counts and ids integral doubles,
+        * checked like those of the time series.  After agx_setup_finalize.
+        * A line is one run of the N physical cells of the block along `along`.  Per line and
+        * variable the mean mu is taken (serially, ascending) and SUBTRACTED, then
+        *   X_m = sum_n (x_n - mu) exp(-2 pi i m n / N),  m = 1 ... N / 2,
+        *   P_m = c_m |X_m|^2 / N^2,  C_ab,m = c_m Re(X_a,m conj X_b,m) / N^2,
+        * c_m = 2 but 1 at m = N / 2 of an even N, and entry m = 0 is mu^2 (mu_a mu_b): the
+        * entries of a line sum to its mean of x_a x_b.  The lines of a bin -- one position of
+        * the directions that are neither `along` nor pooled -- pool with EQUAL weights (pooled
+        * directions are homogeneous; cell volumes are not used), samples by the running mean
+        * S += (w / W)(s - S).  No atomics, every order of summation fixed by the extents and
+        * the plan: the same calls give the same bits; identical lines or samples give one
+        * line's bits; doubling every weight changes no bit; a spectrum depends on its own
+        * variables only, so a plan of a subset or in another order returns the same bits.
+        * SPECTRA_PLAN: upload only,
+        *   {along (0 i, 1 j, 2 k), over (mask of the pooled directions, bit 0 i, 1 j, 2 k),
+        *    nvar, npair, nvar variable ids, npair pairs (a, b) of indices into the variables}
+        * (4 + nvar + 2 npair doubles).  Variables: AGX_OUT_DENSITY, _VEL_X, _VEL_Y, _VEL_Z,
+        * _PRESSURE, _TEMPERATURE, formed as the statistics form them.  The upload replaces the
+        * block's plan, discards its accumulators and allocates; nvar == 0 frees everything
+        * (nothing else is read).  Refused by name, the block left as it was: another variable,
+        * a repeated one, nvar > 6, a pair index out of range, a pair of a variable with
+        * itself, a pair repeated or given in both orders, over containing along, N < 2,
+        * N > AGX_SPECTRA_MAX_N (what the line kernel's LDS holds).
+        * SPECTRA_SAMPLE: upload only, ONE double w: one sample of the state the device holds
+        * now, with weight w.  Two kernels on the context's stream; no synchronisation, no copy,
+        * no allocation.  It reads physical cells only: a READ of the run that leaves it
+        * bit-identical and is legal at every position of the phase API, seeing the state
+        * agx_output_pack would return there.  w == 0 resets W, the sample count and the
+        * accumulators and keeps the plan.  Refused: w negative or not finite.
+        * SPECTRA_ACCUM: download and upload, for carrying an average into another run:
+        *   the plan's payload, then {W, samples, nbin, nmode}, then the raw (nondimensional)
+        *   S[spectrum][bin][mode]: 8 + nvar + 2 npair + (nvar + npair) nbin nmode doubles.
+        * An upload is refused by name unless its plan, nbin and nmode are the block's, and when
+        * W or the sample count is negative or not finite.
+        * SPECTRA_VALUES: download only, out[s][bin][m], dimensional (times the product of the
+        * two variables' output factors, like the second moments of AGX_STAT_BASE): s runs over
+        * the variables in plan order, then the pairs; the bins over the remaining directions,
+        * the lower index direction fastest; m = 0 ... N / 2.
+        * SAMPLE, ACCUM and VALUES are refused by name on a block without a plan. */
+       AGX_FIELD_SPECTRA_PLAN = 29, AGX_FIELD_SPECTRA_SAMPLE = 30, AGX_FIELD_SPECTRA_ACCUM = 31,
+       AGX_FIELD_SPECTRA_VALUES = 32
 };
+/* the longest line of a spectra plan: twiddles, one line of six variables and their means in
+ * the 80 KiB of LDS the line kernel declares */
+#define AGX_SPECTRA_MAX_N 1024
 
 /* variables of a function file, WriteFunFile (output.cpp:235-407): formed and
  * re-dimensionalised ON THE DEVICE by agx_output_pack, so an output step moves what the

@@ -99,6 +99,7 @@ class hotPath {
   int numEqns_ = 5;
   int numBlocks_ = 0;
   std::vector<bool> seriesPlanned_;   // blocks with a time-series plan (SetSeriesPlan)
+  std::vector<bool> spectraPlanned_;  // blocks with a spectra plan (SetSpectraPlan)
 
   static void Check(int rc, const char *what) {
     if (rc != 0) {   // reference convention: report and stop
@@ -305,6 +306,43 @@ class hotPath {
           "hotPath::LocateCells");
     Check(AGX_SYM(field_download)(ctx_, block, AGX_FIELD_SERIES_LOCATE, where),
           "hotPath::LocateCells");
+  }
+  // Spectra along a homogeneous index direction (no counterpart in the reference; see
+  // AGX_FIELD_SPECTRA_PLAN in the C header).  SetSpectraPlan once per block ({along, over,
+  // nvar, npair, ids, pairs} as doubles; nvar == 0 frees the block's spectra); the time loop
+  // calls SampleSpectra(dt) at the place of SampleStatistics -- two kernels per planned block,
+  // no synchronisation, no copy.  Spectra hands out values[spectrum][bin][mode], dimensional;
+  // SpectraPayload / SetSpectraPayload carry an average into another run
+  // (8 + nvar + 2 npair + (nvar + npair) bins modes doubles).
+  void SetSpectraPlan(int block, const double *plan) {
+    Check(AGX_SYM(field_upload)(ctx_, block, AGX_FIELD_SPECTRA_PLAN, plan),
+          "hotPath::SetSpectraPlan");
+    if (block >= static_cast<int>(spectraPlanned_.size()))
+      spectraPlanned_.resize(block + 1, false);
+    spectraPlanned_[block] = plan[2] != 0.0;
+  }
+  void SampleSpectra(double w) {
+    for (int b = 0; b < static_cast<int>(spectraPlanned_.size()); ++b)
+      if (spectraPlanned_[b])
+        Check(AGX_SYM(field_upload)(ctx_, b, AGX_FIELD_SPECTRA_SAMPLE, &w),
+              "hotPath::SampleSpectra");
+  }
+  void Spectra(int block, double *values) const {
+    Check(AGX_SYM(field_download)(ctx_, block, AGX_FIELD_SPECTRA_VALUES, values),
+          "hotPath::Spectra");
+  }
+  void SpectraPayload(int block, double *payload) const {
+    Check(AGX_SYM(field_download)(ctx_, block, AGX_FIELD_SPECTRA_ACCUM, payload),
+          "hotPath::SpectraPayload");
+  }
+  void SetSpectraPayload(int block, const double *payload) {
+    Check(AGX_SYM(field_upload)(ctx_, block, AGX_FIELD_SPECTRA_ACCUM, payload),
+          "hotPath::SetSpectraPayload");
+  }
+  void ClearSpectra() {
+    const double none[4] = {0.0, 0.0, 0.0, 0.0};
+    for (int b = 0; b < static_cast<int>(spectraPlanned_.size()); ++b)
+      if (spectraPlanned_[b]) SetSpectraPlan(b, none);
   }
   // WriteRestart (output.cpp:651-752): the block's payload, numEqns + 1 values per cell;
   // secondSolution: consVarsNm1 (multilevel time integration)
