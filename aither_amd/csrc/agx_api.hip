@@ -831,6 +831,16 @@ bool use_d2(const agx_ctx* c) {
          c->cfg.inv_flux_jacobian == AGX_JACOBIAN_RUSANOV;
 }
 #if AGX_FAST
+// what the D2 kernels take of a block (k_lusgs_kp, k_matrix_resid_d2m)
+KpBlk kp_blk_of(const BlockDev& b) {
+  KpBlk kb;
+  kb.base = b.d2.base; kb.dstart = b.d2.dstart; kb.surf = b.surf;
+  kb.nd2 = b.d2.nd2; kb.ps = b.d2.ps; kb.Pi = b.d2.Pi; kb.Pj = b.d2.Pj;
+  kb.ni = b.ni; kb.nj = b.nj; kb.nk = b.nk; kb.ng = b.ng;
+  kb.nsurf = b.nsurf; kb.nsurf_i = b.nsurf_i; kb.nsurf_j = b.nsurf_j; kb.nsurf_k = b.nsurf_k;
+  for (int q = 0; q < 6; ++q) kb.side_conn[q] = b.side_conn[q];
+  return kb;
+}
 // One LU-SGS half sweep over a block, one launch: a workgroup per k-plane marches
 // the plane's diagonals, the planes follow each other one step apart (k_lusgs_kp).
 template <bool FWD, bool FULL, bool CONN, int CH>
@@ -872,12 +882,7 @@ int lusgs_kp_launch(agx_ctx* c, Block& blk) {
       per_cu < 1)
     per_cu = 1;
   const int wgs = std::min(per_cu * c->num_cu, b.nk);
-  KpBlk kb;
-  kb.base = b.d2.base; kb.dstart = b.d2.dstart; kb.surf = b.surf;
-  kb.nd2 = b.d2.nd2; kb.ps = b.d2.ps; kb.Pi = b.d2.Pi; kb.Pj = b.d2.Pj;
-  kb.ni = b.ni; kb.nj = b.nj; kb.nk = b.nk; kb.ng = b.ng;
-  kb.nsurf = b.nsurf; kb.nsurf_i = b.nsurf_i; kb.nsurf_j = b.nsurf_j; kb.nsurf_k = b.nsurf_k;
-  for (int q = 0; q < 6; ++q) kb.side_conn[q] = b.side_conn[q];
+  const KpBlk kb = kp_blk_of(b);
   const KpGas kg{c->gas.hf, c->gas.n, c->gas.inv_n};
   hipLaunchKernelGGL((k_lusgs_kp<FWD, FULL, CONN, CH>), dim3(wgs), dim3(256), lds, c->stream,
                      kb, kg, c->sp.viscous, nsl, kp);
@@ -2175,14 +2180,16 @@ int agx_conn_create(agx_ctx* c, const agx_connection* cc, int* conn_id) {
   return 0;
 }
 
-// workgroups of k_matrix_resid_d2: 8 XCDs x mresid_split bands x chunks per band x nk
+// workgroups of k_matrix_resid_d2m: (patch, k-chunk) pairs as agx_mresid_plan.hpp deals them;
+// of k_matrix_resid_d2: 8 XCDs x mresid_split bands x chunks per band x nk
 #ifndef AGX_MRESID_KC
 #define AGX_MRESID_KC 32
 #endif
 constexpr int MRESID_KC = AGX_MRESID_KC;   // planes a workgroup of k_matrix_resid_d2m marches
 long mresid_wgs(const agx_ctx* c, const BlockDev& b) {
+  if (c->mresid_march)
+    return mrp_wgs(mrp_patches(MrpPlane{b.d2.Pi, b.d2.Pj, b.ng}), b.nk, MRESID_KC);
   const long nchunk = ((long)b.d2.Pi * b.d2.Pj + 255) / 256;
-  if (c->mresid_march) return 8L * ((nchunk + 7) / 8) * ((b.nk + MRESID_KC - 1) / MRESID_KC);
   const long bands = 8L * c->mresid_split;
   return bands * ((nchunk + bands - 1) / bands) * b.nk;
 }
@@ -4444,10 +4451,16 @@ int agx_phase_matrix_residual(agx_ctx* c, double* mr) {
       if (b.d2.base && !c->mres_plane_form) {
         // (position chunk, k) pairs dealt to the XCDs band by band, see the kernels
         const long nwg = mresid_wgs(c, b);
-        if (c->mresid_march)
-          hipLaunchKernelGGL(k_matrix_resid_d2m, dim3((unsigned)nwg), dim3(256), 0, c->stream, b,
-                             c->gas, c->sp, MRESID_KC, c->partials.get());
-        else
+        if (c->mresid_march) {
+          const int per = mrp_per_xcd(mrp_patches(MrpPlane{b.d2.Pi, b.d2.Pj, b.ng}));
+          if (MR_LDS_BYTES > 48 * 1024)
+            HIPCHK(hipFuncSetAttribute(reinterpret_cast<const void*>(&k_matrix_resid_d2m),
+                                       hipFuncAttributeMaxDynamicSharedMemorySize,
+                                       (int)MR_LDS_BYTES));
+          hipLaunchKernelGGL(k_matrix_resid_d2m, dim3((unsigned)nwg), dim3(MRP_THREADS),
+                             MR_LDS_BYTES, c->stream, kp_blk_of(b), KpGas{c->gas.hf, c->gas.n, c->gas.inv_n},
+                             c->sp.viscous, per, MRESID_KC, c->partials.get());
+        } else
           hipLaunchKernelGGL(k_matrix_resid_d2, dim3((unsigned)nwg), dim3(256), 0, c->stream, b,
                              c->gas, c->sp, c->mresid_split, c->partials.get());
         if (reduce_norms(c, n, nwg, out + n)) return 1;

@@ -39,6 +39,7 @@
 //     kernel reads x through the same tile transposition.
 #pragma once
 #include "agx_device.hpp"
+#include "agx_mresid_plan.hpp"
 
 namespace agx {
 

@@ -793,97 +793,208 @@ k_matrix_resid_d2(BlockDev b, GasDev g, SolverDev sp, int nsplit, NormPartial* p
 }
 
 // ---------------------------------------------------------------------------
-// The same reduction MARCHING along k: a thread keeps state + c, x and the viscous factor of
-// ITS plane position for the planes k-1, k, k+1 in registers (and the k-face statics of
-// k and k+1), so the two k-neighbours -- in the form above two more reads of S and X per
-// cell, 8.6 GB moved for 4.7 GB algorithmic at 256^3 -- cost nothing; only the four
-// in-plane neighbours come from the arrays (rows of the adjacent diagonals, which the
-// neighbouring chunks of the same XCD band are reading as their own at the same time).
-// Grid: (position chunk, k-chunk) pairs, a contiguous band of chunks per XCD.
-#ifndef AGX_MR_WAVES
-#define AGX_MR_WAVES 1
-#endif
-__global__ void __launch_bounds__(256, AGX_MR_WAVES)
-k_matrix_resid_d2m(BlockDev b, GasDev g, SolverDev sp, int kc, NormPartial* partials) {
-  const D2Dev& z = b.d2;
-  const int nchunk = (z.Pi * z.Pj + 255) / 256;
-  const int per = (nchunk + 7) / 8;                 // chunks per XCD band
-  const int xcd = blockIdx.x % 8, m = blockIdx.x / 8;
-  const int chunk = xcd * per + m % per, kch = m / per;
-  const int k0 = kch * kc, k1 = min(k0 + kc, b.nk);
-  const int t = chunk * 256 + threadIdx.x;
-  const bool visc = sp.viscous != 0;
+// The same reduction MARCHING along k, a PATCH of diagonals per workgroup
+// (agx_mresid_plan.hpp): MRP_W runs of MRP_L positions on consecutive diagonals, aligned on
+// je, so that a cell's in-plane neighbours are the same and the adjacent column of the rows
+// below and above.  Per k-step a thread forms the RECORD of its cell (kp_build_rec: what a
+// neighbour needs of it whatever the face) ONCE and publishes it in LDS with its lower i-
+// and j-face statics; the first MRP_EXTRAS threads do the same for the patch's rim (the
+// diagonal below the first, the one above the last, the position beyond either end of a
+// run), read from the arrays.  After one barrier the four in-plane terms take their records
+// from the slots.  Against a chunk of positions per workgroup, where each thread read its
+// four neighbours from the arrays and built their records itself: a row of the arrays is
+// fetched once per patch and not once per chunk of every adjacent diagonal, and a step
+// builds one record per cell instead of six.
+// The k-neighbours stay in registers: the record of plane k+1 is built from the column
+// loaded a step ahead and is the one published in the next step; the term of plane k-1 is
+// formed a step early, when that plane's record is in hand (tk), and added in its place.
+// Ghost positions of the first layer are published like cells where their side has a
+// connection surface.  Per cell the same helpers on the same doubles, the terms added in the
+// order of k_matrix_resid_d2.  Grid: (patch, k-chunk) pairs, a contiguous range of patches
+// per XCD.  LDS: MR_LDS_BYTES, dynamic (two workgroups per CU).
+constexpr int MR_REC_PAIRS = (KP_NV - 1) / 2;     // a record: 9 pairs and the viscous factor
+static_assert(KP_NV == 2 * MR_REC_PAIRS + 1 && MRP_SLOTS % 2 == 0, "record layout in LDS");
+constexpr size_t MR_LDS_BYTES =
+    (size_t)MRP_SLOTS * KP_NV * sizeof(double) + (size_t)MRP_FACE_SLOTS * 5 * sizeof(double2);
+__global__ void __launch_bounds__(MRP_THREADS, 2)
+k_matrix_resid_d2m(KpBlk b, KpGas g, int viscous, int per, int kc, NormPartial* partials) {
+  const KpBlk& z = b;
+  extern __shared__ double2 mr_lds[];
+  // records: MR_REC_PAIRS arrays of pairs, then the viscous factors; faces: i (nx,ny)
+  // (nz,|A|), j the same, (|A|/dist of i, of j)
+  double2* const sr = mr_lds;
+  double* const svf = reinterpret_cast<double*>(mr_lds + MR_REC_PAIRS * MRP_SLOTS);
+  double2* const sf = reinterpret_cast<double2*>(svf + MRP_SLOTS);
+  const MrpPlane pl{z.Pi, z.Pj, z.ng};
+  const MrpWg wg = mrp_deal((int)blockIdx.x, per);
+  MrpPatch pt;
+  const bool live = mrp_patch(pl, wg.patch, pt);
+  int k0, k1;
+  mrp_kchunk(b.nk, kc, wg.kch, k0, k1);
+  const bool visc = viscous != 0;
+  const int conn = (b.side_conn[0] != 0) | (b.side_conn[1] != 0) << 1 |
+                   (b.side_conn[2] != 0) << 2 | (b.side_conn[3] != 0) << 3;
+  auto wanted = [&](int kind) {
+    return live && (kind == MRP_CELL || (kind > 0 && (conn >> (kind - 1) & 1)));
+  };
+  const int t = threadIdx.x, w = t / MRP_L, l = t % MRP_L;
+  const MrpLoad me = mrp_own(pl, pt, t), ex = mrp_extra(pl, pt, t);
+  const bool pub = wanted(me.kind), active = live && me.kind == MRP_CELL;
+  const bool hasx = wanted(ex.kind);
+  const long q = pub ? mrp_pos(pl, me.de, me.je) : 0;
+  const long qx = hasx ? mrp_pos(pl, ex.de, ex.je) : 0;
+  const int i = me.de - me.je - b.ng, j = me.je - b.ng;
+  const MrpNb nli = mrp_neighbour(pt, w, l, 0), nlj = mrp_neighbour(pt, w, l, 1);
+  const MrpNb nui = mrp_neighbour(pt, w, l, 2), nuj = mrp_neighbour(pt, w, l, 3);
+
+  struct Col { double s[AGX_NEQ], cs, x[AGX_NEQ], vf; };
+  auto ld_col = [&](long p, Col& c) {
+    const double2 s0 = z.ld_pair(PA_S, p), s1 = z.ld_pair(PA_S + 1, p), s2 = z.ld_pair(PA_S + 2, p);
+    const double2 x0 = z.ld_pair(PA_X, p), x1 = z.ld_pair(PA_X + 1, p), x2 = z.ld_pair(PA_X + 2, p);
+    c.s[0] = s0.x; c.s[1] = s0.y; c.s[2] = s1.x; c.s[3] = s1.y; c.s[4] = s2.x; c.cs = s2.y;
+    c.x[0] = x0.x; c.x[1] = x0.y; c.x[2] = x1.x; c.x[3] = x1.y; c.x[4] = x2.x;
+    c.vf = visc ? z.ld_vf(p) : 0.0;
+  };
+  auto rec_of = [&](const Col& c, KpRec& r) { kp_build_rec(g, c.s, c.cs, c.vf, c.x, r); };
+  auto put_rec = [&](int slot, const KpRec& r) {
+    sr[0 * MRP_SLOTS + slot] = make_double2(r.dx[0], r.dx[1]);
+    sr[1 * MRP_SLOTS + slot] = make_double2(r.dx[2], r.dx[3]);
+    sr[2 * MRP_SLOTS + slot] = make_double2(r.dx[4], r.r1);
+    sr[3 * MRP_SLOTS + slot] = make_double2(r.v1[0], r.v1[1]);
+    sr[4 * MRP_SLOTS + slot] = make_double2(r.v1[2], r.p1);
+    sr[5 * MRP_SLOTS + slot] = make_double2(r.h1, r.r0);
+    sr[6 * MRP_SLOTS + slot] = make_double2(r.v0[0], r.v0[1]);
+    sr[7 * MRP_SLOTS + slot] = make_double2(r.v0[2], r.p0);
+    sr[8 * MRP_SLOTS + slot] = make_double2(r.h0, r.cs);
+    svf[slot] = r.vf;
+  };
+  auto get_rec = [&](int slot, KpRec& r) {
+    const double2 a0 = sr[0 * MRP_SLOTS + slot], a1 = sr[1 * MRP_SLOTS + slot];
+    const double2 a2 = sr[2 * MRP_SLOTS + slot], a3 = sr[3 * MRP_SLOTS + slot];
+    const double2 a4 = sr[4 * MRP_SLOTS + slot], a5 = sr[5 * MRP_SLOTS + slot];
+    const double2 a6 = sr[6 * MRP_SLOTS + slot], a7 = sr[7 * MRP_SLOTS + slot];
+    const double2 a8 = sr[8 * MRP_SLOTS + slot];
+    r.dx[0] = a0.x; r.dx[1] = a0.y; r.dx[2] = a1.x; r.dx[3] = a1.y; r.dx[4] = a2.x; r.r1 = a2.y;
+    r.v1[0] = a3.x; r.v1[1] = a3.y; r.v1[2] = a4.x; r.p1 = a4.y; r.h1 = a5.x; r.r0 = a5.y;
+    r.v0[0] = a6.x; r.v0[1] = a6.y; r.v0[2] = a7.x; r.p0 = a7.y; r.h0 = a8.x; r.cs = a8.y;
+    r.vf = svf[slot];
+  };
+  auto put_faces = [&](int fslot, const KpFace& fi, const KpFace& fj) {
+    sf[0 * MRP_FACE_SLOTS + fslot] = make_double2(fi.n[0], fi.n[1]);
+    sf[1 * MRP_FACE_SLOTS + fslot] = make_double2(fi.n[2], fi.a);
+    sf[2 * MRP_FACE_SLOTS + fslot] = make_double2(fj.n[0], fj.n[1]);
+    sf[3 * MRP_FACE_SLOTS + fslot] = make_double2(fj.n[2], fj.a);
+    sf[4 * MRP_FACE_SLOTS + fslot] = make_double2(fi.ad, fj.ad);
+  };
+  auto get_face = [&](int fslot, int d, KpFace& f) {
+    const double2 t0 = sf[(2 * d) * MRP_FACE_SLOTS + fslot];
+    const double2 t1 = sf[(2 * d + 1) * MRP_FACE_SLOTS + fslot];
+    const double2 ad = sf[4 * MRP_FACE_SLOTS + fslot];
+    f.n[0] = t0.x; f.n[1] = t0.y; f.n[2] = t1.x; f.a = t1.y;
+    f.ad = d == 0 ? ad.x : ad.y;
+  };
+  auto term = [&](const KpRec& r, const KpFace& f, bool lower, double* acc) {
+    kp_term(r, f.n, f.a, f.ad, visc, lower, acc);
+  };
+
   double l2[AGX_NEQ] = {0, 0, 0, 0, 0};
-  bool active = false;
-  int i = 0, j = 0, je = 0, de = 0;
-  if (chunk < nchunk && t < z.Pi * z.Pj) {
-    const int ij = z.ij_of_pos[t];
-    const int ie = ij & 0xffff;
-    je = ij >> 16;
-    i = ie - b.ng; j = je - b.ng; de = ie + je;
-    active = i >= 0 && i < b.ni && j >= 0 && j < b.nj;
+  double tk[AGX_NEQ] = {0, 0, 0, 0, 0};             // the term of plane k-1, formed a step early
+  KpRec r0 = {}, rp = {};
+  Col cp = {};
+  long own = (long)(k0 + b.ng) * z.ps + q;
+  if (pub) {
+    ld_col(own, cp);
+    rec_of(cp, r0);
   }
-  if (active) {
-    // plane-relative positions of the in-plane neighbours (ie -+ 1, je); (ie, je -+ 1) sit
-    // one position below / above them
-    const long qlo = z.dstart[de - 1] - z.jlo(de - 1) + je;
-    const long qup = z.dstart[de + 1] - z.jlo(de + 1) + je;
-    struct Col { double s[AGX_NEQ], cs, x[AGX_NEQ], vf; };
-    auto ld_col = [&](long p, Col& c) {
-      const double2 s0 = z.ld_pair(PA_S, p), s1 = z.ld_pair(PA_S + 1, p), s2 = z.ld_pair(PA_S + 2, p);
-      const double2 x0 = z.ld_pair(PA_X, p), x1 = z.ld_pair(PA_X + 1, p), x2 = z.ld_pair(PA_X + 2, p);
-      c.s[0] = s0.x; c.s[1] = s0.y; c.s[2] = s1.x; c.s[3] = s1.y; c.s[4] = s2.x; c.cs = s2.y;
-      c.x[0] = x0.x; c.x[1] = x0.y; c.x[2] = x1.x; c.x[3] = x1.y; c.x[4] = x2.x;
-      c.vf = visc ? z.ld_vf(p) : 0.0;
-    };
-    auto col_term = [&](const Col& c, const KpFace& f, bool lower, double* acc) {
-      KpRec r;
-      kp_build_rec(g, c.s, c.cs, c.vf, c.x, r);
-      kp_term(r, f.n, f.a, f.ad, visc, lower, acc);
-    };
-    Col cm, c0, cp;
-    KpFace fk0, fk1;
-    long own = (long)(k0 + b.ng) * z.ps + t;
-    ld_col(own - z.ps, cm);
-    ld_col(own, c0);
+  if (active && (k0 > 0 || bc_is_connection(b, i, j, k0, 5))) {
+    KpFace fk0;
     kp_load_face(z, 2, own, visc, fk0);
-    for (int k = k0; k < k1; ++k, own += z.ps) {
-      const long kbase = own - t;
-      ld_col(own + z.ps, cp);                       // plane k+1 (a ghost plane at the top)
+    ld_col(own - z.ps, cp);
+    rec_of(cp, rp);
+    term(rp, fk0, true, tk);
+  }
+  // every thread of the workgroup takes every step: the barriers are not branched around
+  for (int k = k0; k < k1; ++k, own += z.ps) {
+    const long kbase = (long)(k + b.ng) * z.ps;
+    KpFace fi = {}, fj = {}, fk1 = {};
+    double2 b0 = {}, b1 = {}, b2 = {};
+    // what the barrier waits for: the own in-plane face statics and the rim ...
+    if (pub) {
+      kp_load_face(z, 0, own, visc, fi);
+      kp_load_face(z, 1, own, visc, fj);
+    }
+    Col cx = {};
+    KpFace xi = {}, xj = {};
+    if (hasx) {
+      ld_col(kbase + qx, cx);
+      if (ex.fslot >= 0) {
+        kp_load_face(z, 0, kbase + qx, visc, xi);
+        kp_load_face(z, 1, kbase + qx, visc, xj);
+      }
+    }
+    // ... and what is wanted only after it
+    if (pub) ld_col(own + z.ps, cp);                // plane k+1 (a ghost plane at the top)
+    if (active) {
       kp_load_face(z, 2, own + z.ps, visc, fk1);
-      const double2 b0 = z.pa(PA_B)[own], b1 = z.pa(PA_B + 1)[own], b2 = z.pa(PA_B + 2)[own];
-      double acc[AGX_NEQ] = {0, 0, 0, 0, 0};
+      b0 = z.ld_pair(PA_B, own); b1 = z.ld_pair(PA_B + 1, own); b2 = z.ld_pair(PA_B + 2, own);
+    }
+    if (pub) {
+      put_rec(me.slot, r0);
+      if (me.fslot >= 0) put_faces(me.fslot, fi, fj);
+    }
+    if (hasx) {
+      KpRec rx;
+      rec_of(cx, rx);
+      put_rec(ex.slot, rx);
+      if (ex.fslot >= 0) put_faces(ex.fslot, xi, xj);
+    }
+    __syncthreads();
+    double acc[AGX_NEQ] = {0, 0, 0, 0, 0};
+    if (active) {
+      KpRec rn;
       KpFace ff;
       // the order of k_matrix_resid_d2: lower i, j, k, then upper i, j, k
       if (i > 0 || bc_is_connection(b, i, j, k, 1)) {
-        kp_load_face(z, 0, own, visc, ff);
-        kp_term_mem(z, g, visc, kbase + qlo, ff, true, acc);
+        get_rec(nli.slot, rn);
+        term(rn, fi, true, acc);
       }
       if (j > 0 || bc_is_connection(b, i, j, k, 3)) {
-        kp_load_face(z, 1, own, visc, ff);
-        kp_term_mem(z, g, visc, kbase + qlo - 1, ff, true, acc);
+        get_rec(nlj.slot, rn);
+        term(rn, fj, true, acc);
       }
-      if (k > 0 || bc_is_connection(b, i, j, k, 5)) col_term(cm, fk0, true, acc);
+#pragma unroll
+      for (int e = 0; e < AGX_NEQ; ++e) acc[e] += tk[e];
       if (i < b.ni - 1 || bc_is_connection(b, i + 1, j, k, 2)) {
-        kp_load_face(z, 0, kbase + qup, visc, ff);
-        kp_term_mem(z, g, visc, kbase + qup, ff, false, acc);
+        get_rec(nui.slot, rn);
+        get_face(nui.fslot, 0, ff);
+        term(rn, ff, false, acc);
       }
       if (j < b.nj - 1 || bc_is_connection(b, i, j + 1, k, 4)) {
-        kp_load_face(z, 1, kbase + qup + 1, visc, ff);
-        kp_term_mem(z, g, visc, kbase + qup + 1, ff, false, acc);
+        get_rec(nuj.slot, rn);
+        get_face(nuj.fslot, 1, ff);
+        term(rn, ff, false, acc);
       }
-      if (k < b.nk - 1 || bc_is_connection(b, i, j, k + 1, 6)) col_term(cp, fk1, false, acc);
+    }
+    if (pub) rec_of(cp, rp);                        // published in the next step
+    if (active) {
+      if (k < b.nk - 1 || bc_is_connection(b, i, j, k + 1, 6)) term(rp, fk1, false, acc);
       const double a = 1.0 / b2.y;
       const double bv[AGX_NEQ] = {b0.x, b0.y, b1.x, b1.y, b2.x};
 #pragma unroll
       for (int e = 0; e < AGX_NEQ; ++e) {
-        const double r = -(c0.x[e] * a - acc[e] - bv[e]);
+        const double r = -(r0.dx[e] * a - acc[e] - bv[e]);
         l2[e] += r * r;
+        tk[e] = 0.0;
       }
-      cm = c0; c0 = cp; fk0 = fk1;
+      term(r0, fk1, true, tk);                      // this plane as the lower one of k+1
     }
+    __syncthreads();                                // the slots are free for the next plane
+    r0 = rp;
   }
-  norm_block_fold(l2, -1.0e300, 0x7fffffffffffffffLL, partials + blockIdx.x);
+  // (the fold's scratch inside the slot arrays, which no thread reads any more)
+  norm_block_fold_in(l2, -1.0e300, 0x7fffffffffffffffLL, partials + blockIdx.x,
+                     reinterpret_cast<double(*)[16]>(mr_lds),
+                     reinterpret_cast<long long*>(mr_lds + 8 * (AGX_NEQ + 1)));
 }
 
 // ---------------------------------------------------------------------------
