@@ -11,6 +11,7 @@
 #include "agx_stats.hpp"
 #include "agx_series.hpp"
 #include "agx_series_ring.hpp"
+#include "agx_out_ranges.hpp"
 #include "agx_spectra.hpp"
 #include "agx_flux.hpp"
 #include "agx_mem.hpp"
@@ -349,14 +350,6 @@ struct agx_ctx : agx::Switches {
 static int my_side(const agx_ctx* c, const Conn& k);
 static int implicit_begin(agx_ctx* c, int write_x);
 static int halo_exchange_remote(agx_ctx* c, int what);
-static int stats_field_upload(agx_ctx* c, int id, int field, const double* in);
-static int stats_field_download(agx_ctx* c, int id, int field, double* out);
-static int stats_pack(agx_ctx* c, int id, bool wall, int nvar, const int32_t* vars, double* out);
-static int stats_collapse(agx_ctx* c, int id, int nvar, const int32_t* vars, double* out);
-static int series_field_upload(agx_ctx* c, int id, int field, const double* in);
-static int series_field_download(agx_ctx* c, int id, int field, double* out);
-static int spectra_field_upload(agx_ctx* c, int id, int field, const double* in);
-static int spectra_field_download(agx_ctx* c, int id, int field, double* out);
 #if AGX_FAST
 static int d2_prepare(agx_ctx* c, Block& blk, int write_x, int again, int norms);
 #endif
@@ -701,6 +694,10 @@ TilePlan tile_plan_of(agx_ctx* c, int gx, int gy, int nk, int P, int charge, int
     it = c->tile_plans.emplace(key, tile_plan_make(gx, gy, nk, P, charge, order)).first;
   return it->second;
 }
+// the cells the configured reconstruction reaches across a face
+int recon_reach(const agx_ctx* c) {
+  return c->cfg.recon == AGX_RECON_CONSTANT ? 1 : c->cfg.recon == AGX_RECON_MUSCL ? 2 : 3;
+}
 MarchPlan march_plan(agx_ctx* c, const BlockDev& b) {
   MarchPlan p;
   const int gx = tile_count(b.ni, TILE_INV_I), gy = tile_count(b.nj, g_march_tj);
@@ -714,8 +711,8 @@ MarchPlan march_plan(agx_ctx* c, const BlockDev& b) {
     p.kchunk = 0;
     p.grid = dim3((unsigned)np);
     p.nparts = np;
-    const int halo = c->cfg.recon == AGX_RECON_CONSTANT ? 1 : (c->cfg.recon == AGX_RECON_MUSCL ? 2 : 3);
-    p.tile = tile_plan_of(c, gx, gy, b.nk, (int)np, tile_charge_inviscid(halo), c->tile_order_inv);
+    p.tile = tile_plan_of(c, gx, gy, b.nk, (int)np, tile_charge_inviscid(recon_reach(c)),
+                          c->tile_order_inv);
     return p;
   }
   // aim at >= ~2048 workgroups so that all 256 CUs stay busy to the end
@@ -2535,76 +2532,6 @@ static int ghosts_for_output(agx_ctx* c, const char* who) {
   return ghosts_for_output_inviscid(c, who) || ghosts_for_output_viscous(c);
 }
 
-int agx_field_download(agx_ctx* c, int id, int field, double* out) {
-  if (flush_consn(c)) return 1;
-  if (id < 0 || id >= (int)c->blocks.size()) return fail("bad block id %d", id);
-  if (field == AGX_FIELD_STAT_SAMPLE || field == AGX_FIELD_STAT_ACCUM)
-    return stats_field_download(c, id, field, out);
-  if (field >= AGX_FIELD_SERIES_PLAN && field <= AGX_FIELD_SERIES_LOCATE)
-    return series_field_download(c, id, field, out);
-  if (field >= AGX_FIELD_SPECTRA_PLAN && field <= AGX_FIELD_SPECTRA_VALUES)
-    return spectra_field_download(c, id, field, out);
-  Block& b = c->blocks[id];
-  // (the D2 arrays hold x with the writer's tag in its two lowest mantissa bits: while the
-  // planes are current -- an upload or a multigrid transfer wrote them last -- they are the
-  // untagged x itself, zero ghost cells of a restriction included)
-  if (field == AGX_FIELD_UPDATE && b.x_is_zero) {
-    const int g = b.d.ng;
-    memset(out, 0, sizeof(double) * AGX_NEQ * (size_t)(b.d.ni + 2 * g) * (b.d.nj + 2 * g) *
-                       (b.d.nk + 2 * g));
-    return 0;
-  }
-  if (field == AGX_FIELD_UPDATE && b.d.d2.base && !b.x_planes_current && d2_x_copy(c, b, 0))
-    return 1;
-  // (k_lusgs_prepare forms the diagonal inside the D2 arrays, as 1 / a beside x: the plane
-  // d.a keeps the spectral radii the residual summed, without the time term)
-  if (field == AGX_FIELD_DIAGONAL && b.d.d2.base)
-    return fail("agx_field_download: the diagonal-ordered LU-SGS path keeps the scalar diagonal "
-                "a_ only as 1 / a inside its sweep arrays, not as a field (AGX_LUSGS=plane, the "
-                "hyperplane form, keeps it)");
-  if (field >= AGX_FIELD_VEL_GRAD && field <= AGX_FIELD_PRESS_GRAD) {
-    // cell-centre gradients: formed on demand into a temporary (an output path)
-    const long ncell = (long)b.d.ni * b.d.nj * b.d.nk;
-    double* tmp = nullptr;
-    if (ghosts_for_output(c, "agx_field_download")) return 1;
-    if (stage_buffer(c, (size_t)3 * NGF * ncell, &tmp)) return 1;
-    hipLaunchKernelGGL(k_cell_grads, cell_grid(b.d, CELL_BLOCK), CELL_BLOCK, 0, c->stream, b.d,
-                       c->gas, tmp);
-    HIPCHK(hipGetLastError());
-    const int off = field == AGX_FIELD_VEL_GRAD ? 0 : 9 + 3 * (field - AGX_FIELD_TEMP_GRAD);
-    const int nc = field == AGX_FIELD_VEL_GRAD ? 9 : 3;
-    // strided device -> host copy of the requested columns
-    HIPCHK(hipMemcpy2DAsync(out, sizeof(double) * nc, tmp + off, sizeof(double) * 3 * NGF,
-                            sizeof(double) * nc, ncell, hipMemcpyDeviceToHost, c->stream));
-    HIPCHK(hipStreamSynchronize(c->stream));
-    return 0;
-  }
-  if (field == AGX_FIELD_TEMPERATURE || field == AGX_FIELD_VISCOSITY) {
-    // formed on demand from the current state into a scratch plane (the x_old
-    // plane of DPLUR: rebuilt at the start of every implicit iteration)
-    if (field == AGX_FIELD_VISCOSITY && !c->sp.viscous)
-      return fail("viscosity_ is only kept for viscous runs (procBlock.cpp:6171)");
-    double* scratch = b.d.xold[0];
-    hipLaunchKernelGGL(k_aux_field, dim3((b.d.nplane + 255) / 256), dim3(256), 0, c->stream,
-                       b.d, c->gas, field == AGX_FIELD_VISCOSITY ? 1 : 0, scratch);
-    HIPCHK(hipGetLastError());
-    double* one[1] = {scratch};
-    const int g = b.d.ng;
-    return download_aos(c, b, out, one, 1, b.d.ni + 2 * g, b.d.nj + 2 * g, b.d.nk + 2 * g, g);
-  }
-  double* const* p; int nc, gh;
-  if (!geom_field_info(b, field, &p, &nc, &gh)) {      // (gh: the face direction here)
-    if (b.node_built && !c->finalized)
-      return fail("the geometry of a node-built block is complete after agx_setup_finalize");
-    const int g = b.d.ng;
-    return download_aos(c, b, out, p, nc, b.d.ni + 2 * g + (gh == 0), b.d.nj + 2 * g + (gh == 1),
-                        b.d.nk + 2 * g + (gh == 2), g);
-  }
-  if (field_info(b, field, &p, &nc, &gh))
-    return fail("unknown field %d", field);
-  const int g = gh ? b.d.ng : 0;
-  return download_aos(c, b, out, p, nc, b.d.ni + 2 * g, b.d.nj + 2 * g, b.d.nk + 2 * g, g);
-}
 // ---- output: WriteFunFile / WriteRestart payloads packed on the device ------
 namespace {
 OutSpec out_spec(const agx_ctx* c, const Block& b, int nvar = 0, const int32_t* vars = nullptr) {
@@ -2619,6 +2546,49 @@ OutSpec out_spec(const agx_ctx* c, const Block& b, int nvar = 0, const int32_t* 
   sp.global_pos = b.global_pos;
   return sp;
 }
+// ---- what the output and sampling paths share, each stated once; a caller keeps its message
+// the flags of wall_face_vars: bit 0 the fourth-order viscous reconstruction, bit 1 a
+// largeEddySimulation run (the iteration path passes bit 0 alone)
+int wall_eval_flags(const agx_ctx* c) {
+  return (c->cfg.viscous_recon == AGX_VISC_RECON_CENTRAL_4TH ? 1 : 0) | (c->sp.les ? 2 : 0);
+}
+// wall-law surfaces take their wall data from a residual; field: the caller's, if it names one
+int wall_data_missing(const agx_ctx* c, const Block& b, const char* call, const char* field = "") {
+  if (!b.d.wallv || c->have_wall_data) return 0;
+  return fail("%s: %s%sthe wall-law surfaces hold no wall data before the first residual", call,
+              field, *field ? ": " : "");
+}
+// plan: the field that uploads the plan of the series or of the spectra
+int no_plan(const char* call, const char* field, int id, const char* plan) {
+  return fail("%s: %s: block %d has no plan (upload %s first)", call, field, id, plan);
+}
+int no_statistics(const char* who, int id) {
+  return fail("%s: block %d has no statistics: no sample has been taken (AGX_FIELD_STAT_SAMPLE)",
+              who, id);
+}
+// what a 5-equation library keeps, a predicate per kind of id (it has no tke, sdr, f1, f2):
+// cell ids AGX_OUT_*, wall ids AGX_WALL_*, n of AGX_STAT_BASE + n, and q of AGX_FLUX_BASE + q
+// or AGX_BUDGET_BASE + q (1 + e and 8 + e carry equation e)
+bool kept_cell_id(int var) {
+  return AGX_NEQ != 5 || !(var == AGX_OUT_TKE || var == AGX_OUT_SDR || var == AGX_OUT_F1 ||
+                           var == AGX_OUT_F2 || (var >= AGX_OUT_TKEGRAD && var < AGX_OUT_RESID) ||
+                           var >= AGX_OUT_RESID + 5);
+}
+bool kept_wall_id(int var) {
+  return AGX_NEQ != 5 || !(var == AGX_WALL_TKE || var == AGX_WALL_SDR);
+}
+bool kept_stat_index(int n) { return AGX_NEQ != 5 || !(n == 10 || n == 11); }
+bool kept_flux_equation(int q) { return AGX_NEQ != 5 || !(q > 0 && (q - 1) % FLUX_NE >= AGX_NEQ); }
+// entry `at` of a field payload as an integer in [lo, hi]; refuses by name, saying which entry
+int payload_entry(const char* field, const double* in, long at, const char* what, double lo,
+                  double hi, long* out) {
+  const double x = in[at];
+  if (!std::isfinite(x) || x != std::floor(x) || x < lo || x > hi)
+    return fail("agx_field_upload: %s: entry %ld (%s) is %g: an integer from %.0f to %.0f is "
+                "expected", field, at, what, x, lo, hi);
+  *out = (long)x;
+  return 0;
+}
 // WriteWallFun's payload of one block (the ids are wall ids, nvar is in their range)
 int wall_pack(agx_ctx* c, int id, int nvar, const int32_t* vars, double* out) {
   Block& b = c->blocks[id];
@@ -2628,19 +2598,14 @@ int wall_pack(agx_ctx* c, int id, int nvar, const int32_t* vars, double* out) {
   if (b.wall_tab.empty())
     return fail("agx_output_pack: block %d has no viscousWall surface", id);
   if (!c->finalized) return fail("agx_setup_finalize has not been called");
-  if (b.d.wallv && !c->have_wall_data)
-    return fail("agx_output_pack: the wall-law surfaces hold no wall data before the first "
-                "residual");
+  if (wall_data_missing(c, b, "agx_output_pack")) return 1;
   const long total = b.wall_faces;
   double* tmp = nullptr;
   if (stage_buffer(c, (size_t)nvar * total, &tmp)) return 1;
   if (ghosts_for_output(c, "agx_output_pack")) return 1;
-  // (bit 1: a largeEddySimulation run, wall_face_vars)
-  const int fourth = (c->cfg.viscous_recon == AGX_VISC_RECON_CENTRAL_4TH ? 1 : 0) |
-                     (c->sp.les ? 2 : 0);
   hipLaunchKernelGGL(k_wall_pack, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, c->stream,
                      b.d, c->gas, out_spec(c, b, nvar, vars), b.wall_tab_dev.get(),
-                     (int)b.wall_tab.size(), total, fourth, tmp);
+                     (int)b.wall_tab.size(), total, wall_eval_flags(c), tmp);
   return copy_out(c, out, tmp, (size_t)nvar * total);
 }
 // The integrated wall loads of one block's load surfaces (the ids are load ids, nvar is in
@@ -2651,9 +2616,7 @@ int wall_loads(agx_ctx* c, int id, int nvar, const int32_t* vars, double* out) {
     return fail("agx_output_pack: block %d has no viscousWall or slipWall surface", id);
   if (!c->finalized) return fail("agx_setup_finalize has not been called");
   const bool viscous = c->cfg.is_viscous != 0;
-  if (viscous && b.d.wallv && !c->have_wall_data)
-    return fail("agx_output_pack: the wall-law surfaces hold no wall data before the first "
-                "residual");
+  if (viscous && wall_data_missing(c, b, "agx_output_pack")) return 1;
   if (!b.load_fcen)
     for (int v = 0; v < nvar; ++v)
       if (vars[v] >= AGX_LOAD_PRESSURE_MOMENT_X) {
@@ -2671,11 +2634,9 @@ int wall_loads(agx_ctx* c, int id, int nvar, const int32_t* vars, double* out) {
   // a viscous context evaluates its viscousWall faces with the ghost cells the next residual
   // would see; an inviscid one reads physical cells only
   if (viscous && ghosts_for_output(c, "agx_output_pack")) return 1;
-  const int fourth = (c->cfg.viscous_recon == AGX_VISC_RECON_CENTRAL_4TH ? 1 : 0) |
-                     (c->sp.les ? 2 : 0);
   hipLaunchKernelGGL(k_wall_loads, dim3((unsigned)b.load_chunks), dim3(LOAD_CHUNK), 0, c->stream,
                      b.d, c->gas, b.load_tab_dev.get(), nsurf, b.load_faces, viscous ? 1 : 0,
-                     fourth, b.load_fcen.get(), b.load_partial.get());
+                     wall_eval_flags(c), b.load_fcen.get(), b.load_partial.get());
   hipLaunchKernelGGL(k_wall_loads_sum, dim3((unsigned)((nvar * nsurf + 63) / 64)), dim3(64), 0,
                      c->stream, out_spec(c, b, nvar, vars), b.load_tab_dev.get(), nsurf,
                      b.load_chunks, 1.0 / c->gas.scaling, b.load_partial.get(), tmp);
@@ -2734,7 +2695,7 @@ int flux_table(agx_ctx* c, int id) {
 }
 // equations 5 and 6 (rho k, rho omega) of the flux and budget ranges in a 5-equation library
 int flux_eq_refused(const char* range, int q, int var) {
-  return AGX_NEQ == 5 && q > 0 && (q - 1) % FLUX_NE >= AGX_NEQ
+  return !kept_flux_equation(q)
              ? fail("agx_output_pack: %s variable %d (tke, sdr) is not kept by the 5-equation "
                     "libraries", range, var)
              : 0;
@@ -2751,10 +2712,8 @@ int surface_fluxes(agx_ctx* c, int id, int nvar, const int32_t* vars, double* ou
     return fail("agx_output_pack: block %d has no flux surface (every surface it has is a "
                 "connection to another rank)", id);
   const bool viscous = c->cfg.is_viscous != 0;
-  if (viscous && b.d.wallv && !c->have_wall_data)
-    return fail("agx_output_pack: the wall-law surfaces hold no wall data before the first "
-                "residual");
-  const int halo = c->cfg.recon == AGX_RECON_CONSTANT ? 1 : c->cfg.recon == AGX_RECON_MUSCL ? 2 : 3;
+  if (viscous && wall_data_missing(c, b, "agx_output_pack")) return 1;
+  const int halo = recon_reach(c);
   if (halo > b.d.ng)
     return fail("agx_output_pack: flux variables: the reconstruction reaches %d cells across a "
                 "face, the blocks have %d ghost layers", halo, b.d.ng);
@@ -2785,12 +2744,9 @@ int surface_fluxes(agx_ctx* c, int id, int nvar, const int32_t* vars, double* ou
           launch(std::integral_constant<int, AGX_LIMITER_NONE>{});
       });
   if (ghosts_for_output_viscous(c)) return 1;
-  if (viscous) {
-    const int fourth = (c->cfg.viscous_recon == AGX_VISC_RECON_CENTRAL_4TH ? 1 : 0) |
-                       (c->sp.les ? 2 : 0);
+  if (viscous)
     hipLaunchKernelGGL(k_surface_flux_visc, grid, tb, 0, c->stream, b.d, c->gas,
-                       b.flux_tab_dev.get(), nsurf, fourth, b.flux_partial.get());
-  }
+                       b.flux_tab_dev.get(), nsurf, wall_eval_flags(c), b.flux_partial.get());
   hipLaunchKernelGGL(k_surface_flux_sum, dim3((unsigned)((nvar * nsurf + 63) / 64)), dim3(64), 0,
                      c->stream, out_spec(c, b, nvar, vars), b.flux_tab_dev.get(), nsurf,
                      b.flux_chunks, viscous ? 1 : 0, b.flux_partial.get(), tmp);
@@ -2858,113 +2814,6 @@ int point_pack(agx_ctx* c, int id, bool node, int nvar, const int32_t* vars, dou
 }
 }  // namespace
 
-int agx_output_pack(agx_ctx* c, int id, int nvar, const int32_t* vars, double* out) {
-  if (flush_consn(c)) return 1;
-  if (id < 0 || id >= (int)c->blocks.size()) return fail("bad block id %d", id);
-  if (nvar < 1 || nvar > AGX_OUT_COUNT) return fail("agx_output_pack: nvar %d out of range", nvar);
-  // cell variables, wall variables (WriteWallFun), node variables (WriteNodeFun) or integrated
-  // wall loads, each range with its own bound on nvar
-  int n_wall = 0, n_node = 0, n_load = 0, n_stat = 0, n_wstat = 0, n_cstat = 0;
-  int n_flux = 0, n_budget = 0;
-  for (int v = 0; v < nvar; ++v) {
-    const bool flux = vars[v] >= AGX_FLUX_BASE && vars[v] < AGX_FLUX_END;
-    const bool budget = vars[v] >= AGX_BUDGET_BASE && vars[v] < AGX_BUDGET_END;
-    n_flux += flux;
-    n_budget += budget;
-    if (flux || budget) continue;
-    const bool cell = vars[v] >= 0 && vars[v] < AGX_OUT_COUNT;
-    const bool wall = vars[v] >= AGX_WALL_YPLUS && vars[v] < AGX_WALL_END;
-    const bool node = vars[v] >= AGX_NODE_BASE && vars[v] < AGX_NODE_END;
-    const bool load = vars[v] >= AGX_LOAD_BASE && vars[v] < AGX_LOAD_END;
-    const bool stat = vars[v] >= AGX_STAT_BASE && vars[v] < AGX_STAT_END;
-    const bool wstat = vars[v] >= AGX_WSTAT_BASE && vars[v] < AGX_WSTAT_END;
-    const bool cstat = vars[v] >= AGX_CSTAT_BASE && vars[v] < AGX_CSTAT_END;
-    if (!cell && !wall && !node && !load && !stat && !wstat && !cstat)
-      return fail("unknown output variable %d", vars[v]);
-    n_cstat += cstat;
-    n_wall += wall;
-    n_node += node;
-    n_load += load;
-    n_stat += stat;
-    n_wstat += wstat;
-  }
-  // the boundary fluxes and the block balance (agx_flux.hpp)
-  if (n_flux > 0 || n_budget > 0) {
-    const bool is_flux = n_flux > 0;
-    const int mine = is_flux ? n_flux : n_budget;
-    const char* other = is_flux && n_budget > 0 ? "budget"
-                        : n_cstat > 0 ? "collapsed statistics" : n_wstat > 0 ? "wall statistics"
-                        : n_stat > 0 ? "statistics" : n_load > 0 ? "load" : n_node > 0 ? "node"
-                        : n_wall > 0 ? "wall" : mine != nvar ? "cell" : nullptr;
-    if (other)
-      return fail("agx_output_pack: %s and %s variables in one call (a call holds ids of one "
-                  "range)", other, is_flux ? "flux" : "budget");
-    if (nvar > AGX_FLUX_END - AGX_FLUX_BASE)
-      return fail("agx_output_pack: nvar %d out of range", nvar);
-    return is_flux ? surface_fluxes(c, id, nvar, vars, out) : block_budget(c, id, nvar, vars, out);
-  }
-  // the statistics collapsed along index directions
-  if (n_cstat > 0) {
-    const char* other = n_wstat > 0 ? "wall statistics" : n_stat > 0 ? "statistics"
-                        : n_load > 0 ? "load" : n_node > 0 ? "node" : n_wall > 0 ? "wall"
-                        : n_cstat != nvar ? "cell" : nullptr;
-    if (other)
-      return fail("agx_output_pack: %s and collapsed statistics variables in one call (a call "
-                  "holds ids of one range)", other);
-    if (nvar > AGX_CSTAT_COUNT) return fail("agx_output_pack: nvar %d out of range", nvar);
-    return stats_collapse(c, id, nvar, vars, out);
-  }
-  // the two statistics ranges (cell statistics, wall statistics)
-  if (n_stat > 0 || n_wstat > 0) {
-    const char* mine = n_stat > 0 ? "statistics" : "wall statistics";
-    if (n_stat > 0 && n_wstat > 0)
-      return fail("agx_output_pack: statistics and wall statistics variables in one call (a "
-                  "call holds ids of one range)");
-    const char* other = n_load > 0 ? "load" : n_node > 0 ? "node" : n_wall > 0 ? "wall"
-                        : n_stat + n_wstat != nvar ? "cell" : nullptr;
-    if (other)
-      return fail("agx_output_pack: %s and %s variables in one call (a call holds ids of one "
-                  "range)", other, mine);
-    if (nvar > (n_stat > 0 ? AGX_STAT_END - AGX_STAT_BASE : AGX_WSTAT_END - AGX_WSTAT_BASE))
-      return fail("agx_output_pack: nvar %d out of range", nvar);
-    return stats_pack(c, id, n_wstat > 0, nvar, vars, out);
-  }
-  if (n_load > 0) {
-    if (n_node > 0)
-      return fail("agx_output_pack: node and load variables in one call (a call holds ids of "
-                  "one range)");
-    if (n_wall > 0)
-      return fail("agx_output_pack: wall and load variables in one call (a call holds ids of "
-                  "one range)");
-    if (n_load != nvar)
-      return fail("agx_output_pack: cell and load variables in one call (a call holds ids of "
-                  "one range)");
-    if (nvar > AGX_LOAD_END - AGX_LOAD_BASE)
-      return fail("agx_output_pack: nvar %d out of range", nvar);
-    return wall_loads(c, id, nvar, vars, out);
-  }
-  if (n_node > 0) {
-    if (n_wall > 0)
-      return fail("agx_output_pack: node and wall variables in one call (a function file holds "
-                  "one kind)");
-    if (n_node != nvar)
-      return fail("agx_output_pack: cell and node variables in one call (a function file holds "
-                  "one kind)");
-    int32_t ids[AGX_OUT_COUNT];
-    for (int v = 0; v < nvar; ++v) ids[v] = vars[v] - AGX_NODE_BASE;
-    return point_pack(c, id, true, nvar, ids, out);
-  }
-  if (n_wall > 0) {
-    if (n_wall != nvar)
-      return fail("agx_output_pack: cell and wall variables in one call (a function file holds "
-                  "one kind)");
-    if (nvar > AGX_WALL_END - AGX_WALL_YPLUS)
-      return fail("agx_output_pack: nvar %d out of range", nvar);
-    return wall_pack(c, id, nvar, vars, out);
-  }
-  return point_pack(c, id, false, nvar, vars, out);
-}
-
 // ---- time statistics (agx_stats.hpp; include/aither_gfx950.h at AGX_STAT_BASE) ---------------
 namespace {
 // extras of the sampled cell vector: the eddy viscosity (largeEddySimulation, 7 equations),
@@ -3015,7 +2864,7 @@ int stat_not_kept(bool refused, int var) {
                         "kept by the 5-equation libraries", var) : 0;
 }
 int stat_cell_refused(const agx_ctx* c, int n, int var) {
-  if (stat_not_kept(AGX_NEQ == 5 && (n == 10 || n == 11), var)) return 1;
+  if (stat_not_kept(!kept_stat_index(n), var)) return 1;
   if (n == 9 && stat_nx(c) == 0)
     return fail("agx_output_pack: statistics variable %d (mean turbulentViscosity): this "
                 "context has no eddy viscosity (largeEddySimulation and the rans libraries "
@@ -3031,9 +2880,7 @@ int stats_sample(agx_ctx* c, int id, double w) {
   if (!c->finalized) return fail("agx_setup_finalize has not been called");
   const bool wall = stat_wall_values(c, b) > 0;
   if (wall) {
-    if (b.d.wallv && !c->have_wall_data)
-      return fail("agx_field_upload: AGX_FIELD_STAT_SAMPLE: the wall-law surfaces hold no wall "
-                  "data before the first residual");
+    if (wall_data_missing(c, b, "agx_field_upload", "AGX_FIELD_STAT_SAMPLE")) return 1;
     // the wall faces are evaluated with the ghost cells the next residual would see
     if (ghosts_for_output(c, "agx_field_upload")) return 1;
   }
@@ -3049,13 +2896,10 @@ int stats_sample(agx_ctx* c, int id, double w) {
                          c->gas, ncell, pitch, r, cf, b.stat_cells.get());
     return 0;
   });
-  if (wall) {
-    const int fourth = (c->cfg.viscous_recon == AGX_VISC_RECON_CENTRAL_4TH ? 1 : 0) |
-                       (c->sp.les ? 2 : 0);
+  if (wall)
     hipLaunchKernelGGL(k_stats_wall, dim3((unsigned)((b.wall_faces + 255) / 256)), dim3(256), 0,
                        c->stream, b.d, c->gas, b.wall_tab_dev.get(), (int)b.wall_tab.size(),
-                       b.wall_faces, fourth, r, cf, b.stat_wall.get());
-  }
+                       b.wall_faces, wall_eval_flags(c), r, cf, b.stat_wall.get());
   HIPCHK(hipGetLastError());
   b.stat_W = W;
   b.stat_n += 1.0;
@@ -3063,10 +2907,9 @@ int stats_sample(agx_ctx* c, int id, double w) {
 }
 }  // namespace
 
+// (agx_field_upload has flushed and has checked the block id and the pointer, for the series
+// and the spectra below as well)
 static int stats_field_upload(agx_ctx* c, int id, int field, const double* in) {
-  if (flush_consn(c)) return 1;
-  if (id < 0 || id >= (int)c->blocks.size()) return fail("bad block id %d", id);
-  if (!in) return fail("agx_field_upload: null pointer");
   if (!c->have_cfg) return fail("agx_config_set has not been called");
   if (field == AGX_FIELD_STAT_SAMPLE) return stats_sample(c, id, in[0]);
   if (!c->finalized) return fail("agx_setup_finalize has not been called");
@@ -3101,9 +2944,7 @@ static int stats_field_download(agx_ctx* c, int id, int field, double* out) {
     return fail("agx_field_download: AGX_FIELD_STAT_SAMPLE is upload only (a sample's weight); "
                 "AGX_FIELD_STAT_ACCUM holds the accumulators");
   Block& b = c->blocks[id];
-  if (!b.stat_cells)
-    return fail("agx_field_download: AGX_FIELD_STAT_ACCUM: block %d has no statistics: no "
-                "sample has been taken (AGX_FIELD_STAT_SAMPLE)", id);
+  if (!b.stat_cells) return no_statistics("agx_field_download: AGX_FIELD_STAT_ACCUM", id);
   if (!stats_fit(c, b)) return stats_misfit("agx_field_download", id);
   const int np = stat_planes(c), nwv = stat_wall_values(c, b);
   const long ncell = stat_ncell(b), pitch = stat_pitch(b);
@@ -3131,14 +2972,11 @@ static int stats_pack(agx_ctx* c, int id, bool wall, int nvar, const int32_t* va
   int32_t ids[AGX_OUT_COUNT];
   for (int v = 0; v < nvar; ++v) {
     ids[v] = vars[v] - (wall ? AGX_WSTAT_BASE : AGX_STAT_BASE);
-    const int wv = AGX_WALL_YPLUS + ids[v];
-    if (wall ? stat_not_kept(AGX_NEQ == 5 && (wv == AGX_WALL_TKE || wv == AGX_WALL_SDR), vars[v])
+    if (wall ? stat_not_kept(!kept_wall_id(AGX_WALL_YPLUS + ids[v]), vars[v])
              : stat_cell_refused(c, ids[v], vars[v]))
       return 1;
   }
-  if (!b.stat_cells)
-    return fail("agx_output_pack: block %d has no statistics: no sample has been taken "
-                "(AGX_FIELD_STAT_SAMPLE)", id);
+  if (!b.stat_cells) return no_statistics("agx_output_pack", id);
   if (!stats_fit(c, b)) return stats_misfit("agx_output_pack", id);
   const long n = wall ? b.wall_faces : stat_ncell(b);
   double* tmp = nullptr;
@@ -3183,9 +3021,7 @@ static int stats_collapse(agx_ctx* c, int id, int nvar, const int32_t* vars, dou
       cs.means |= 1u << stat_second_a(n - 12) | 1u << stat_second_b(n - 12);
     }
   }
-  if (!b.stat_cells)
-    return fail("agx_output_pack: block %d has no statistics: no sample has been taken "
-                "(AGX_FIELD_STAT_SAMPLE)", id);
+  if (!b.stat_cells) return no_statistics("agx_output_pack", id);
   if (!stats_fit(c, b)) return stats_misfit("agx_output_pack", id);
   const long ni = b.d.ni, nj = b.d.nj, nk = b.d.nk;
   cs.pitch = stat_pitch(b);
@@ -3216,31 +3052,18 @@ static int stats_collapse(agx_ctx* c, int id, int nvar, const int32_t* vars, dou
 
 // ---- time series (agx_series.hpp; include/aither_gfx950.h at AGX_FIELD_SERIES_PLAN) ----------
 namespace {
-// entry `at` of a payload as an integer in [lo, hi]; refuses by name, saying which entry
-int series_entry(const char* field, const double* in, long at, const char* what, double lo,
-                 double hi, long* out) {
-  const double x = in[at];
-  if (!std::isfinite(x) || x != std::floor(x) || x < lo || x > hi)
-    return fail("agx_field_upload: %s: entry %ld (%s) is %g: an integer from %.0f to %.0f is "
-                "expected", field, at, what, x, lo, hi);
-  *out = (long)x;
-  return 0;
-}
 constexpr double SERIES_MAX_COUNT = 16777216.0;     // points of a plan or a locate, rows of a ring
 // ids of a plan that this library does not keep (the 5-equation libraries: the rans variables)
 int series_id_refused(const agx_ctx* c, const Block& b, int id, int kind, int var) {
   if (kind == 0) {
-    const bool rans = var == AGX_OUT_TKE || var == AGX_OUT_SDR || var == AGX_OUT_F1 ||
-                      var == AGX_OUT_F2 || (var >= AGX_OUT_TKEGRAD && var < AGX_OUT_RESID) ||
-                      var >= AGX_OUT_RESID + 5;
-    if (AGX_NEQ == 5 && rans)
+    if (!kept_cell_id(var))
       return fail("agx_field_upload: AGX_FIELD_SERIES_PLAN: variable %d (tke, sdr, f1, f2, "
                   "their gradients and residuals) is not kept by the 5-equation libraries", var);
     if (var == AGX_OUT_VISCOSITY && !c->sp.viscous)
       return fail("viscosity_ is only kept for viscous runs (procBlock.cpp:6171)");
     return 0;
   }
-  if (AGX_NEQ == 5 && (var == AGX_WALL_TKE || var == AGX_WALL_SDR))
+  if (!kept_wall_id(var))
     return fail("agx_field_upload: AGX_FIELD_SERIES_PLAN: wall variable %d (tke, sdr) is not "
                 "kept by the 5-equation libraries", var);
   if (!c->cfg.is_viscous)
@@ -3251,29 +3074,25 @@ int series_id_refused(const agx_ctx* c, const Block& b, int id, int kind, int va
                 id);
   return 0;
 }
-int series_no_plan(const char* call, const char* field, int id) {
-  return fail("%s: %s: block %d has no plan (upload AGX_FIELD_SERIES_PLAN first)", call, field,
-              id);
-}
 int series_plan_upload(agx_ctx* c, int id, const double* in) {
   static const char F[] = "AGX_FIELD_SERIES_PLAN";
   Block& b = c->blocks[id];
   long kind, P, V, cap;
-  if (series_entry(F, in, 0, "kind: 0 cells, 1 wall faces", 0, 1, &kind)) return 1;
-  if (series_entry(F, in, 1, "P, the points", 0, SERIES_MAX_COUNT, &P)) return 1;
+  if (payload_entry(F, in, 0, "kind: 0 cells, 1 wall faces", 0, 1, &kind)) return 1;
+  if (payload_entry(F, in, 1, "P, the points", 0, SERIES_MAX_COUNT, &P)) return 1;
   if (P == 0) {
     HIPCHK(hipStreamSynchronize(c->stream));     // (before the rows are freed)
     b.series = Block::Series();
     return 0;
   }
-  if (series_entry(F, in, 2, "V, the variables", 1, AGX_OUT_COUNT, &V)) return 1;
-  if (series_entry(F, in, 3, "capacity, the rows of the record", 1, SERIES_MAX_COUNT, &cap))
+  if (payload_entry(F, in, 2, "V, the variables", 1, AGX_OUT_COUNT, &V)) return 1;
+  if (payload_entry(F, in, 3, "capacity, the rows of the record", 1, SERIES_MAX_COUNT, &cap))
     return 1;
   Block::Series s;
   s.kind = (int)kind; s.V = (int)V; s.P = P; s.wall_epoch = b.wall_epoch;
   for (long v = 0; v < V; ++v) {
     long var;
-    if (series_entry(F, in, 4 + v, "a variable id", 0, 2147483647.0, &var)) return 1;
+    if (payload_entry(F, in, 4 + v, "a variable id", 0, 2147483647.0, &var)) return 1;
     if (kind == 0 ? var >= AGX_OUT_COUNT : var < AGX_WALL_YPLUS || var >= AGX_WALL_END)
       return fail("agx_field_upload: %s: entry %ld: unknown output variable %ld (a plan of "
                   "kind %ld holds %s)", F, 4 + v, var, kind,
@@ -3289,10 +3108,10 @@ int series_plan_upload(agx_ctx* c, int id, const double* in) {
     if (kind == 0) {
       long ijk[3];
       for (int d = 0; d < 3; ++d)
-        if (series_entry(F, in, 4 + V + 3 * p + d, d == 0 ? "i of a cell" : d == 1 ? "j of a cell"
+        if (payload_entry(F, in, 4 + V + 3 * p + d, d == 0 ? "i of a cell" : d == 1 ? "j of a cell"
                          : "k of a cell", 0, nn[d] - 1, &ijk[d])) return 1;
       pts[p] = (ijk[2] * b.d.nj + ijk[1]) * b.d.ni + ijk[0];
-    } else if (series_entry(F, in, 4 + V + p, "a face of the wall payload", 0,
+    } else if (payload_entry(F, in, 4 + V + p, "a face of the wall payload", 0,
                             (double)(b.wall_faces - 1), &pts[p])) {
       return 1;
     }
@@ -3312,7 +3131,7 @@ int series_sample(agx_ctx* c, int id, double t) {
   static const char F[] = "AGX_FIELD_SERIES_SAMPLE";
   Block& b = c->blocks[id];
   Block::Series& s = b.series;
-  if (s.payload.empty()) return series_no_plan("agx_field_upload", F, id);
+  if (s.payload.empty()) return no_plan("agx_field_upload", F, id, "AGX_FIELD_SERIES_PLAN");
   if (!std::isfinite(t)) return fail("agx_field_upload: %s: the time %g is not finite", F, t);
   if (s.ring.full())
     return fail("agx_field_upload: %s: the record of block %d is full (%ld rows, its capacity): "
@@ -3323,25 +3142,20 @@ int series_sample(agx_ctx* c, int id, double t) {
     if (s.wall_epoch != b.wall_epoch)
       return fail("agx_field_upload: %s: the wall surfaces of block %d changed since its plan was "
                   "uploaded; upload the plan again (AGX_FIELD_SERIES_PLAN)", F, id);
-    if (b.d.wallv && !c->have_wall_data)
-      return fail("agx_field_upload: %s: the wall-law surfaces hold no wall data before the first "
-                  "residual", F);
+    if (wall_data_missing(c, b, "agx_field_upload", F)) return 1;
   }
   // gradients and wall faces are evaluated with the ghost cells the next residual would see
   if ((wall || s.grads) && ghosts_for_output(c, "agx_field_upload")) return 1;
   double* row = s.rows.get() + (size_t)s.ring.next() * s.V * s.P;
   const dim3 grid((unsigned)((s.P * s.V + 255) / 256));
   const OutSpec sp = out_spec(c, b, s.V, s.var);
-  if (wall) {
-    const int fourth = (c->cfg.viscous_recon == AGX_VISC_RECON_CENTRAL_4TH ? 1 : 0) |
-                       (c->sp.les ? 2 : 0);
+  if (wall)
     hipLaunchKernelGGL(k_series_wall, grid, dim3(256), 0, c->stream, b.d, c->gas, sp,
-                       b.wall_tab_dev.get(), (int)b.wall_tab.size(), fourth, s.pts.get(), s.P,
-                       row);
-  } else {
+                       b.wall_tab_dev.get(), (int)b.wall_tab.size(), wall_eval_flags(c),
+                       s.pts.get(), s.P, row);
+  else
     hipLaunchKernelGGL(k_series_cells, grid, dim3(256), 0, c->stream, b.d, c->gas, sp,
                        s.pts.get(), s.P, row);
-  }
   HIPCHK(hipGetLastError());
   s.t[(size_t)s.ring.next()] = t;
   s.ring.push();
@@ -3350,7 +3164,7 @@ int series_sample(agx_ctx* c, int id, double t) {
 int series_drop(agx_ctx* c, int id, double n) {
   static const char F[] = "AGX_FIELD_SERIES_ROWS";
   Block::Series& s = c->blocks[id].series;
-  if (s.payload.empty()) return series_no_plan("agx_field_upload", F, id);
+  if (s.payload.empty()) return no_plan("agx_field_upload", F, id, "AGX_FIELD_SERIES_PLAN");
   if (!std::isfinite(n) || n != std::floor(n) || n < 0.0 || n > (double)s.ring.count)
     return fail("agx_field_upload: %s: cannot drop %g rows: the record of block %d holds %ld "
                 "(an integer from 0 to that)", F, n, id, s.ring.count);
@@ -3361,7 +3175,7 @@ int series_locate(agx_ctx* c, int id, const double* in) {
   static const char F[] = "AGX_FIELD_SERIES_LOCATE";
   Block& b = c->blocks[id];
   long P;
-  if (series_entry(F, in, 0, "P, the points", 1, SERIES_MAX_COUNT, &P)) return 1;
+  if (payload_entry(F, in, 0, "P, the points", 1, SERIES_MAX_COUNT, &P)) return 1;
   for (long n = 0; n < 3 * P; ++n)
     if (!(std::fabs(in[1 + n]) <= 1e150))
       return fail("agx_field_upload: %s: entry %ld (coordinate %ld of point %ld) is %g: a finite "
@@ -3387,9 +3201,6 @@ int series_locate(agx_ctx* c, int id, const double* in) {
 }  // namespace
 
 static int series_field_upload(agx_ctx* c, int id, int field, const double* in) {
-  if (flush_consn(c)) return 1;
-  if (id < 0 || id >= (int)c->blocks.size()) return fail("bad block id %d", id);
-  if (!in) return fail("agx_field_upload: null pointer");
   if (!c->finalized) return fail("agx_setup_finalize has not been called");
   switch (field) {
     case AGX_FIELD_SERIES_PLAN: return series_plan_upload(c, id, in);
@@ -3412,8 +3223,8 @@ static int series_field_download(agx_ctx* c, int id, int field, double* out) {
     return copy_out(c, out, b.locate_out.get(), (size_t)4 * b.locate_n);
   }
   if (s.payload.empty())
-    return series_no_plan("agx_field_download", field == AGX_FIELD_SERIES_PLAN
-                          ? "AGX_FIELD_SERIES_PLAN" : "AGX_FIELD_SERIES_ROWS", id);
+    return no_plan("agx_field_download", field == AGX_FIELD_SERIES_PLAN
+                   ? "AGX_FIELD_SERIES_PLAN" : "AGX_FIELD_SERIES_ROWS", id, "AGX_FIELD_SERIES_PLAN");
   if (field == AGX_FIELD_SERIES_PLAN) {
     std::copy(s.payload.begin(), s.payload.end(), out);
     return 0;
@@ -3443,17 +3254,13 @@ static int series_field_download(agx_ctx* c, int id, int field, double* out) {
 
 // ---- spectra (agx_spectra.hpp; include/aither_gfx950.h at AGX_FIELD_SPECTRA_PLAN) ------------
 namespace {
-int spectra_no_plan(const char* call, const char* field, int id) {
-  return fail("%s: %s: block %d has no plan (upload AGX_FIELD_SPECTRA_PLAN first)", call, field,
-              id);
-}
 // doubles of a plan payload; the header of an accumulator payload follows it
 size_t spectra_plan_size(const SpectraShape& s) { return 4 + (size_t)s.nvar + 2 * (size_t)s.npair; }
 int spectra_plan_upload(agx_ctx* c, int id, const double* in) {
   static const char F[] = "AGX_FIELD_SPECTRA_PLAN";
   Block& b = c->blocks[id];
   long along, over, nvar, npair;
-  if (series_entry(F, in, 2, "nvar, the variables", 0, 2147483647.0, &nvar)) return 1;
+  if (payload_entry(F, in, 2, "nvar, the variables", 0, 2147483647.0, &nvar)) return 1;
   if (nvar == 0) {
     HIPCHK(hipStreamSynchronize(c->stream));     // (before the memory is freed)
     b.spectra = Block::Spectra();
@@ -3462,9 +3269,9 @@ int spectra_plan_upload(agx_ctx* c, int id, const double* in) {
   if (nvar > SPECTRA_MAX_VAR)
     return fail("agx_field_upload: %s: nvar = %ld: a plan holds at most %d variables", F, nvar,
                 SPECTRA_MAX_VAR);
-  if (series_entry(F, in, 0, "along: 0 i, 1 j, 2 k", 0, 2, &along)) return 1;
-  if (series_entry(F, in, 1, "over, the mask of the pooled directions", 0, 7, &over)) return 1;
-  if (series_entry(F, in, 3, "npair, the pairs", 0, SPECTRA_MAX_PAIR, &npair)) return 1;
+  if (payload_entry(F, in, 0, "along: 0 i, 1 j, 2 k", 0, 2, &along)) return 1;
+  if (payload_entry(F, in, 1, "over, the mask of the pooled directions", 0, 7, &over)) return 1;
+  if (payload_entry(F, in, 3, "npair, the pairs", 0, SPECTRA_MAX_PAIR, &npair)) return 1;
   if (over >> along & 1)
     return fail("agx_field_upload: %s: over (mask %ld) contains along (%ld): a direction is "
                 "transformed or pooled, not both", F, over, along);
@@ -3478,7 +3285,7 @@ int spectra_plan_upload(agx_ctx* c, int id, const double* in) {
                                 AGX_OUT_PRESSURE, AGX_OUT_TEMPERATURE};
   for (long v = 0; v < nvar; ++v) {
     long var;
-    if (series_entry(F, in, 4 + v, "a variable id", 0, 2147483647.0, &var)) return 1;
+    if (payload_entry(F, in, 4 + v, "a variable id", 0, 2147483647.0, &var)) return 1;
     int code = -1;
     for (int n = 0; n < 6; ++n)
       if (var == OUT_ID[n]) code = n;
@@ -3495,7 +3302,7 @@ int spectra_plan_upload(agx_ctx* c, int id, const double* in) {
   for (long p = 0; p < npair; ++p) {
     long ab[2];
     for (int e = 0; e < 2; ++e)
-      if (series_entry(F, in, 4 + nvar + 2 * p + e, "a variable of a pair, an index into the "
+      if (payload_entry(F, in, 4 + nvar + 2 * p + e, "a variable of a pair, an index into the "
                        "plan's variables", 0, (double)(nvar - 1), &ab[e])) return 1;
     if (ab[0] == ab[1])
       return fail("agx_field_upload: %s: pair %ld is (%ld, %ld): the auto-spectrum of a variable "
@@ -3539,7 +3346,7 @@ int spectra_sample(agx_ctx* c, int id, double w) {
   static const char F[] = "AGX_FIELD_SPECTRA_SAMPLE";
   Block& b = c->blocks[id];
   Block::Spectra& sp = b.spectra;
-  if (sp.payload.empty()) return spectra_no_plan("agx_field_upload", F, id);
+  if (sp.payload.empty()) return no_plan("agx_field_upload", F, id, "AGX_FIELD_SPECTRA_PLAN");
   if (!std::isfinite(w) || w < 0.0)
     return fail("agx_field_upload: %s: the weight %g is negative or not finite (w > 0 samples, "
                 "w == 0 resets the block's spectra)", F, w);
@@ -3573,7 +3380,7 @@ int spectra_sample(agx_ctx* c, int id, double w) {
 int spectra_accum_upload(agx_ctx* c, int id, const double* in) {
   static const char F[] = "AGX_FIELD_SPECTRA_ACCUM";
   Block::Spectra& sp = c->blocks[id].spectra;
-  if (sp.payload.empty()) return spectra_no_plan("agx_field_upload", F, id);
+  if (sp.payload.empty()) return no_plan("agx_field_upload", F, id, "AGX_FIELD_SPECTRA_PLAN");
   const SpectraShape& s = sp.dev.s;
   const size_t np = spectra_plan_size(s);
   for (size_t n = 0; n < np; ++n)
@@ -3598,9 +3405,6 @@ int spectra_accum_upload(agx_ctx* c, int id, const double* in) {
 }  // namespace
 
 static int spectra_field_upload(agx_ctx* c, int id, int field, const double* in) {
-  if (flush_consn(c)) return 1;
-  if (id < 0 || id >= (int)c->blocks.size()) return fail("bad block id %d", id);
-  if (!in) return fail("agx_field_upload: null pointer");
   if (!c->finalized) return fail("agx_setup_finalize has not been called");
   switch (field) {
     case AGX_FIELD_SPECTRA_PLAN: return spectra_plan_upload(c, id, in);
@@ -3608,7 +3412,7 @@ static int spectra_field_upload(agx_ctx* c, int id, int field, const double* in)
     case AGX_FIELD_SPECTRA_ACCUM: return spectra_accum_upload(c, id, in);
   }
   if (c->blocks[id].spectra.payload.empty())
-    return spectra_no_plan("agx_field_upload", "AGX_FIELD_SPECTRA_VALUES", id);
+    return no_plan("agx_field_upload", "AGX_FIELD_SPECTRA_VALUES", id, "AGX_FIELD_SPECTRA_PLAN");
   return fail("agx_field_upload: AGX_FIELD_SPECTRA_VALUES is download only (the dimensional "
               "spectra); AGX_FIELD_SPECTRA_ACCUM carries an average on");
 }
@@ -3622,8 +3426,8 @@ static int spectra_field_download(agx_ctx* c, int id, int field, double* out) {
                 ? "AGX_FIELD_SPECTRA_PLAN" : "AGX_FIELD_SPECTRA_SAMPLE");
   const bool raw = field == AGX_FIELD_SPECTRA_ACCUM;
   if (sp.payload.empty())
-    return spectra_no_plan("agx_field_download", raw ? "AGX_FIELD_SPECTRA_ACCUM"
-                           : "AGX_FIELD_SPECTRA_VALUES", id);
+    return no_plan("agx_field_download", raw ? "AGX_FIELD_SPECTRA_ACCUM"
+                   : "AGX_FIELD_SPECTRA_VALUES", id, "AGX_FIELD_SPECTRA_PLAN");
   const SpectraShape& s = sp.dev.s;
   const size_t nval = (size_t)spectra_values(s);
   if (raw) {
@@ -3638,6 +3442,99 @@ static int spectra_field_download(agx_ctx* c, int id, int field, double* out) {
   for (int n = 0; n < s.nvar + s.npair; ++n)
     for (size_t e = 0; e < per; ++e) out[n * per + e] = out[n * per + e] * sp.factor[n];
   return 0;
+}
+
+// ---- the entry points of the output: what they dispatch to is defined above ------------------
+int agx_field_download(agx_ctx* c, int id, int field, double* out) {
+  if (flush_consn(c)) return 1;
+  if (id < 0 || id >= (int)c->blocks.size()) return fail("bad block id %d", id);
+  if (agx::field_is_stats(field)) return stats_field_download(c, id, field, out);
+  if (agx::field_is_series(field)) return series_field_download(c, id, field, out);
+  if (agx::field_is_spectra(field)) return spectra_field_download(c, id, field, out);
+  Block& b = c->blocks[id];
+  // (the D2 arrays hold x with the writer's tag in its two lowest mantissa bits: while the
+  // planes are current -- an upload or a multigrid transfer wrote them last -- they are the
+  // untagged x itself, zero ghost cells of a restriction included)
+  if (field == AGX_FIELD_UPDATE && b.x_is_zero) {
+    const int g = b.d.ng;
+    memset(out, 0, sizeof(double) * AGX_NEQ * (size_t)(b.d.ni + 2 * g) * (b.d.nj + 2 * g) *
+                       (b.d.nk + 2 * g));
+    return 0;
+  }
+  if (field == AGX_FIELD_UPDATE && b.d.d2.base && !b.x_planes_current && d2_x_copy(c, b, 0))
+    return 1;
+  // (k_lusgs_prepare forms the diagonal inside the D2 arrays, as 1 / a beside x: the plane
+  // d.a keeps the spectral radii the residual summed, without the time term)
+  if (field == AGX_FIELD_DIAGONAL && b.d.d2.base)
+    return fail("agx_field_download: the diagonal-ordered LU-SGS path keeps the scalar diagonal "
+                "a_ only as 1 / a inside its sweep arrays, not as a field (AGX_LUSGS=plane, the "
+                "hyperplane form, keeps it)");
+  if (field >= AGX_FIELD_VEL_GRAD && field <= AGX_FIELD_PRESS_GRAD) {
+    // cell-centre gradients: formed on demand into a temporary (an output path)
+    const long ncell = (long)b.d.ni * b.d.nj * b.d.nk;
+    double* tmp = nullptr;
+    if (ghosts_for_output(c, "agx_field_download")) return 1;
+    if (stage_buffer(c, (size_t)3 * NGF * ncell, &tmp)) return 1;
+    hipLaunchKernelGGL(k_cell_grads, cell_grid(b.d, CELL_BLOCK), CELL_BLOCK, 0, c->stream, b.d,
+                       c->gas, tmp);
+    HIPCHK(hipGetLastError());
+    const int off = field == AGX_FIELD_VEL_GRAD ? 0 : 9 + 3 * (field - AGX_FIELD_TEMP_GRAD);
+    const int nc = field == AGX_FIELD_VEL_GRAD ? 9 : 3;
+    // strided device -> host copy of the requested columns
+    HIPCHK(hipMemcpy2DAsync(out, sizeof(double) * nc, tmp + off, sizeof(double) * 3 * NGF,
+                            sizeof(double) * nc, ncell, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(hipStreamSynchronize(c->stream));
+    return 0;
+  }
+  if (field == AGX_FIELD_TEMPERATURE || field == AGX_FIELD_VISCOSITY) {
+    // formed on demand from the current state into a scratch plane (the x_old
+    // plane of DPLUR: rebuilt at the start of every implicit iteration)
+    if (field == AGX_FIELD_VISCOSITY && !c->sp.viscous)
+      return fail("viscosity_ is only kept for viscous runs (procBlock.cpp:6171)");
+    double* scratch = b.d.xold[0];
+    hipLaunchKernelGGL(k_aux_field, dim3((b.d.nplane + 255) / 256), dim3(256), 0, c->stream,
+                       b.d, c->gas, field == AGX_FIELD_VISCOSITY ? 1 : 0, scratch);
+    HIPCHK(hipGetLastError());
+    double* one[1] = {scratch};
+    const int g = b.d.ng;
+    return download_aos(c, b, out, one, 1, b.d.ni + 2 * g, b.d.nj + 2 * g, b.d.nk + 2 * g, g);
+  }
+  double* const* p; int nc, gh;
+  if (!geom_field_info(b, field, &p, &nc, &gh)) {      // (gh: the face direction here)
+    if (b.node_built && !c->finalized)
+      return fail("the geometry of a node-built block is complete after agx_setup_finalize");
+    const int g = b.d.ng;
+    return download_aos(c, b, out, p, nc, b.d.ni + 2 * g + (gh == 0), b.d.nj + 2 * g + (gh == 1),
+                        b.d.nk + 2 * g + (gh == 2), g);
+  }
+  if (field_info(b, field, &p, &nc, &gh))
+    return fail("unknown field %d", field);
+  const int g = gh ? b.d.ng : 0;
+  return download_aos(c, b, out, p, nc, b.d.ni + 2 * g, b.d.nj + 2 * g, b.d.nk + 2 * g, g);
+}
+
+// The ids of a call are of one range of agx_out_ranges.hpp: its table holds the ranges, their
+// precedence and their bounds on nvar, its classifier the refusals of a call that has none
+int agx_output_pack(agx_ctx* c, int id, int nvar, const int32_t* vars, double* out) {
+  if (flush_consn(c)) return 1;
+  if (id < 0 || id >= (int)c->blocks.size()) return fail("bad block id %d", id);
+  const agx::OutCall call = agx::out_classify(nvar, vars);
+  switch (call.range) {
+    case agx::OUT_FLUX: return surface_fluxes(c, id, nvar, vars, out);
+    case agx::OUT_BUDGET: return block_budget(c, id, nvar, vars, out);
+    case agx::OUT_CSTAT: return stats_collapse(c, id, nvar, vars, out);
+    case agx::OUT_WSTAT: return stats_pack(c, id, true, nvar, vars, out);
+    case agx::OUT_STAT: return stats_pack(c, id, false, nvar, vars, out);
+    case agx::OUT_LOAD: return wall_loads(c, id, nvar, vars, out);
+    case agx::OUT_NODE: {
+      int32_t ids[AGX_OUT_COUNT];
+      for (int v = 0; v < nvar; ++v) ids[v] = vars[v] - AGX_NODE_BASE;
+      return point_pack(c, id, true, nvar, ids, out);
+    }
+    case agx::OUT_WALL: return wall_pack(c, id, nvar, vars, out);
+    case agx::OUT_CELL: return point_pack(c, id, false, nvar, vars, out);
+  }
+  return fail("%s", call.refusal);
 }
 
 int agx_restart_pack(agx_ctx* c, int id, int which, double* out) {
@@ -3837,16 +3734,18 @@ int agx_field_upload(agx_ctx* c, int id, int field, const double* in) {
   // (an upload of x writes this block's planes and, on the D2 path, copies them to its D2
   // arrays below: the planes of this block are current afterwards, those of the other blocks
   // are what they were)
-  // (the two statistics fields write nothing the solver reads: a sample is a read of the run
-  // and leaves every flag as a read would)
-  if (field == AGX_FIELD_STAT_SAMPLE || field == AGX_FIELD_STAT_ACCUM)
-    return stats_field_upload(c, id, field, in);
-  // (nor do the time-series fields: a sample is a read, a plan and a locate own their memory)
-  if (field >= AGX_FIELD_SERIES_PLAN && field <= AGX_FIELD_SERIES_LOCATE)
-    return series_field_upload(c, id, field, in);
-  // (nor do the spectra: a sample is a read, a plan and an upload of S own their memory)
-  if (field >= AGX_FIELD_SPECTRA_PLAN && field <= AGX_FIELD_SPECTRA_VALUES)
-    return spectra_field_upload(c, id, field, in);
+  // (the statistics, the time series and the spectra write nothing the solver reads: a sample
+  // is a read of the run and leaves every flag as a read would, a plan, a locate and an upload
+  // of accumulators own their memory)
+  const bool stats = agx::field_is_stats(field), series = agx::field_is_series(field);
+  if (stats || series || agx::field_is_spectra(field)) {
+    if (flush_consn(c)) return 1;
+    if (id < 0 || id >= (int)c->blocks.size()) return fail("bad block id %d", id);
+    if (!in) return fail("agx_field_upload: null pointer");
+    return stats    ? stats_field_upload(c, id, field, in)
+           : series ? series_field_upload(c, id, field, in)
+                    : spectra_field_upload(c, id, field, in);
+  }
   field_written_by_caller(c);
   if (flush_consn(c)) return 1;
   if (id < 0 || id >= (int)c->blocks.size()) return fail("bad block id %d", id);

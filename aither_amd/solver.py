@@ -342,28 +342,40 @@ class Solver:
                                        a.ctypes.data_as(abi.c_dp))
         self.api.check(rc, "upload")
 
+    def _pack(self, gb, ids, shape):
+        """agx_output_pack of block gb with these ids (of one range) into a new array."""
+        ids = (C.c_int32 * len(ids))(*ids)
+        out = np.empty(shape)
+        self.api.check(self.api.output_pack(self.ctx, self.block_ids[gb], len(ids), ids,
+                                            out.ctypes.data_as(abi.c_dp)), "output_pack")
+        return out
+
+    @staticmethod
+    def _per_surface(surfs, names, out):
+        """A [nvar, total] wall payload as {name: [one array per surface, in its shape]}."""
+        res = {}
+        for q, name in enumerate(names):
+            off, rows = 0, []
+            for s in surfs:
+                cnt = int(np.prod(s["shape"]))
+                rows.append(out[q, off:off + cnt].reshape(s["shape"]).copy())
+                off += cnt
+            res[name] = rows
+        return res
+
     def output_pack(self, gb, names):
         """WriteFunFile's variables of block gb (reference names, abi.OUT), packed by the
         library: [nvar, nk, nj, ni], dimensional."""
-        g = self.case.blocks[gb].geom
-        ni, nj, nk = g.n
-        ids = (C.c_int32 * len(names))(*[abi.OUT[n] for n in names])
-        out = np.empty((len(names), nk, nj, ni))
-        self.api.check(self.api.output_pack(self.ctx, self.block_ids[gb], len(names), ids,
-                                            out.ctypes.data_as(abi.c_dp)), "output_pack")
-        return out
+        ni, nj, nk = self.case.blocks[gb].geom.n
+        return self._pack(gb, [abi.OUT[n] for n in names], (len(names), nk, nj, ni))
 
     def node_pack(self, gb, names):
         """WriteNodeFun's variables of block gb (reference names, abi.NODE_OUT), converted to
         the block's nodes and packed by the library: [nvar, nk + 1, nj + 1, ni + 1],
         dimensional."""
-        g = self.case.blocks[gb].geom
-        ni, nj, nk = g.n
-        ids = (C.c_int32 * len(names))(*[abi.NODE_OUT[n] for n in names])
-        out = np.empty((len(names), nk + 1, nj + 1, ni + 1))
-        self.api.check(self.api.output_pack(self.ctx, self.block_ids[gb], len(names), ids,
-                                            out.ctypes.data_as(abi.c_dp)), "output_pack")
-        return out
+        ni, nj, nk = self.case.blocks[gb].geom.n
+        return self._pack(gb, [abi.NODE_OUT[n] for n in names],
+                          (len(names), nk + 1, nj + 1, ni + 1))
 
     def wall_surfaces(self, gb):
         """The viscousWall surfaces of block gb in the order of the wall payload (the order
@@ -388,19 +400,8 @@ class Solver:
         dimensional.  A name given twice keeps its last row."""
         surfs = self.wall_surfaces(gb)
         total = sum(int(np.prod(s["shape"])) for s in surfs)
-        ids = (C.c_int32 * len(names))(*[abi.WALL_OUT[n] for n in names])
-        out = np.empty((len(names), total))
-        self.api.check(self.api.output_pack(self.ctx, self.block_ids[gb], len(names), ids,
-                                            out.ctypes.data_as(abi.c_dp)), "output_pack")
-        res = {}
-        for q, name in enumerate(names):
-            off, rows = 0, []
-            for s in surfs:
-                cnt = int(np.prod(s["shape"]))
-                rows.append(out[q, off:off + cnt].reshape(s["shape"]).copy())
-                off += cnt
-            res[name] = rows
-        return res
+        out = self._pack(gb, [abi.WALL_OUT[n] for n in names], (len(names), total))
+        return self._per_surface(surfs, names, out)
 
     def load_surfaces(self, gb):
         """The load surfaces of block gb -- viscousWall and slipWall -- in the order of the
@@ -438,10 +439,7 @@ class Solver:
                 if any(n.startswith(kind + "Moment") for n in names):
                     ask += [f"{kind}Force_{c}" for c in "xyz" if f"{kind}Force_{c}" not in ask]
         nsurf = len(self.load_surfaces(gb))
-        ids = (C.c_int32 * len(ask))(*[abi.LOAD_OUT[n] for n in ask])
-        out = np.empty((len(ask), max(nsurf, 1)))
-        self.api.check(self.api.output_pack(self.ctx, self.block_ids[gb], len(ask), ids,
-                                            out.ctypes.data_as(abi.c_dp)), "output_pack")
+        out = self._pack(gb, [abi.LOAD_OUT[n] for n in ask], (len(ask), max(nsurf, 1)))
         got = {n: out[q, :nsurf].copy() for q, n in enumerate(ask)}
         if about is not None:
             r = [float(x) for x in about]
@@ -519,10 +517,7 @@ class Solver:
         out of the block; inviscid_e + viscous_e is the net outward flux of equation e."""
         names = list(self.flux_names() if names is None else names)
         nsurf = len(self.flux_surfaces(gb))
-        ids = (C.c_int32 * len(names))(*[abi.FLUX_OUT[n] for n in names])
-        out = np.empty((len(names), max(nsurf, 1)))
-        self.api.check(self.api.output_pack(self.ctx, self.block_ids[gb], len(names), ids,
-                                            out.ctypes.data_as(abi.c_dp)), "output_pack")
+        out = self._pack(gb, [abi.FLUX_OUT[n] for n in names], (len(names), max(nsurf, 1)))
         return {n: out[q, :nsurf].copy() for q, n in enumerate(names)}
 
     def block_budget(self, gb, names=None):
@@ -530,10 +525,7 @@ class Solver:
         -- the volume, the conserved totals of the state now and the sums of the residual as
         the last residual pass left it."""
         names = list(self.flux_names(abi.BUDGET_OUT) if names is None else names)
-        ids = (C.c_int32 * len(names))(*[abi.BUDGET_OUT[n] for n in names])
-        out = np.empty(len(names))
-        self.api.check(self.api.output_pack(self.ctx, self.block_ids[gb], len(names), ids,
-                                            out.ctypes.data_as(abi.c_dp)), "output_pack")
+        out = self._pack(gb, [abi.BUDGET_OUT[n] for n in names], len(names))
         return {n: float(out[q]) for q, n in enumerate(names)}
 
     def flux_balance(self, gb):
@@ -635,11 +627,7 @@ class Solver:
         """Time statistics of block gb's cells (abi.STAT_OUT), shaped like output_pack:
         [nvar, nk, nj, ni], dimensional."""
         ni, nj, nk = self.case.blocks[gb].geom.n
-        ids = (C.c_int32 * len(names))(*[abi.STAT_OUT[n] for n in names])
-        out = np.empty((len(names), nk, nj, ni))
-        self.api.check(self.api.output_pack(self.ctx, self.block_ids[gb], len(names), ids,
-                                            out.ctypes.data_as(abi.c_dp)), "output_pack")
-        return out
+        return self._pack(gb, [abi.STAT_OUT[n] for n in names], (len(names), nk, nj, ni))
 
     def stats_collapse(self, gb, names, over):
         """Time statistics of block gb's cells (abi.STAT_OUT and "volume") pooled, volume
@@ -650,30 +638,16 @@ class Solver:
         mask = abi.cstat_mask(over)
         ni, nj, nk = self.case.blocks[gb].geom.n
         rest = tuple(n for bit, n in ((4, nk), (2, nj), (1, ni)) if not mask & bit)
-        ids = (C.c_int32 * len(names))(*[abi.cstat_id(mask, n) for n in names])
-        out = np.empty((len(names),) + rest)
-        self.api.check(self.api.output_pack(self.ctx, self.block_ids[gb], len(names), ids,
-                                            out.ctypes.data_as(abi.c_dp)), "output_pack")
-        return out
+        return self._pack(gb, [abi.cstat_id(mask, n) for n in names], (len(names),) + rest)
 
     def wall_stats_pack(self, gb, names):
         """Time statistics of block gb's viscousWall faces (abi.WALL_STAT_OUT), shaped like
         wall_pack: {name: [one array per wall surface]}, dimensional."""
         surfs = self.wall_surfaces(gb)
         total = sum(int(np.prod(s["shape"])) for s in surfs)
-        ids = (C.c_int32 * len(names))(*[abi.WALL_STAT_OUT[n] for n in names])
-        out = np.empty((len(names), max(total, 1)))
-        self.api.check(self.api.output_pack(self.ctx, self.block_ids[gb], len(names), ids,
-                                            out.ctypes.data_as(abi.c_dp)), "output_pack")
-        res = {}
-        for q, name in enumerate(names):
-            off, rows = 0, []
-            for s in surfs:
-                cnt = int(np.prod(s["shape"]))
-                rows.append(out[q, off:off + cnt].reshape(s["shape"]).copy())
-                off += cnt
-            res[name] = rows
-        return res
+        out = self._pack(gb, [abi.WALL_STAT_OUT[n] for n in names],
+                         (len(names), max(total, 1)))
+        return self._per_surface(surfs, names, out)
 
     # -- time series at chosen cells and wall faces, recorded on the device ----------------
     def _series_up(self, gb, field, payload, what):
@@ -1098,98 +1072,18 @@ class MultigridSolver:
     def block_ids(self):
         return self.levels[0].block_ids
 
-    def download(self, field, gb, level=0):
-        return self.levels[level].download(field, gb)
-
-    def load_surfaces(self, gb, level=0):
-        return self.levels[level].load_surfaces(gb)
-
-    def wall_loads(self, gb, names=None, about=None, level=0):
-        return self.levels[level].wall_loads(gb, names, about)
-
-    def total_loads(self, tags=None, about=None, level=0):
-        return self.levels[level].total_loads(tags, about)
-
-    def flux_surfaces(self, gb, level=0):
-        return self.levels[level].flux_surfaces(gb)
-
-    def surface_fluxes(self, gb, names=None, level=0):
-        return self.levels[level].surface_fluxes(gb, names)
-
-    def block_budget(self, gb, names=None, level=0):
-        return self.levels[level].block_budget(gb, names)
-
-    # time statistics: those of the finest level
-    def stats_sample(self, weight=1.0):
-        return self.levels[0].stats_sample(weight)
-
-    def stats_reset(self):
-        return self.levels[0].stats_reset()
-
-    def stats_weight(self, gb):
-        return self.levels[0].stats_weight(gb)
-
-    def stats_pack(self, gb, names):
-        return self.levels[0].stats_pack(gb, names)
-
-    def stats_collapse(self, gb, names, over):
-        return self.levels[0].stats_collapse(gb, names, over)
-
-    def wall_stats_pack(self, gb, names):
-        return self.levels[0].wall_stats_pack(gb, names)
-
-    def stats_download(self, gb):
-        return self.levels[0].stats_download(gb)
-
-    def stats_upload(self, gb, payload):
-        return self.levels[0].stats_upload(gb, payload)
-
-    # time series: those of the finest level
-    def series_plan(self, gb, names, points, capacity, kind="cells"):
-        return self.levels[0].series_plan(gb, names, points, capacity, kind)
-
-    def series_sample(self, t):
-        return self.levels[0].series_sample(t)
-
-    def series_rows(self, gb):
-        return self.levels[0].series_rows(gb)
-
-    def series_drop(self, gb, n=None):
-        return self.levels[0].series_drop(gb, n)
-
-    def series_clear(self):
-        return self.levels[0].series_clear()
-
-    def series_locate(self, points):
-        return self.levels[0].series_locate(points)
-
-    def series_plan_located(self, where, names, capacity):
-        return self.levels[0].series_plan_located(where, names, capacity)
-
-    # spectra: those of the finest level
-    def spectra_plan(self, gb, names, pairs=(), along="i", over=""):
-        return self.levels[0].spectra_plan(gb, names, pairs, along, over)
-
-    def spectra_sample(self, weight=1.0):
-        return self.levels[0].spectra_sample(weight)
-
-    def spectra(self, gb):
-        return self.levels[0].spectra(gb)
-
-    def spectra_download(self, gb):
-        return self.levels[0].spectra_download(gb)
-
-    def spectra_upload(self, gb, payload):
-        return self.levels[0].spectra_upload(gb, payload)
-
-    def spectra_reset(self):
-        return self.levels[0].spectra_reset()
-
-    def spectra_clear(self):
-        return self.levels[0].spectra_clear()
-
-    def spectra_lines(self, gb):
-        return self.levels[0].spectra_lines(gb)
+    # What a Solver gives and the multigrid driver hands on.  Of the finest level: the time
+    # statistics, the time series, the spectra.
+    _OF_FINEST = (
+        "stats_sample", "stats_reset", "stats_weight", "stats_pack", "stats_collapse",
+        "wall_stats_pack", "stats_download", "stats_upload",
+        "series_plan", "series_sample", "series_rows", "series_drop", "series_clear",
+        "series_locate", "series_plan_located",
+        "spectra_plan", "spectra_sample", "spectra", "spectra_download", "spectra_upload",
+        "spectra_reset", "spectra_clear", "spectra_lines")
+    # Of any level, with level=0 after the Solver's own arguments.
+    _OF_LEVEL = ("download", "load_surfaces", "wall_loads", "total_loads", "flux_surfaces",
+                 "surface_fluxes", "block_budget")
 
     def _p(self, a, ctype):
         return a.ctypes.data_as(C.POINTER(ctype))
@@ -1305,3 +1199,22 @@ class MultigridSolver:
         for nn in range(iterations):
             out = self.step(nn)
         return out
+
+
+def _forwarder(name, leveled):
+    own = getattr(Solver, name).__code__.co_argcount - 1      # (its arguments, without self)
+
+    def method(self, *args, **kw):
+        level = 0
+        if leveled and len(args) > own:
+            *args, level = args
+        elif leveled:
+            level = kw.pop("level", 0)
+        return getattr(self.levels[level], name)(*args, **kw)
+    method.__name__ = name
+    method.__doc__ = getattr(Solver, name).__doc__
+    return method
+
+
+for _name in MultigridSolver._OF_FINEST + MultigridSolver._OF_LEVEL:
+    setattr(MultigridSolver, _name, _forwarder(_name, _name in MultigridSolver._OF_LEVEL))
